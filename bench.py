@@ -3,9 +3,18 @@
 bench.py -- VB outer iterations per second of the LDA hot path on SYN-NSF (M=128804, V=25319), K=50
 (BASELINE.json configs[1]), document-sharded over N MI355X of one node.
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
-           --master-port P bench.py --gpus N --steps K --warmup W
+           --master-port P bench.py --gpus N --steps K --warmup W [--full]
+
+A plain run does only what the headline needs: set-up, the clock warm-up, burn-in and warm-up, the K timed steps (with the
+roofline block, which the same steps' events give), the outputs when --dump-outputs is given, and the line.  --full adds
+everything else: the cold-start window, the ELBO plateau, the CPU baseline with its parity check and the side configurations
+(N = 1), the multi-GPU self-check (N > 1).
+
+--dump-outputs DIR writes the model state that the last timed step left, as a caller of train! receives it (update_host!), to
+DIR/<name>.npy: alpha (K, float64, as the device keeps it), beta (K x V), gamma and Elogtheta (K x documents of rank 0), float32.
+The inputs are seeded, so two builds run with the same arguments can be compared array by array.
 
 A "step" is one outer iteration of train! (src/LDA.jl:169-183) with checkelbo=Inf: fused E-step over this rank's
 documents, the Elogtheta_sum reduction, ONE all-reduce of the packed K*V+K statistics (N>1; RCCL inside libtmvb_hip.so
@@ -19,10 +28,11 @@ does, profiles/r6_lda_cold_vs_steady.txt), so today the two windows differ by 2 
 first brought to its operating point with `--burnin` (default 60) untimed iterations -- state preparation, like the
 corpus upload -- then W warm-up iterations, then exactly K timed iterations between barrier+synchronize pairs; the time
 is the MAX over ranks.  `value` is that steady-state rate; the cold-start rate of the same W+K window (what round 1
-reported) is carried in "cold_start".  The corpus is fixed as N grows ("scaling": "strong").
+reported) is carried in "cold_start" (--full).  The corpus is fixed as N grows ("scaling": "strong").
 
 Rank 0 prints ONE JSON line.  Besides the contract fields it carries
   roofline     : the E-step against the HBM roofline (algorithmic bytes, HIP-event timing on the launch stream),
+and with --full
   elbo_plateau : wall time until check_elbo!'s own stop rule (delta_elbo < tol = 1.0, src/modelutils.jl:580) fires from
                  a cold start with checkelbo = 1 -- or "reached": false after the iteration cap,
   cpu_baseline : the fp64 oracle (a port of the reference's CPU path -- the reference itself is Julia and cannot run
@@ -239,6 +249,27 @@ def write_detail(result):
     log("bench detail: " + json.dumps(result, default=str))
 
 
+DUMP_LIMIT = 64 * 1024 * 1024 - 4096        # bytes of --dump-outputs in all (the .npy headers inside the 64 MB)
+
+
+def dump_outputs(d, model, seed=0):
+    """--dump-outputs: the state the last timed step left (update_host!) -> d/<name>.npy.  alpha in float64 (the device's), the rest
+    in float32 (the device's).  Should the whole exceed DUMP_LIMIT, gamma and Elogtheta keep a fixed seeded sample of documents."""
+    import numpy as np
+    model.update_host()
+    out = {"alpha": np.asarray(model.alpha, dtype=np.float64), "beta": np.asarray(model.beta, dtype=np.float32)}
+    K, M = model.gamma.shape
+    room = (DUMP_LIMIT - sum(a.nbytes for a in out.values())) // (2 * 4 * K)
+    cols = slice(None) if room >= M else np.sort(np.random.default_rng(seed).choice(M, max(room, 0), replace=False))
+    out["gamma"] = np.asarray(model.gamma[:, cols], dtype=np.float32)
+    out["Elogtheta"] = np.asarray(model.Elogtheta[:, cols], dtype=np.float32)
+    os.makedirs(d, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(d, f"{name}.npy"), np.ascontiguousarray(a))
+    log(f"outputs of the last timed step -> {d}: " + ", ".join(f"{n} {a.shape} {a.dtype}" for n, a in out.items())
+        + ("" if room >= M else f" (gamma, Elogtheta: {room} of {M} documents, seed {seed})"))
+
+
 def usable_cpus():
     """CPUs this process may really use: the affinity mask and the cgroup CPU quota (containers often see every host
     core in os.cpu_count() while being limited to a few)."""
@@ -354,6 +385,11 @@ def main():
                          "an early one of its own)")
     ap.add_argument("--collective", choices=["lib", "torch"], default="lib",
                     help="lib: RCCL inside libtmvb_hip.so (tmvb_comm_allreduce); torch: torch.distributed all_reduce on the bound buffer")
+    ap.add_argument("--full", action="store_true",
+                    help="also the cold-start window, the ELBO plateau, the CPU baseline with its parity check and the side configurations (N = 1), "
+                         "the multi-GPU self-check (N > 1); the --no-* options below switch parts of it off")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the state the last timed step left (alpha, beta, gamma, Elogtheta of rank 0) as DIR/<name>.npy")
     ap.add_argument("--plateau-cap", type=int, default=4000)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-plateau", action="store_true")
@@ -556,10 +592,12 @@ def main():
     elapsed, estep_ms = run_window(eng, allreduce, args.burnin, args.warmup, args.steps)
     sweep_hist = eng.model.sweep_hist(viter + 1).tolist()
     n_launch = eng.model.estep_launches()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, eng.model)
 
     # ---- cold-start window (round 1's number), fresh state
     cold = None
-    if not args.no_cold:
+    if args.full and not args.no_cold:
         eng_c = make_engine()
         ar_c, comm_c = attach_comm(eng_c)
         el_c, ms_c = run_window(eng_c, ar_c, 0, args.warmup, args.steps)
@@ -577,7 +615,7 @@ def main():
     # all-gathered and compared, (ii) rank 0 alone runs the same 5 iterations on the WHOLE corpus on its own GPU (N = 1) and the
     # two ELBO trajectories are compared: they differ by fp32 summation order only.
     mg_check = None
-    if world > 1:
+    if world > 1 and args.full:
         n_chk = 5
 
         def sharded_check(Kc, beta0c):
@@ -673,7 +711,7 @@ def main():
     # ---- time to ELBO plateau (second half of the BASELINE metric): fresh cold start, checkelbo=1, tol=1.0, the
     # library's own train! loop (sharded through the communicator when N>1), in chunks so that the wall clock of the
     # trajectory is known; the stop rule carries across chunks (every chunk re-evaluates its baseline ELBO)
-    if not args.no_plateau:
+    if args.full and not args.no_plateau:
         eng2 = make_engine()
         ar2, comm2 = attach_comm(eng2)
         if world > 1 and comm2 is None:
@@ -722,7 +760,7 @@ def main():
         eng2.model.close(); del eng2
 
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             result["cpu_baseline"], result["parity"] = cpu_baseline(tm, corpus, K, beta0)
             if not result["parity"]["pass"]:
                 log("PARITY FAILED against the fp64 oracle at the timed size: " + json.dumps(result["parity"]["worst"]))
@@ -732,7 +770,7 @@ def main():
     if rank == 0:
         # BASELINE.json configs 3-5 (N = 1 only; default sizes only): one measured line each, steady-state window, roofline and a
         # full-corpus OpenMP cpu_baseline -- tools/model_bench.py; the headline fields above stay config 2's
-        if world == 1 and not args.no_other_configs and (args.K, args.docs, args.vocab) == (50, 128804, 25319):
+        if world == 1 and args.full and not args.no_other_configs and (args.K, args.docs, args.vocab) == (50, 128804, 25319):
             sys.path.insert(0, os.path.join(ROOT, "tools"))
             import model_bench
             others = {}

@@ -11,6 +11,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import bench  # noqa: E402  (imports no torch at module level)
+import numpy as np  # noqa: E402
 
 
 def _full():
@@ -75,3 +76,48 @@ def test_non_finite_numbers_do_not_break_json():
     full["roofline"]["estep_ms"] = float("nan")
     r = json.loads(bench.slim_line(full))                      # strict JSON: NaN would not parse everywhere
     assert r["roofline"]["estep_ms"] is None
+
+
+class _State:
+    """what dump_outputs reads of a gpuLDA: update_host! and the host fields it fills (float64, Fortran order, as lda.py has them)"""
+
+    def __init__(self, K, V, M):
+        rng = np.random.default_rng(3)
+        self.alpha = rng.uniform(0.1, 2.0, K)
+        self.beta = np.asfortranarray(rng.dirichlet(np.ones(V), K))
+        self.gamma = np.asfortranarray(rng.uniform(0.5, 9.0, (K, M)))
+        self.Elogtheta = np.asfortranarray(-rng.uniform(0.5, 9.0, (K, M)))
+        self.hosted = 0
+
+    def update_host(self):
+        self.hosted += 1
+
+
+def test_dump_outputs_writes_the_last_state(tmp_path):
+    st = _State(5, 40, 30)
+    bench.dump_outputs(str(tmp_path / "out"), st)
+    assert st.hosted == 1
+    got = {n: np.load(tmp_path / "out" / f"{n}.npy") for n in ("alpha", "beta", "gamma", "Elogtheta")}
+    assert got["alpha"].dtype == np.float64 and np.array_equal(got["alpha"], st.alpha)
+    for n in ("beta", "gamma", "Elogtheta"):
+        assert got[n].dtype == np.float32 and np.array_equal(got[n], getattr(st, n).astype(np.float32)), n
+    assert got["gamma"].shape == (5, 30) and got["beta"].shape == (5, 40)
+
+
+def test_dump_outputs_samples_documents_above_the_limit(tmp_path, monkeypatch):
+    """above the limit gamma and Elogtheta keep the same seeded documents in every run, and the whole stays within it"""
+    st = _State(4, 10, 1000)
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 4 * 8 + 4 * 4 * 10 + 2 * 4 * 4 * 100)      # alpha + beta + 100 documents of gamma and Elogtheta
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), st)
+    total = 0
+    for n in ("alpha", "beta", "gamma", "Elogtheta"):
+        a, b = np.load(tmp_path / "a" / f"{n}.npy"), np.load(tmp_path / "b" / f"{n}.npy")
+        assert np.array_equal(a, b), n
+        total += a.nbytes
+    assert total <= bench.DUMP_LIMIT
+    g = np.load(tmp_path / "a" / "gamma.npy")
+    assert g.shape == (4, 100)
+    cols = [int(np.flatnonzero((st.gamma.astype(np.float32) == g[:, [j]]).all(axis=0))[0]) for j in range(100)]
+    assert cols == sorted(set(cols))                             # distinct documents, in document order
+    assert np.array_equal(np.load(tmp_path / "a" / "Elogtheta.npy"), st.Elogtheta[:, cols].astype(np.float32))

@@ -27,7 +27,7 @@ def _launch(world, extra_env=None, docs="6000", K=None):
     env = dict(os.environ, TMVB_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0", **(extra_env or {}))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "4", "--warmup", "1",
-           "--burnin", "3", "--docs", docs, "--clock-warmup", "0", "--plateau-cap", "100"] + (["--K", str(K)] if K else [])
+           "--burnin", "3", "--docs", docs, "--clock-warmup", "0", "--plateau-cap", "100", "--full"] + (["--K", str(K)] if K else [])
     out = subprocess.run(cmd, capture_output=True, text=True, env=env, cwd=ROOT, timeout=1500)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]

@@ -8,8 +8,8 @@
 #   tests:<expr>     `pytest -m gpu -k <expr>`               -> t_<n>.txt
 #   file:<path>      `pytest -m gpu <path>`                  -> t_<n>.txt
 #   smoke            __graft_entry__.smoke()                 -> smoke.txt
-#   bench            default bench.py line                   -> bench.json / bench.err
-#   bench:<args>     bench.py with extra args (use , for spaces)  -> bench_<n>.json
+#   bench            bench.py --full line                    -> bench.json / bench.err
+#   bench:<args>     bench.py --full with extra args (use , for spaces)  -> bench_<n>.json
 #   model:<names>    tools/model_bench.py <names> (comma separated) -> models.jsonl
 #   trace:<name>:<cmd>       rocprofv3 --kernel-trace --stats -- python <cmd>  -> trace_<name>_summary.txt (+ _window.txt with
 #                            env:TRACE_MARKER=<kernel substring>, + _timeline.txt with env:TRACE_TIMELINE=1)
@@ -35,7 +35,7 @@ for step in "$@"; do
     file)   ( time timeout 2400 python -m pytest -q -m gpu -x -s ${arg//,/ } ) > "$O/t_$n.txt" 2>&1; echo "rc=$?" >> "$O/t_$n.txt"; tail -40 "$O/t_$n.txt" ;;
     smoke)  timeout 600 python __graft_entry__.py smoke > "$O/smoke.txt" 2>&1; echo "rc=$?" >> "$O/smoke.txt"; tail -4 "$O/smoke.txt" ;;
     bench)  if [ -z "$arg" ]; then f=bench; else f=bench_$n; fi
-            ( time timeout 1500 python bench.py ${arg//,/ } ) > "$O/$f.json" 2> "$O/$f.err"; echo "rc=$?" >> "$O/$f.err"; tail -12 "$O/$f.err"; cut -c1-1800 "$O/$f.json" ;;
+            ( time timeout 1500 python bench.py --full ${arg//,/ } ) > "$O/$f.json" 2> "$O/$f.err"; echo "rc=$?" >> "$O/$f.err"; tail -12 "$O/$f.err"; cut -c1-1800 "$O/$f.json" ;;
     model)  ( time timeout 1500 python tools/model_bench.py ${arg//,/ } ) >> "$O/models.jsonl" 2> "$O/models_$n.err"; echo "rc=$?" >> "$O/models_$n.err"; tail -8 "$O/models_$n.err"; tail -n 3 "$O/models.jsonl" | cut -c1-900 ;;
     trace)  name=${arg%%:*}; cmd=${arg#*:}                       # trace:<name>:<python command, commas for spaces>
             ( cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats -d "$O/trace_$name" -- python $R/${cmd//,/ } ) > "$O/trace_$name.log" 2>&1; echo "rc=$?" >> "$O/trace_$name.log"
