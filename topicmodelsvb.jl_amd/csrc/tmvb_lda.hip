@@ -1707,6 +1707,9 @@ static int lda_estep_impl(tmvb_lda* h, int32_t viter, double vtol)
     TermStatsParams tp;
     tp.K = h->K; tp.tstride = h->KP; tp.ostride = h->K;
     tp.w = h->d_wtok; tp.E = h->d_E; tp.T = h->d_beta[h->cur]; tp.eps = TMVB_EPS_F; tp.base = 0.0f; tp.keps = (float)h->K * TMVB_EPS_F;
+#ifdef TMVB_MUTANT_LDA_STATS_NO_EPS
+    tp.eps = 0.0f;                // MUTANT (tests/test_mutants_gpu.py, never in a shipped build): beta_temp without its eps * sum w term (src/LDA.jl:152)
+#endif
     tp.out = h->d_stats; tp.partial = h->d_ts_partial; tp.estride = h->e_padded ? h->estride : 0;
     // gather-side statistics of the documents whose kernels precede `after` on its stream:
     //   S[:, j] += beta[:, j] .* sum_tokens w E[:, doc] + eps sum w     (update_beta!(model, d))
