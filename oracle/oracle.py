@@ -284,10 +284,13 @@ class fLDA(LDA):
         vtol = 1.0 / self.K ** 2 if vtol is None else vtol
         d1 = self.M if d1 is None else d1
         if omp_threads:
-            return lib().orc_flda_estep_omp(*self._corp_args(), c_i64(d0), c_i64(d1), c_dbl(self.eta), _pd(self.alpha), _pd(self.kappa),
-                                            _pd(self.beta), _pd(self.beta_temp), _pd(self.kappa_temp), _pd(self.gamma), _pd(self.Elogtheta),
-                                            _pd(self.Elogtheta_old), _pd(self.tau), _pd(self.tau_old), C.c_int(viter), c_dbl(vtol),
-                                            C.c_int(omp_threads))
+            # document-parallel; per-document sweep counts as the sequential E-step reports them
+            sw = np.zeros(max(d1 - d0, 1), dtype=np.int32)
+            lib().orc_flda_estep_omp_sw(*self._corp_args(), c_i64(d0), c_i64(d1), c_dbl(self.eta), _pd(self.alpha), _pd(self.kappa),
+                                        _pd(self.beta), _pd(self.beta_temp), _pd(self.kappa_temp), _pd(self.gamma), _pd(self.Elogtheta),
+                                        _pd(self.Elogtheta_old), _pd(self.tau), _pd(self.tau_old), C.c_int(viter), c_dbl(vtol),
+                                        C.c_int(omp_threads), _pi32(sw))
+            return sw[: d1 - d0]
         sw = np.zeros(max(d1 - d0, 1), dtype=np.int32)
         rc = lib().orc_flda_estep(*self._corp_args(), c_i64(d0), c_i64(d1), c_dbl(self.eta), _pd(self.alpha), _pd(self.kappa),
                                   _pd(self.beta), _pd(self.beta_temp), _pd(self.kappa_temp), _pd(self.gamma), _pd(self.Elogtheta),
@@ -435,10 +438,14 @@ class fCTM(CTM):
         vtol = 1.0 / self.K ** 2 if vtol is None else vtol
         d1 = self.M if d1 is None else d1
         if omp_threads:
-            return lib().orc_fctm_estep_omp(*self._corp_args(), c_i64(d0), c_i64(d1), c_dbl(self.eta), _pd(self.kappa), _pd(self.mu),
-                                            _pd(self.invsigma), _pd(self.beta), _pd(self.beta_temp), _pd(self.kappa_temp), _pd(self.lam),
-                                            _pd(self.lam_old), _pd(self.vsq), _pd(self.logzeta), _pd(self.tau), _pd(self.tau_old),
-                                            C.c_int(niter), c_dbl(ntol), C.c_int(viter), c_dbl(vtol), C.c_int(omp_threads))
+            sw = np.zeros(max(d1 - d0, 1), dtype=np.int32); nw = np.zeros(max(d1 - d0, 1), dtype=np.int32)
+            lib().orc_fctm_estep_omp_sw(*self._corp_args(), c_i64(d0), c_i64(d1), c_dbl(self.eta), _pd(self.kappa), _pd(self.mu),
+                                        _pd(self.invsigma), _pd(self.beta), _pd(self.beta_temp), _pd(self.kappa_temp), _pd(self.lam),
+                                        _pd(self.lam_old), _pd(self.vsq), _pd(self.logzeta), _pd(self.tau), _pd(self.tau_old),
+                                        C.c_int(niter), c_dbl(ntol), C.c_int(viter), c_dbl(vtol), C.c_int(omp_threads), _pi32(sw), _pi32(nw))
+            self.newton_per_doc = nw[: d1 - d0]
+            self.newton_steps = int(nw[: d1 - d0].sum())
+            return sw[: d1 - d0]
         sw = np.zeros(max(d1 - d0, 1), dtype=np.int32)
         nst = c_i64(0)
         rc = lib().orc_fctm_estep(*self._corp_args(), c_i64(d0), c_i64(d1), c_dbl(self.eta), _pd(self.kappa), _pd(self.mu),

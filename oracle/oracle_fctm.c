@@ -160,13 +160,14 @@ int orc_fctm_estep(int64_t M, int64_t V, int64_t K,
     return 0;
 }
 
-/* The same E-step, document-parallel with OpenMP (cpu_baseline only; private statistics ADD duplicate ids: condensed corpora) */
-int orc_fctm_estep_omp(int64_t M, int64_t V, int64_t K,
-                       const int64_t* doc_ptr, const int32_t* terms, const int32_t* counts,
-                       int64_t d0, int64_t d1, double eta, const double* kappa, const double* mu, const double* invsigma,
-                       const double* beta, double* beta_temp, double* kappa_temp, double* lambda, double* lambda_old,
-                       double* vsq, double* logzeta, double* tau, double* tau_old,
-                       int niter, double ntol, int viter, double vtol, int nthreads)
+/* The same E-step, document-parallel with OpenMP (cpu_baseline only; private statistics ADD duplicate ids: condensed corpora).
+ * sweeps_out / newton_out (may be NULL): per-document sweep counts and lambda Newton steps, [d - d0] (oracle/parity.py) */
+int orc_fctm_estep_omp_sw(int64_t M, int64_t V, int64_t K,
+                          const int64_t* doc_ptr, const int32_t* terms, const int32_t* counts,
+                          int64_t d0, int64_t d1, double eta, const double* kappa, const double* mu, const double* invsigma,
+                          const double* beta, double* beta_temp, double* kappa_temp, double* lambda, double* lambda_old,
+                          double* vsq, double* logzeta, double* tau, double* tau_old,
+                          int niter, double ntol, int viter, double vtol, int nthreads, int32_t* sweeps_out, int32_t* newton_out)
 {
     int used = 1;
 #ifdef _OPENMP
@@ -181,13 +182,15 @@ int orc_fctm_estep_omp(int64_t M, int64_t V, int64_t K,
         double* bt = (double*)calloc((size_t)(K * V), sizeof(double));
         double* kt = (double*)calloc((size_t)V, sizeof(double));
         for (int64_t q = 0; q < K * mx; ++q) phi[q] = 1.0 / (double)K;
-        int64_t newton = 0;
 #pragma omp for schedule(dynamic, 16)
         for (int64_t d = d0; d < d1; ++d) {
             int64_t off = doc_ptr[d], Nd = doc_ptr[d + 1] - off;
             const int32_t* tm = terms + off; const int32_t* ct = counts + off;
-            fctm_doc(K, Nd, tm, ct, eta, kappa, mu, invsigma, beta, lambda + d * K, lambda_old + d * K, vsq + d * K,
-                     logzeta + d, tau + off, tau_old + off, phi, ws, niter, ntol, viter, vtol, &newton);
+            int64_t newton = 0;
+            int sw = fctm_doc(K, Nd, tm, ct, eta, kappa, mu, invsigma, beta, lambda + d * K, lambda_old + d * K, vsq + d * K,
+                              logzeta + d, tau + off, tau_old + off, phi, ws, niter, ntol, viter, vtol, &newton);
+            if (sweeps_out) sweeps_out[d - d0] = sw;
+            if (newton_out) newton_out[d - d0] = (int32_t)newton;
             for (int64_t n = 0; n < Nd; ++n) {
                 double* col = bt + (int64_t)tm[n] * K;
                 const double wn = tau[off + n] * (double)ct[n];
@@ -204,11 +207,23 @@ int orc_fctm_estep_omp(int64_t M, int64_t V, int64_t K,
     }
 #else
     (void)nthreads;
+    (void)newton_out;
     orc_fctm_estep(M, V, K, doc_ptr, terms, counts, d0, d1, eta, kappa, mu, invsigma, beta, beta_temp, kappa_temp, lambda,
-                   lambda_old, vsq, logzeta, tau, tau_old, niter, ntol, viter, vtol, NULL, NULL);
+                   lambda_old, vsq, logzeta, tau, tau_old, niter, ntol, viter, vtol, sweeps_out, NULL);
 #endif
     (void)M;
     return used;
+}
+
+int orc_fctm_estep_omp(int64_t M, int64_t V, int64_t K,
+                       const int64_t* doc_ptr, const int32_t* terms, const int32_t* counts,
+                       int64_t d0, int64_t d1, double eta, const double* kappa, const double* mu, const double* invsigma,
+                       const double* beta, double* beta_temp, double* kappa_temp, double* lambda, double* lambda_old,
+                       double* vsq, double* logzeta, double* tau, double* tau_old,
+                       int niter, double ntol, int viter, double vtol, int nthreads)
+{
+    return orc_fctm_estep_omp_sw(M, V, K, doc_ptr, terms, counts, d0, d1, eta, kappa, mu, invsigma, beta, beta_temp, kappa_temp,
+                                 lambda, lambda_old, vsq, logzeta, tau, tau_old, niter, ntol, viter, vtol, nthreads, NULL, NULL);
 }
 
 /* update_elbo!  :105-115 with the seven terms of :68-102 */

@@ -123,11 +123,13 @@ int orc_flda_estep(int64_t M, int64_t V, int64_t K,
 /* The same E-step, document-parallel with OpenMP (bench.py / tools/model_bench.py cpu_baseline only): every thread runs whole
  * documents and accumulates private statistics, reduced at the end.  Private accumulation ADDS duplicate term ids of one
  * document (quirk Q1 overwrites them), so this variant is for condensed corpora -- which every corpus the engine accepts is. */
-int orc_flda_estep_omp(int64_t M, int64_t V, int64_t K,
-                       const int64_t* doc_ptr, const int32_t* terms, const int32_t* counts,
-                       int64_t d0, int64_t d1, double eta, const double* alpha, const double* kappa, const double* beta,
-                       double* beta_temp, double* kappa_temp, double* gamma, double* Elogtheta, double* Elogtheta_old,
-                       double* tau, double* tau_old, int viter, double vtol, int nthreads)
+/* sweeps_out (may be NULL): sweeps_out[d - d0] = the sweeps document d ran, as orc_flda_estep reports them -- the full-size parity
+ * checks (oracle/parity.py) compare them per document and re-run the documents that left at a different sweep. */
+int orc_flda_estep_omp_sw(int64_t M, int64_t V, int64_t K,
+                          const int64_t* doc_ptr, const int32_t* terms, const int32_t* counts,
+                          int64_t d0, int64_t d1, double eta, const double* alpha, const double* kappa, const double* beta,
+                          double* beta_temp, double* kappa_temp, double* gamma, double* Elogtheta, double* Elogtheta_old,
+                          double* tau, double* tau_old, int viter, double vtol, int nthreads, int32_t* sweeps_out)
 {
     int used = 1;
 #ifdef _OPENMP
@@ -146,8 +148,9 @@ int orc_flda_estep_omp(int64_t M, int64_t V, int64_t K,
             int64_t off = doc_ptr[d], Nd = doc_ptr[d + 1] - off;
             const int32_t* tm = terms + off;
             const int32_t* ct = counts + off;
-            orc_flda_doc_sweeps(K, Nd, tm, ct, eta, alpha, kappa, beta, gamma + d * K, Elogtheta + d * K,
-                                Elogtheta_old + d * K, tau + off, tau_old + off, phi, viter, vtol);
+            int sw = orc_flda_doc_sweeps(K, Nd, tm, ct, eta, alpha, kappa, beta, gamma + d * K, Elogtheta + d * K,
+                                         Elogtheta_old + d * K, tau + off, tau_old + off, phi, viter, vtol);
+            if (sweeps_out) sweeps_out[d - d0] = sw;
             for (int64_t n = 0; n < Nd; ++n) {
                 double* col = bt + (int64_t)tm[n] * K;
                 const double wn = tau[off + n] * (double)ct[n];
@@ -165,10 +168,20 @@ int orc_flda_estep_omp(int64_t M, int64_t V, int64_t K,
 #else
     (void)nthreads;
     orc_flda_estep(M, V, K, doc_ptr, terms, counts, d0, d1, eta, alpha, kappa, beta, beta_temp, kappa_temp, gamma, Elogtheta,
-                   Elogtheta_old, tau, tau_old, viter, vtol, NULL);
+                   Elogtheta_old, tau, tau_old, viter, vtol, sweeps_out);
 #endif
     (void)M;
     return used;
+}
+
+int orc_flda_estep_omp(int64_t M, int64_t V, int64_t K,
+                       const int64_t* doc_ptr, const int32_t* terms, const int32_t* counts,
+                       int64_t d0, int64_t d1, double eta, const double* alpha, const double* kappa, const double* beta,
+                       double* beta_temp, double* kappa_temp, double* gamma, double* Elogtheta, double* Elogtheta_old,
+                       double* tau, double* tau_old, int viter, double vtol, int nthreads)
+{
+    return orc_flda_estep_omp_sw(M, V, K, doc_ptr, terms, counts, d0, d1, eta, alpha, kappa, beta, beta_temp, kappa_temp, gamma,
+                                 Elogtheta, Elogtheta_old, tau, tau_old, viter, vtol, nthreads, NULL);
 }
 
 /* update_kappa!(model)  :138-142 */

@@ -34,6 +34,21 @@ CTM_TOL = {"lambda_err_p999": 3.0, "lambda_err_max": 20.0, "vsq_rel_p999": 5e-5,
            "beta_rel_max": 5e-5, "mu_abs_max": 1e-5, "sigma_abs_rel_max": 5e-6, "elbo_rel": 2e-7, "sweep_mismatch_frac": 1e-3}
 CTPF_TOL = {"gimel_rel_p999": 5e-4, "zayin_rel_p999": 8e-7, "gimel_rel_max": 3e-3, "zayin_rel_max": 1e-2, "alef_rel_max": 5e-4, "he_rel_max": 1.5e-3,
             "rates_rel_max": 1e-4, "elbo_rel": 1e-6, "sweep_mismatch_frac": 0.05}
+# fLDA / fCTM: the bounds of the small-corpus tests, no looser -- tests/tol.py's flda.* / fctm.* keys (TOL_KEYS names them; tests/test_parity_module.py
+# asserts that each bound here is at most the key's), the sweep-mismatch bounds of tests/test_flda_gpu.py (5 %) and tests/test_fctm_gpu.py (10 %).
+# fCTM's eta is a parameter (update_eta! is commented out of its train!, src/fCTM.jl:253): it must not move at all.
+FLDA_TOL = {"gamma_rel_max": 1e-5, "Elogtheta_rel_max": 3e-6, "tau_abs_max": 1e-5, "beta_rel_max": 5e-5, "beta_abs_max": 1e-6, "kappa_rel_max": 1e-3,
+            "alpha_rel_max": 1.5e-5, "eta_abs": 2e-7, "elbo_rel": 1e-6, "sweep_mismatch_frac": 0.05}
+FCTM_TOL = {"lambda_err_max": 3.0, "vsq_rel_max": 5e-5, "logzeta_abs_max": 1e-5, "tau_abs_max": 5e-6, "beta_rel_max": 5e-5, "kappa_rel_max": 1e-4,
+            "mu_abs_max": 1e-5, "sigma_rel_max": 1e-5, "invsigma_rel_max": 1e-5, "eta_abs": 0.0, "elbo_rel": 3e-7, "sweep_mismatch_frac": 0.1}
+TOL_KEYS = {
+    "flda": {"gamma_rel_max": "flda.gamma_rel", "Elogtheta_rel_max": "flda.Elogtheta_rel", "tau_abs_max": "flda.tau_abs", "beta_rel_max": "flda.beta_rel",
+             "beta_abs_max": "flda.beta_abs", "kappa_rel_max": "flda.kappa_rel", "alpha_rel_max": "flda.alpha_rel", "eta_abs": "flda.eta_abs",
+             "elbo_rel": "flda.elbo_rel_step"},
+    "fctm": {"lambda_err_max": "fctm.lambda_err", "vsq_rel_max": "fctm.vsq_rel", "logzeta_abs_max": "fctm.logzeta_abs", "tau_abs_max": "fctm.tau_abs",
+             "beta_rel_max": "fctm.beta_rel", "kappa_rel_max": "fctm.kappa_rel", "mu_abs_max": "fctm.mu_abs", "sigma_rel_max": "fctm.sigma_rel",
+             "invsigma_rel_max": "ctm.invsigma_rel", "elbo_rel": "fctm.elbo_rel_step"},      # (update_sigma! is CTM's: no fctm.invsigma key)
+}
 MEASURED = {
     "lda": {"gamma_rel_p999": 7.61e-7, "Elogtheta_rel_p999": 3.97e-7, "gamma_rel_max": 1.77e-6, "Elogtheta_rel_max": 1.28e-6, "beta_rel_max": 8.34e-7,
             "alpha_rel_max": 7.06e-6, "elbo_rel": 3.89e-7, "sweep_mismatch_frac": 7.61e-4},
@@ -276,3 +291,153 @@ def ctpf_parity(gm, om, iters=3, threads=0, elbo=False, log=None):
     return {"pass": ok, "iterations": iters, "mode": "teacher-forced, every document compared (documents whose exit sweep differs: oracle re-run with the device's sweep count)",
             "documents": M, "worst": worst, "tolerances": CTPF_TOL, "per_iteration": rows,
             **{k: worst[k] for k in ("gimel_rel_p999", "alef_rel_max", "he_rel_max", "rates_rel_max", "sweep_mismatch_frac")}}, secs
+
+
+# --------------------------------------------------------------------------------------------------------- fLDA / fCTM
+def _filtered_fix_up(om, bad, sw_g, doc_fields, pre_doc, pre_tok, redo):
+    """the sweep fix-up of the filtered models: beta_temp AND kappa_temp, per-document columns and per-token tau / tau_old restored.
+    redo(d, viter, vtol): the oracle's sequential E-step of document d (viter = None: the default exit rule)."""
+    ptr = om.corp.doc_ptr
+    kb, kk = om.beta_temp, om.kappa_temp
+    Ab, Bb, Ak, Bk = np.zeros_like(kb), np.zeros_like(kb), np.zeros_like(kk), np.zeros_like(kk)
+
+    def restore(d):
+        for n, p in zip(doc_fields, pre_doc):
+            getattr(om, n)[..., d] = p[..., d]
+        a, b = int(ptr[d]), int(ptr[d + 1])
+        om.tau[a:b] = pre_tok[0][a:b]; om.tau_old[a:b] = pre_tok[1][a:b]
+    for d in bad:
+        d = int(d)
+        restore(d); om.beta_temp, om.kappa_temp = Ab, Ak; redo(d, None, None)
+        restore(d); om.beta_temp, om.kappa_temp = Bb, Bk; redo(d, int(sw_g[d]), 0.0)
+    kb += Bb; kb -= Ab; kk += Bk; kk -= Ak
+    om.beta_temp, om.kappa_temp = kb, kk
+
+
+KAPPA_BG_SHARE = 1e-2
+
+
+def kappa_mask(om):
+    """the terms whose kappa fp32 tau can determine: kappa > 1e-8 (the small-corpus tests' mask) and a background share
+    sum (1 - tau) c / sum c of the term's tokens >= KAPPA_BG_SHARE.  kappa_j = sum (1 - tau) c / norm: where the term's tokens
+    sit at tau within a few fp32 ulps of 1 (trained states: frequent topical terms), 1 - tau cancels and the device's kappa
+    carries tau's ~30-ulp error as a relative error of percents; at a share >= 1 % that error is < 3e-4.
+    At the cold start every term passes (tau ~ eta)."""
+    c = om.corp
+    C = np.bincount(c.terms, weights=c.counts, minlength=om.V)
+    bg = np.bincount(c.terms, weights=(1.0 - om.tau) * c.counts, minlength=om.V)
+    return (om.kappa > 1e-8) & (bg >= KAPPA_BG_SHARE * C)
+
+
+def _tau_kappa(gm, om):
+    bk = kappa_mask(om)
+    return {"tau_abs_max": max(_mx(np.abs(gm.tau - om.tau)), _mx(np.abs(gm.tau_old - om.tau_old))),
+            "kappa_rel_max": _mx(_rel(gm.kappa[bk], om.kappa[bk])), "kappa_compared_frac": float(bk.mean()) if bk.size else 1.0,
+            "eta_abs": abs(float(gm.eta) - float(om.eta))}
+
+
+FLDA_FIELDS = ("eta", "alpha", "kappa", "kappa_old", "beta", "beta_old", "gamma", "Elogtheta", "Elogtheta_old", "tau", "tau_old")
+FCTM_FIELDS = ("eta", "mu", "sigma", "invsigma", "kappa", "kappa_old", "beta", "beta_old", "lam", "lam_old", "vsq", "logzeta", "tau", "tau_old")
+
+
+def _force(gm, om, fields):
+    for n in fields:
+        v = getattr(om, n)
+        setattr(gm, n, np.array(v, copy=True, order="F") if isinstance(v, np.ndarray) else float(v))
+    gm.update_buffer()
+
+
+def flda_force(gm, om):
+    _force(gm, om, FLDA_FIELDS)
+
+
+def fctm_force(gm, om):
+    _force(gm, om, FCTM_FIELDS)
+
+
+def flda_parity(gm, om, iters=2, threads=0, elbo=True, viter=10, vtol=None, niter=1000, ntol=None, log=None):
+    """fLDA (src/fLDA.jl): gamma, Elogtheta per document, tau and tau_old per token, eta, alpha, kappa, beta -- as
+    tests/test_flda_gpu.py::test_teacher_forced_fixed_sweeps compares them, over every document."""
+    K, M = om.K, om.M
+    rows, secs = [], []
+    for it in range(iters):
+        flda_force(gm, om)
+        docf = ("gamma", "Elogtheta", "Elogtheta_old")
+        pre = tuple(getattr(om, n).copy(order="F") for n in docf); pre_t = (om.tau.copy(), om.tau_old.copy())
+        gm.estep(viter, vtol); gm.reduce_docs()
+        t0 = time.perf_counter()
+        sw_o = np.asarray(om.estep(viter, vtol, omp_threads=threads) if threads else om.estep(viter, vtol))
+        t_e = time.perf_counter() - t0
+        gm.synchronize()
+        sw_g = gm.doc_sweeps().astype(np.int64)
+        bad = np.nonzero(sw_g != sw_o)[0]
+        if len(bad):
+            _filtered_fix_up(om, bad, sw_g, docf, pre, pre_t,
+                             lambda d, v, t: om.estep(viter if v is None else v, vtol if t is None else t, d0=d, d1=d + 1))
+        t0 = time.perf_counter()
+        om.mstep(niter, ntol)
+        t_m = time.perf_counter() - t0
+        gm.mstep(niter, ntol)
+        r = {"sweep_mismatch_frac": len(bad) / max(M, 1), "sweep_mismatch_max": int(np.abs(sw_g - sw_o).max()) if M else 0}
+        if elbo:
+            e_g = gm.update_elbo(); e_o = om.update_elbo()
+            r["elbo_rel"] = abs(e_g - e_o) / abs(e_o); r["elbo_hip"] = e_g; r["elbo_oracle"] = e_o
+        gm.update_host()
+        rg = _rel(gm.gamma, om.gamma); re = _rel(gm.Elogtheta, om.Elogtheta)
+        big = om.beta > 1e-6
+        r.update({"gamma_rel_p999": _q(rg), "gamma_rel_max": _mx(rg), "Elogtheta_rel_p999": _q(re), "Elogtheta_rel_max": _mx(re),
+                  "beta_rel_max": _mx(_rel(gm.beta[big], om.beta[big])), "beta_abs_max": _mx(np.abs(gm.beta - om.beta)),
+                  "alpha_rel_max": _mx(_rel(gm.alpha, om.alpha)), **_tau_kappa(gm, om), "oracle_estep_s": t_e, "oracle_mstep_s": t_m})
+        rows.append(r); secs.append(t_e + t_m)
+        if log:
+            log(f"parity fLDA K={K} iteration {it + 1}: " + ", ".join(f"{k}={v:.3g}" for k, v in r.items() if isinstance(v, float)))
+    worst, ok = _verdict(rows, FLDA_TOL, "flda")
+    return {"pass": ok, "iterations": iters, "mode": "teacher-forced, every document compared (documents whose exit sweep differs: oracle re-run with the device's sweep count)",
+            "documents": M, "worst": worst, "tolerances": FLDA_TOL, "per_iteration": rows,
+            **{k: worst[k] for k in ("gamma_rel_max", "tau_abs_max", "beta_rel_max", "kappa_rel_max", "elbo_rel", "sweep_mismatch_frac")}}, secs
+
+
+def fctm_parity(gm, om, iters=1, threads=0, elbo=True, viter=10, vtol=None, log=None):
+    """fCTM (src/fCTM.jl): lambda (in units of LAMBDA_ABS + LAMBDA_REL |lambda|), vsq, logzeta per document, tau and tau_old per
+    token, eta, mu, sigma, invsigma, kappa, beta -- as tests/test_fctm_gpu.py compares them, over every document."""
+    K, M = om.K, om.M
+    rows, secs = [], []
+    for it in range(iters):
+        fctm_force(gm, om)
+        docf = ("lam", "lam_old", "vsq", "logzeta")
+        pre = tuple(getattr(om, n).copy(order="F") for n in docf); pre_t = (om.tau.copy(), om.tau_old.copy())
+        gm.estep(viter=viter, vtol=vtol); gm.reduce_docs()
+        t0 = time.perf_counter()
+        sw_o = np.asarray(om.estep(viter=viter, vtol=vtol, omp_threads=threads) if threads else om.estep(viter=viter, vtol=vtol))
+        t_e = time.perf_counter() - t0
+        gm.synchronize()
+        sw_g = gm.doc_sweeps().astype(np.int64)
+        bad = np.nonzero(sw_g != sw_o)[0]
+        if len(bad):
+            _filtered_fix_up(om, bad, sw_g, docf, pre, pre_t,
+                             lambda d, v, t: om.estep(viter=viter if v is None else v, vtol=vtol if t is None else t, d0=d, d1=d + 1))
+        t0 = time.perf_counter()
+        om.mstep()
+        t_m = time.perf_counter() - t0
+        gm.mstep()
+        r = {"sweep_mismatch_frac": len(bad) / max(M, 1), "sweep_mismatch_max": int(np.abs(sw_g - sw_o).max()) if M else 0}
+        if elbo:
+            e_g = gm.update_elbo(); e_o = om.update_elbo()
+            r["elbo_rel"] = abs(e_g - e_o) / abs(e_o); r["elbo_hip"] = e_g; r["elbo_oracle"] = e_o
+        gm.update_host()
+        lerr = np.abs(gm.lam - om.lam) / (LAMBDA_ABS + LAMBDA_REL * np.abs(om.lam))
+        big = om.beta > 1e-6
+        r.update({"lambda_err_p999": _q(lerr), "lambda_err_max": _mx(lerr), "lambda_abs_max": _mx(np.abs(gm.lam - om.lam)),
+                  "vsq_rel_max": _mx(_rel(gm.vsq, om.vsq)), "logzeta_abs_max": _mx(np.abs(gm.logzeta - om.logzeta)),
+                  "beta_rel_max": _mx(_rel(gm.beta[big], om.beta[big])), "mu_abs_max": _mx(np.abs(gm.mu - om.mu)),
+                  "sigma_rel_max": _mx(np.abs(gm.sigma - om.sigma)) / _mx(np.abs(om.sigma)),
+                  "invsigma_rel_max": _mx(np.abs(gm.invsigma - om.invsigma)) / _mx(np.abs(om.invsigma)),
+                  **_tau_kappa(gm, om), "oracle_estep_s": t_e, "oracle_mstep_s": t_m})
+        rows.append(r); secs.append(t_e + t_m)
+        if log:
+            log(f"parity fCTM K={K} iteration {it + 1}: " + ", ".join(f"{k}={v:.3g}" for k, v in r.items() if isinstance(v, float)))
+    worst, ok = _verdict(rows, FCTM_TOL, "fctm")
+    return {"pass": ok, "iterations": iters, "mode": "teacher-forced, every document compared (documents whose exit sweep differs: oracle re-run with the device's sweep count)",
+            "documents": M, "worst": worst, "tolerances": FCTM_TOL, "per_iteration": rows,
+            "lambda_err_is": "|lambda_hip - lambda_oracle| / (1.5e-5 + 1.5e-5 |lambda_oracle|)",
+            **{k: worst[k] for k in ("lambda_err_max", "tau_abs_max", "beta_rel_max", "kappa_rel_max", "elbo_rel", "sweep_mismatch_frac")}}, secs

@@ -62,6 +62,64 @@ def test_omp_estep_matches_sequential_filtered(tmvb, oracle):
     np.testing.assert_allclose(a.kappa, b.kappa, rtol=1e-9, atol=1e-300)
 
 
+def _plain_omp(m, kind, threads=3):
+    """the OpenMP entry point without per-document outputs (orc_flda_estep_omp / orc_fctm_estep_omp), as cpu_baseline calls it"""
+    from oracle import oracle as oc
+    C = oc.C
+    a = (*m._corp_args(), oc.c_i64(0), oc.c_i64(m.M), oc.c_dbl(m.eta))
+    if kind == "flda":
+        vt = 1.0 / m.K ** 2
+        oc.lib().orc_flda_estep_omp(*a, oc._pd(m.alpha), oc._pd(m.kappa), oc._pd(m.beta), oc._pd(m.beta_temp), oc._pd(m.kappa_temp),
+                                    oc._pd(m.gamma), oc._pd(m.Elogtheta), oc._pd(m.Elogtheta_old), oc._pd(m.tau), oc._pd(m.tau_old),
+                                    C.c_int(10), oc.c_dbl(vt), C.c_int(threads))
+    else:
+        vt = 1.0 / m.K ** 2
+        oc.lib().orc_fctm_estep_omp(*a, oc._pd(m.kappa), oc._pd(m.mu), oc._pd(m.invsigma), oc._pd(m.beta), oc._pd(m.beta_temp),
+                                    oc._pd(m.kappa_temp), oc._pd(m.lam), oc._pd(m.lam_old), oc._pd(m.vsq), oc._pd(m.logzeta), oc._pd(m.tau),
+                                    oc._pd(m.tau_old), C.c_int(1000), oc.c_dbl(vt), C.c_int(10), oc.c_dbl(vt), C.c_int(threads))
+
+
+@pytest.mark.parametrize("kind", ["flda", "fctm"])
+def test_omp_sw_sweep_counts_filtered(tmvb, oracle, kind):
+    """orc_flda/fctm_estep_omp_sw (what oracle/parity.py's fix-up runs on): the per-document sweep counts are the sequential E-step's,
+    the state is the plain OpenMP entry point's, and re-running every document with its own reported sweep count and vtol = 0 -- the
+    fix-up, applied to all of them -- reproduces that state and its statistics"""
+    pc = _nsf(tmvb, M=80, V=300, seed=8)
+    K = 5
+    beta0 = tmvb.dirichlet_rows(K, pc.V, seed=3); kappa0 = tmvb.dirichlet_rows(1, pc.V, seed=9)[0]
+    csr = oracle.CSR(pc.doc_ptr, pc.terms, pc.counts, pc.V)
+    cls = oracle.fLDA if kind == "flda" else oracle.fCTM
+    docf = ("gamma", "Elogtheta") if kind == "flda" else ("lam", "vsq", "logzeta")
+    seq, sw_m, plain, pinned = (cls(csr, K, beta0, kappa0) for _ in range(4))
+    for it in range(2):                                             # the cold start and the state one iteration later
+        s_seq = seq.estep()
+        s_sw = sw_m.estep(omp_threads=3)
+        _plain_omp(plain, kind)
+        assert np.array_equal(s_seq, s_sw) and s_sw.dtype == np.int32 and len(s_sw) == pc.M, kind
+        assert len(np.unique(s_sw)) >= 2, np.unique(s_sw)           # the default rule left documents at different sweeps
+        if kind == "fctm":
+            assert sw_m.newton_steps == seq.newton_steps and len(sw_m.newton_per_doc) == pc.M
+        for n in docf + ("tau", "tau_old"):
+            assert np.array_equal(getattr(sw_m, n), getattr(plain, n)), (kind, n)          # documents are independent: bit for bit
+        for n in docf + ("tau", "tau_old", "beta_temp", "kappa_temp"):
+            # (the statistics' summation order follows the dynamic schedule: not bit for bit between two OpenMP runs)
+            np.testing.assert_allclose(getattr(sw_m, n), getattr(plain, n), rtol=1e-12, atol=1e-300, err_msg=f"{kind} {n}")
+            np.testing.assert_allclose(getattr(sw_m, n), getattr(seq, n), rtol=1e-10, atol=1e-13, err_msg=f"{kind} {n}")
+        for d in range(pc.M):                                       # document by document, each with its own sweep count, through _sw
+            s1 = pinned.estep(viter=int(s_sw[d]), vtol=0.0, d0=d, d1=d + 1, omp_threads=2)
+            assert s1.tolist() == [s_sw[d]]
+        for n in docf + ("tau", "tau_old"):
+            assert np.array_equal(getattr(pinned, n), getattr(plain, n)), (kind, n)
+        np.testing.assert_allclose(pinned.beta_temp, plain.beta_temp, rtol=1e-12, atol=1e-300)
+        np.testing.assert_allclose(pinned.kappa_temp, plain.kappa_temp, rtol=1e-12, atol=1e-300)
+        seq.mstep()
+        from oracle import parity
+        for m in (sw_m, plain, pinned):                             # all four from the same state again (the statistics' order moves the last bits)
+            for n in (parity.FLDA_FIELDS if kind == "flda" else parity.FCTM_FIELDS) + ("beta_temp", "kappa_temp"):
+                v = getattr(seq, n)
+                setattr(m, n, np.array(v, copy=True, order="F") if isinstance(v, np.ndarray) else v)
+
+
 ASAN_SCRIPT = r'''
 import ctypes as C, os, sys, numpy as np
 sys.path.insert(0, sys.argv[1])
@@ -87,10 +145,14 @@ g = load("flda_m30_v50_k9_empty")
 m = oc.fLDA(oc.CSR(g["doc_ptr"], g["terms"], g["counts"], int(g["V"])), int(g["K"]), g["beta0"], g["kappa0"])
 t = m.train(iter=2, tol=0.0, checkelbo=1); assert np.all(np.isfinite(t))
 m.estep(omp_threads=2)
+sw = m.estep(omp_threads=2); assert len(sw) == m.M and sw.min() >= 1
+m.estep(viter=int(sw[3]), vtol=0.0, d0=3, d1=4, omp_threads=2)
 g = load("fctm_m30_v50_k4")
 m = oc.fCTM(oc.CSR(g["doc_ptr"], g["terms"], g["counts"], int(g["V"])), int(g["K"]), g["beta0"], g["kappa0"])
 t = m.train(iter=2, tol=0.0, checkelbo=1); assert np.all(np.isfinite(t))
 m.estep(omp_threads=2)
+sw = m.estep(omp_threads=2); assert len(sw) == m.M and sw.min() >= 1 and len(m.newton_per_doc) == m.M
+m.estep(viter=int(sw[3]), vtol=0.0, d0=3, d1=4, omp_threads=2)
 print("asan-ok")
 '''
 

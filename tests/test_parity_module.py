@@ -21,11 +21,15 @@ class _Stand:
 
     def update_buffer(self):
         for n in self.fields:
-            getattr(self.m, "lam" if n == "lam" else n)[...] = getattr(self, n)
+            if np.ndim(getattr(self.m, n)) == 0:
+                setattr(self.m, n, float(getattr(self, n)))          # (the filtered models' eta)
+            else:
+                getattr(self.m, n)[...] = getattr(self, n)
 
     def update_host(self):
         for n in self.fields:
-            setattr(self, n, np.array(getattr(self.m, n), copy=True, order="F"))
+            v = getattr(self.m, n)
+            setattr(self, n, float(v) if np.ndim(v) == 0 else np.array(v, copy=True, order="F"))
 
     def reduce_docs(self): pass
     def synchronize(self): pass
@@ -62,6 +66,28 @@ class StandCTPF(_Stand):
 
     def estep(self):
         self.sw = self.m.estep(vtol=self.vtol_scale / self.K ** 2)
+
+    def mstep(self): self.m.mstep()
+
+
+class StandFLDA(_Stand):
+    def __init__(self, m, **kw): super().__init__(m, parity.FLDA_FIELDS, **kw)
+
+    def estep(self, viter=10, vtol=None):
+        vtol = 1.0 / self.K ** 2 if vtol is None else vtol
+        self.sw = self.m.estep(viter, vtol * self.vtol_scale)
+        self.m.tau *= 1.0 - self.spoil                               # (after the statistics: only the per-token comparison can see it)
+
+    def mstep(self, niter=1000, ntol=None): self.m.mstep(niter, ntol)
+
+
+class StandFCTM(_Stand):
+    def __init__(self, m, **kw): super().__init__(m, parity.FCTM_FIELDS, **kw)
+
+    def estep(self, niter=1000, ntol=None, viter=10, vtol=None):
+        vtol = 1.0 / self.K ** 2 if vtol is None else vtol
+        self.sw = self.m.estep(niter, ntol, viter, vtol * self.vtol_scale)
+        self.m.lam *= 1.0 + self.spoil
 
     def mstep(self): self.m.mstep()
 
@@ -113,3 +139,61 @@ def test_ctpf_fix_up(tmvb, oracle):
     assert block["pass"], block["worst"]
     assert block["worst"]["sweep_mismatch_frac"] > 0
     assert block["worst"]["gimel_rel_p999"] <= 1e-12 and block["worst"]["alef_rel_max"] <= 1e-11 and block["worst"]["elbo_rel"] <= 1e-12
+
+
+def _filtered_pair(tmvb, oracle, cls, stand, K, M, V, **kw):
+    pc = tmvb.syn_nsf(M=M, V=V, seed=12)
+    beta0 = tmvb.dirichlet_rows(K, pc.V, seed=3); kappa0 = tmvb.dirichlet_rows(1, pc.V, seed=9)[0]
+    csr = oracle.CSR(pc.doc_ptr, pc.terms, pc.counts, pc.V)
+    return stand(cls(csr, K, beta0, kappa0), **kw), cls(csr, K, beta0, kappa0)
+
+
+def _fix_up_holds(block, tol):
+    assert all(v <= tol[k] for k, v in block["worst"].items() if v is not None and k != "sweep_mismatch_frac"), block["worst"]
+    assert set(tol) <= set(block["per_iteration"][0])
+    return [r["sweep_mismatch_frac"] for r in block["per_iteration"]]
+
+
+def test_flda_fix_up(tmvb, oracle):
+    """fLDA's fix-up also takes the mismatched documents' kappa statistics out and puts them back, and restores their tokens' tau / tau_old"""
+    gm, om = _filtered_pair(tmvb, oracle, oracle.fLDA, StandFLDA, K=7, M=300, V=400, vtol_scale=1.005)
+    block, secs = parity.flda_parity(gm, om, iters=4, threads=2)
+    mism = _fix_up_holds(block, parity.FLDA_TOL)
+    assert 0 < max(mism) <= 0.05 and block["pass"]
+    w = block["worst"]
+    assert w["gamma_rel_max"] <= 1e-12 and w["tau_abs_max"] <= 1e-13 and w["beta_rel_max"] <= 1e-10 and w["kappa_rel_max"] <= 1e-10
+    assert w["eta_abs"] <= 1e-14 and w["elbo_rel"] <= 1e-13 and w["alpha_rel_max"] <= 1e-10
+    assert len(secs) == 4 and all(s > 0 for s in secs)
+
+
+def test_flda_wrong_device_fails(tmvb, oracle):
+    gm, om = _filtered_pair(tmvb, oracle, oracle.fLDA, StandFLDA, K=7, M=300, V=400, spoil=1e-4)
+    block, _ = parity.flda_parity(gm, om, iters=2)
+    assert not block["pass"] and block["worst"]["tau_abs_max"] > 2e-5 and block["worst"]["gamma_rel_max"] <= 1e-12
+
+
+def test_fctm_fix_up(tmvb, oracle):
+    gm, om = _filtered_pair(tmvb, oracle, oracle.fCTM, StandFCTM, K=6, M=150, V=300, vtol_scale=1.003)
+    block, _ = parity.fctm_parity(gm, om, iters=3, threads=2)
+    mism = _fix_up_holds(block, parity.FCTM_TOL)
+    assert max(mism) > 0 and block["pass"]
+    w = block["worst"]
+    assert w["lambda_err_max"] <= 1e-6 and w["tau_abs_max"] <= 1e-12 and w["beta_rel_max"] <= 1e-9 and w["kappa_rel_max"] <= 1e-9
+    assert w["eta_abs"] == 0.0 and w["elbo_rel"] <= 1e-12 and w["sigma_rel_max"] <= 1e-9
+
+
+def test_fctm_wrong_device_fails(tmvb, oracle):
+    gm, om = _filtered_pair(tmvb, oracle, oracle.fCTM, StandFCTM, K=6, M=150, V=300, spoil=1e-3)
+    block, _ = parity.fctm_parity(gm, om, iters=1)
+    assert not block["pass"] and block["worst"]["lambda_err_max"] > 10
+
+
+def test_filtered_bounds_are_the_small_corpus_ones():
+    """FLDA_TOL / FCTM_TOL are no looser than the keys of tests/tol.py the small-corpus tests use"""
+    import tol
+    for model, d in (("flda", parity.FLDA_TOL), ("fctm", parity.FCTM_TOL)):
+        keys = parity.TOL_KEYS[model]
+        assert set(keys) == set(d) - {"sweep_mismatch_frac"} - ({"eta_abs"} if model == "fctm" else set()), model
+        for k, key in keys.items():
+            assert d[k] <= tol.TOL[key], (model, k, d[k], key, tol.TOL[key])
+    assert parity.FLDA_TOL["sweep_mismatch_frac"] <= 0.05 and parity.FCTM_TOL["sweep_mismatch_frac"] <= 0.1 and parity.FCTM_TOL["eta_abs"] == 0.0

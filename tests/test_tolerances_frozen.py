@@ -40,9 +40,12 @@ def test_the_measured_values_are_the_committed_evidence():
     ev6 = json.load(open(os.path.join(ROOT, "profiles", "r6_tolerances_measured.json")))       # the round-6 keys (section 8(f) rows, full-size free-running CTM)
     evt = json.load(open(os.path.join(ROOT, "profiles", "trained_tolerances_measured.json")))   # the trained-state keys (tests/test_trained_state_parity_gpu.py)
     assert not (set(ev6) & set(ev)), "a key is measured in one round's evidence file only"
+    # the trained fLDA keys (tests/test_trained_state_parity_gpu.py::test_flda_trained_state): their own evidence file, measured later
+    evf = json.load(open(os.path.join(ROOT, "profiles", "flda_trained_tolerances_measured.json")))
     assert not (set(evt) & (set(ev) | set(ev6))) and all(k.startswith("trained.") for k in evt)
-    ev.update(ev6); ev.update(evt)
-    assert {k for k in tol.MEASURED if k.startswith("trained.")} == set(evt), "every trained.* key has its measurement and no more"
+    assert not (set(evf) & (set(ev) | set(ev6) | set(evt))) and all(k.startswith("trained.flda.") for k in evf)
+    ev.update(ev6); ev.update(evt); ev.update(evf)
+    assert {k for k in tol.MEASURED if k.startswith("trained.")} == set(evt) | set(evf), "every trained.* key has its measurement and no more"
     scale = 10.0                                  # the evidence file holds lambda_err in units of the round-4 bound (1.5e-4): x 10 in today's units
     for k, m in tol.MEASURED.items():
         e = ev[k] * (scale if k == "ctm.lambda_err" else 1.0)

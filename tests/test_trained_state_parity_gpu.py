@@ -208,6 +208,66 @@ def test_fctm_trained_state(tmvb, oracle):
     assert m["cond_sigma"] > 2e4 and m["beta_below_1e30_frac"] > 0.2 and m["kappa_fp32_zero_frac"] > 0.45, m   # measured 4.5e4, 42 %, 90 %
 
 
+# ------------------------------------------------------------------------------------------------------------- fLDA
+# K = 50: one topic slot per lane of the fLDA kernels (dispatch_nslot), K = 100: two.  A trained fLDA state: most of kappa at fp32 zero (the
+# background mass sits on few terms), tau = 1.0f exactly for topical tokens (1 - tau below half an fp32 ulp), beta over hundreds of decades --
+# where the Bernoulli entropy H(tau) of update_elbo! needs its 0 log 0 guard (src/fLDA.jl:94-97; both ELBO forms of csrc/tmvb_flda.hip).
+# Measured on MI355X: K = 50 min alpha 486, kappa at fp32 zero 5.4 %, tau = 1.0f 1.1 %, beta < 1e-30 3.3 %; K = 100: 256, 22 %, 13.6 %, 4.0 %.
+# (Unlike LDA's, fLDA's alpha grows: the background switch takes the rare terms out of phi.)  No tau reaches 0.  Asserted at about half.
+FLDA_CASES = {50: dict(M=2000, V=6000, seed=17, iters=300, alpha_min=240.0, kappa_zero_min=0.025, tau_one_min=0.005, beta_low_min=0.015),
+              100: dict(M=1500, V=5000, seed=18, iters=300, alpha_min=128.0, kappa_zero_min=0.1, tau_one_min=0.06, beta_low_min=0.02)}
+
+
+@pytest.mark.parametrize("K", sorted(FLDA_CASES))
+def test_flda_trained_state(tmvb, oracle, K):
+    """fLDA from a state the device trained for 300 iterations: one pinned-sweep step (viter = 5, vtol = 0) and one default-rule step through
+    oracle/parity.py's flda_parity, each with update_elbo!.  The oracle gets the device state with its exact zeros of beta and kappa lifted to
+    1e-300, as test_fctm_trained_state explains."""
+    from oracle import parity
+    c = FLDA_CASES[K]
+    pc = tmvb.syn_nsf(M=c["M"], V=c["V"], seed=c["seed"])
+    beta0 = tmvb.dirichlet_rows(K, pc.V, seed=7); kappa0 = tmvb.dirichlet_rows(1, pc.V, seed=9)[0]
+    gm = tmvb.gpufLDA(pc, K)
+    gm.beta = np.asfortranarray(beta0); gm.beta_old = gm.beta.copy(order="F"); gm.kappa = kappa0.copy(); gm.kappa_old = kappa0.copy()
+    gm.train(iter=c["iters"], tol=0.0, checkelbo=np.inf, printelbo=False)
+    om = oracle.fLDA(oracle.CSR(pc.doc_ptr, pc.terms, pc.counts, pc.V), K, beta0, kappa0)
+    _copy_state(om, gm, parity.FLDA_FIELDS)
+    for n in ("alpha", "kappa", "kappa_old", "tau", "tau_old"):
+        setattr(om, n, np.ascontiguousarray(getattr(om, n)))
+    b, t = om.beta, om.tau
+    markers = dict(min_alpha=float(om.alpha.min()), eta=float(om.eta), kappa_fp32_zero_frac=_frac(om.kappa == 0), tau_one_frac=_frac(t == 1.0),
+                   tau_zero_frac=_frac(t == 0.0), beta_below_1e30_frac=_frac(b < TAIL), beta_zero_frac=_frac(b == 0))
+    _say(f"fLDA K={K} after {c['iters']} device iterations", **markers)
+    nt = oracle.usable_cpus()
+    for label, kw in (("pinned sweeps viter=5 vtol=0", dict(viter=5, vtol=0.0)), ("default exit rule", dict())):
+        parity.flda_force(gm, om)                                    # the device from the oracle's copy (identical values), then the zeros lifted
+        for n in ("beta", "beta_old", "kappa", "kappa_old"):
+            a = getattr(om, n)
+            a[a == 0.0] = 1e-300
+        block, _ = parity.flda_parity(gm, om, iters=1, threads=nt, **kw)
+        w = block["worst"]
+        _say(f"fLDA K={K} {label}", **{k: w[k] for k in ("gamma_rel_max", "Elogtheta_rel_max", "tau_abs_max", "alpha_rel_max", "eta_abs", "elbo_rel",
+                                                           "sweep_mismatch_frac")})
+        within("trained.flda.gamma_rel", w["gamma_rel_max"], label)
+        within("trained.flda.Elogtheta_rel", w["Elogtheta_rel_max"], label)
+        within("trained.flda.tau_abs", w["tau_abs_max"], label)
+        within("trained.flda.alpha_rel", w["alpha_rel_max"], label)
+        within("trained.flda.eta_abs", w["eta_abs"], label)
+        within("trained.flda.elbo_rel", w["elbo_rel"], (label, w))
+        # kappa where fp32 tau determines it (oracle/parity.py kappa_mask: 1 - tau does not cancel; test_fctm_trained_state, DESIGN.md section 6)
+        within("trained.flda.kappa_rel", w["kappa_rel_max"], (label, block["per_iteration"][0]["kappa_compared_frac"]))
+        _beta_tail(gm, om, "trained.flda", fp32_zeros=False)
+        assert w["sweep_mismatch_frac"] <= parity.FLDA_TOL["sweep_mismatch_frac"], w
+        for n in ("alpha", "gamma", "Elogtheta", "tau", "beta", "kappa"):
+            assert np.all(np.isfinite(getattr(gm, n))), n
+        assert np.isfinite(w["elbo_rel"])
+    oracle.lib().orc_omp_pool_free()
+    # tau = 1.0f: the regime where H(tau) needs its guard
+    for k, lim in (("min_alpha", c["alpha_min"]), ("kappa_fp32_zero_frac", c["kappa_zero_min"]), ("tau_one_frac", c["tau_one_min"]),
+                   ("beta_below_1e30_frac", c["beta_low_min"])):
+        assert markers[k] > lim, (k, markers)
+
+
 # ------------------------------------------------------------------------------------------------------------- CTPF
 def test_ctpf_trained_state(tmvb, oracle):
     """CTPF K = 50 after 300 device iterations (the oracle stays inside [0.1, 4e3] there: for completeness, nothing extreme expected)"""

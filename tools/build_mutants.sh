@@ -1,5 +1,5 @@
 #!/bin/bash
-# The six deliberately WRONG libraries of tests/test_mutants_gpu.py (negative controls of the parity suite), each = the shipped objects with one
+# The seven deliberately WRONG libraries of tests/test_mutants_gpu.py (negative controls of the parity suite), each = the shipped objects with one
 # translation unit recompiled under a -DTMVB_MUTANT_* flag (csrc/tmvb_internal.h lists them):
 #   topicmodelsvb.jl_amd/libtmvb_hip_mut_lda_eps.so     epsilon dropped from LDA's phi / gamma            (src/LDA.jl:152, :145)
 #   topicmodelsvb.jl_amd/libtmvb_hip_mut_ctpf_bet.so    log bet for log vav in CTPF's xi                   (src/CTPF.jl:336 vs src/gpuCTPF.jl:624)
@@ -7,6 +7,7 @@
 #   topicmodelsvb.jl_amd/libtmvb_hip_mut_flda_eps.so    the filtered models' log(beta + eps) without epsilon (src/fLDA.jl:184, :191)
 #   topicmodelsvb.jl_amd/libtmvb_hip_mut_fctm_order.so  fCTM's sweep in CTM's order, vsq before lambda     (src/fCTM.jl:239-240)
 #   topicmodelsvb.jl_amd/libtmvb_hip_mut_lda_stats_eps.so  LDA's statistics pass without eps * sum w      (src/LDA.jl:152)
+#   topicmodelsvb.jl_amd/libtmvb_hip_mut_flda_entropy.so   fLDA's ELBO without the 0 < tau < 1 guard of H(tau) (src/fLDA.jl:94-97)
 # Needs the shipped build first (python -c "import __graft_entry__ as g; g.build()").  ~4 minutes; in parallel (the two builds of tmvb_ctm.hip one after the other: they share a temporary).
 cd "$(dirname "$0")/.." || exit 1
 tools/build_variant.sh mut_lda_eps tmvb_lda.hip -DTMVB_MUTANT_LDA_NO_EPS=1 &
@@ -16,5 +17,6 @@ tools/build_variant.sh mut_flda_eps tmvb_flda.hip -DTMVB_MUTANT_FLDA_NO_EPS=1 &
 wait
 tools/build_variant.sh mut_fctm_order tmvb_ctm.hip -DTMVB_MUTANT_FCTM_VSQ_FIRST=1 &
 tools/build_variant.sh mut_lda_stats_eps tmvb_lda.hip -DTMVB_MUTANT_LDA_STATS_NO_EPS=1 &
+tools/build_variant.sh mut_flda_entropy tmvb_flda.hip -DTMVB_MUTANT_FLDA_H_NO_GUARD=1 &
 wait
 ls -la topicmodelsvb.jl_amd/libtmvb_hip_mut_*.so

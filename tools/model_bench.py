@@ -378,8 +378,18 @@ def flda(burnin=60, warmup=3, steps=20, cpu=True):
 
         def ostep(m, nt):
             m.estep(omp_threads=nt); m.mstep()
+
+        def check(om, iters, threads):
+            from oracle import parity as op
+            g = tm.gpufLDA(sh, K)
+            g.beta = np.asfortranarray(beta0); g.beta_old = g.beta.copy(order="F"); g.kappa = kappa0.copy(); g.kappa_old = kappa0.copy(); g.update_buffer()
+            try:
+                return op.flda_parity(g, om, iters=iters, threads=threads, log=_log)
+            finally:
+                g.close()
         line["cpu_baseline"] = cpu_line("port of src/fLDA.jl train!", lambda: oc.fLDA(oc.CSR(sh.doc_ptr, sh.terms, sh.counts, sh.V), K, beta0, kappa0), ostep,
-                                        sh.nnz / pc.nnz, f"first {sh.M} documents of SYN-NSF ({sh.nnz} of {pc.nnz} nnz), K=50")
+                                        sh.nnz / pc.nnz, f"first {sh.M} documents of SYN-NSF ({sh.nnz} of {pc.nnz} nnz), K=50", check=check)
+        line["parity"] = line["cpu_baseline"].pop("parity", None)
     return line
 
 
@@ -414,8 +424,18 @@ def fctm(burnin=30, warmup=2, steps=6, cpu=True):
 
         def ostep(m, nt):
             m.estep(omp_threads=nt); m.mstep()
+
+        def check(om, iters, threads):
+            from oracle import parity as op
+            g = tm.gpufCTM(sh, K)
+            g.beta = np.asfortranarray(beta0); g.beta_old = g.beta.copy(order="F"); g.kappa = kappa0.copy(); g.kappa_old = kappa0.copy(); g.update_buffer()
+            try:
+                return op.fctm_parity(g, om, iters=iters, threads=threads, log=_log)
+            finally:
+                g.close()
         line["cpu_baseline"] = cpu_line("port of src/fCTM.jl train!", lambda: oc.fCTM(oc.CSR(sh.doc_ptr, sh.terms, sh.counts, sh.V), K, beta0, kappa0), ostep,
-                                        sh.M / pc.M, f"first {sh.M} documents of SYN-NSF (the Newton solves scale with the document count), K=50")
+                                        sh.M / pc.M, f"first {sh.M} documents of SYN-NSF (the Newton solves scale with the document count), K=50", check=check)
+        line["parity"] = line["cpu_baseline"].pop("parity", None)
     return line
 
 

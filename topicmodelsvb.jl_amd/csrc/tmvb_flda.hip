@@ -272,7 +272,7 @@ __global__ __launch_bounds__(64) void flda_elbo_kernel(int K, int KP, const int6
         }
         if (lane == 0) {
             acc += (double)c * (1.0 - (double)tn) * (double)logf(kappa[t] + TMVB_EPS_F);           // Elogpw :83, background part
-            if (tn > 0.0f && tn < 1.0f) acc -= (double)c * ((double)tn * log((double)tn) + (1.0 - (double)tn) * log(1.0 - (double)tn));   // -Elogqc :94-97
+            if (TMVB_FLDA_H_GUARD(tn > 0.0f && tn < 1.0f)) acc -= (double)c * ((double)tn * log((double)tn) + (1.0 - (double)tn) * log(1.0 - (double)tn));   // -Elogqc :94-97
         }
         ta += (double)tn * (double)c; Cd += (double)c;
     }
@@ -325,7 +325,7 @@ __global__ __launch_bounds__(64) void flda_elbo_doc_parts_kernel(int K, const in
         const double tn = (double)tau[off + n], to = (double)tau_old[off + n];
         double v = (double)lse[off + n] + (tn - to) * (double)aold[off + n];
         v += (1.0 - tn) * (double)logf(kappa[terms[off + n]] + TMVB_EPS_F);                         // Elogpw :83, background part
-        if (tn > 0.0 && tn < 1.0) v -= tn * log(tn) + (1.0 - tn) * log(1.0 - tn);                  // -Elogqc :94-97
+        if (TMVB_FLDA_H_GUARD(tn > 0.0 && tn < 1.0)) v -= tn * log(tn) + (1.0 - tn) * log(1.0 - tn);   // -Elogqc :94-97
         acc += c * v;
         ta += tn * c; Cd += c;
     }

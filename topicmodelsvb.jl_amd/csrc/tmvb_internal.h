@@ -152,7 +152,7 @@ int tmvb_comm_allreduce_on(tmvb_comm* c, void* dev_ptr, int64_t count, int32_t d
 int tmvb_corpus_reader_index(tmvb_corpus* c);
 
 // EPSILON of the reference (src/utils.jl:3) = 2^-99, exactly representable in fp32.
-// MUTANTS (tests/test_mutants_gpu.py; never defined in a shipped build): deliberately wrong variants of six operators, one -D flag each, built as
+// MUTANTS (tests/test_mutants_gpu.py; never defined in a shipped build): deliberately wrong variants of seven operators, one -D flag each, built as
 // libtmvb_hip_<name>.so by tools/build_mutants.sh -- the negative controls of the parity suite: a named test must FAIL on each of them.
 //   TMVB_MUTANT_LDA_NO_EPS          epsilon dropped from LDA's phi / gamma (src/LDA.jl:152, :145)
 //   TMVB_MUTANT_CTPF_LOG_BET        `log bet` where xi needs `log vav` (the reference's own OpenCL bug, src/gpuCTPF.jl:624 vs src/CTPF.jl:336)
@@ -160,6 +160,13 @@ int tmvb_corpus_reader_index(tmvb_corpus* c);
 //   TMVB_MUTANT_FLDA_NO_EPS         (round 6) the filtered models' log table without epsilon: log(beta) for log(beta + eps) (src/fLDA.jl:184, :191)
 //   TMVB_MUTANT_FCTM_VSQ_FIRST      (round 6) fCTM's sweep in CTM's order: update_vsq! in front of update_lambda! (src/fCTM.jl:239-240 against src/CTM.jl:198-199)
 //   TMVB_MUTANT_LDA_STATS_NO_EPS    LDA's statistics pass without the eps * sum w term of beta_temp (src/LDA.jl:152); phi and gamma keep theirs
+//   TMVB_MUTANT_FLDA_H_NO_GUARD     fLDA's update_elbo! without the 0 < tau < 1 guard of the Bernoulli entropy (0 log 0 = NaN at tau = 0 or 1,
+//                                   src/fLDA.jl:94-97), in both ELBO forms; only a trained state holds tau = 1.0f
+#ifdef TMVB_MUTANT_FLDA_H_NO_GUARD
+#define TMVB_FLDA_H_GUARD(cond) true
+#else
+#define TMVB_FLDA_H_GUARD(cond) (cond)
+#endif
 #ifdef TMVB_MUTANT_LDA_NO_EPS
 #define TMVB_EPS_F 0.0f
 #else
