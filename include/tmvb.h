@@ -483,6 +483,40 @@ int tmvb_ctpf_last_estep_ms(tmvb_ctpf* h, float* ms);
 int tmvb_ctpf_recommend(tmvb_ctpf* h, double* scores, int32_t* drecs, int32_t* drec_count, int32_t* urecs,
                         int32_t* urec_count, float* ms_scores, float* ms_rank);
 
+/* ============================== gendoc / gencorp (src/modelutils.jl:594-649) ==============================
+ * A model run as a generative process, on the device: for document d of M, C_d ~ Poisson(mean_C) (the caller passes mean(model.C), :597),
+ * theta_d ~ Dirichlet(alpha) (LDA / gpuLDA / fLDA, :598) or additive_logistic(N(mu, sigma)) (CTM / gpuCTM / fCTM, :619; src/utils.jl:125-130),
+ * then C_d tokens z ~ Cat(theta_d), w ~ Cat((beta[z,:] + laplace_smooth) / (1 + laplace_smooth V)) (:601-607).  The reference's CTM method
+ * draws from `topicdist` at :626, a typo for `topic_dist` that throws as written: the intent is implemented.  The reference returns a Dict's
+ * keys / values (unique terms, arbitrary order, :610); here each document is its unique 0-based term ids SORTED ASCENDING with summed counts,
+ * the condensed CSR of tmvb_corpus_create.  A document with C_d = 0 is empty (doc_ptr[d + 1] == doc_ptr[d]).  With laplace_smooth = 0 a
+ * term whose beta entry is exactly zero is never drawn.  The filtered models' kappa / tau take no part (the reference's gendoc ignores them).
+ * Every random number is Philox4x32-10 of (seed, doc_offset + d, stage, draw index): the same seed gives the same bytes, documents
+ * [d0, d0 + m) of a large call equal the call (M = m, doc_offset = d0) -- gendoc is M = 1, and shards of a corpus can be generated apart.
+ * alpha[K] / mu[K], sigma[K*K] (column-major, symmetric; factored on the host in fp64), beta[K*V] column-major, all on the HOST.
+ * flags & 1: also return the diagnostics.  Errors: M <= 0 ("corp_size parameter must be a positive integer.", :643), laplace_smooth < 0
+ * ("laplace_smooth parameter must be nonnegative.", :595 / :644), mean_C <= 0 or not finite, K outside [1, 1024] (LDA) / [1, 256] (CTM), or
+ * more than 2^26 - 1 documents or
+ * 2^31 or more tokens in one call (generate in shards through doc_offset) -> TMVB_EINVAL; beta not right stochastic, alpha not positive, mu not finite, sigma not positive-definite
+ * -> TMVB_ESHAPE with check_model's wording (src/modelutils.jl:47, :56, :114, :116); arguments are judged before the device, then ctx == NULL
+ * without a visible device -> TMVB_ENODEVICE (there is no CPU path).  The arrays of *out are allocated by the library: tmvb_gencorp_free. */
+typedef struct {
+    int64_t M, nnz, sum_counts;
+    int64_t* doc_ptr; int32_t* terms; int32_t* counts;   /* [M+1], [nnz], [nnz] */
+    /* diagnostics, filled only when requested (flags & 1), else NULL */
+    float*   log_theta;    /* [M][K]  log theta_d as drawn */
+    int32_t* doc_topic;    /* [M][K]  tokens of document d assigned to topic k */
+    int64_t* topic_term;   /* [K][V]  tokens drawn as (topic k, term v), before condensing */
+    float    ms_tables, ms_docs, ms_tokens, ms_condense;  /* device time per stage: HIP events around the stage's kernels and library sort / scan calls only */
+} tmvb_gencorp_t;
+int  tmvb_lda_gencorp(tmvb_ctx* ctx, int32_t K, int64_t V, const double* alpha, const double* beta, int64_t M, int64_t doc_offset,
+                      double mean_C, double laplace_smooth, int64_t seed, int32_t flags, tmvb_gencorp_t* out);
+int  tmvb_ctm_gencorp(tmvb_ctx* ctx, int32_t K, int64_t V, const double* mu, const double* sigma, const double* beta, int64_t M,
+                      int64_t doc_offset, double mean_C, double laplace_smooth, int64_t seed, int32_t flags, tmvb_gencorp_t* out);
+void tmvb_gencorp_free(tmvb_gencorp_t* g);
+/* Diagnostics: one block of the generator behind gencorp (Philox4x32-10; Salmon et al., SC'11), on the host: counter[4], key[2] -> out[4]. */
+int  tmvb_philox4x32_10(const uint32_t* counter, const uint32_t* key, uint32_t* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,107 @@
+"""
+gendoc / gencorp (src/modelutils.jl:594-649): a model run as a generative process, on the device.
+
+    gencorp(model, M, laplace_smooth=0.0, seed=0)   -> PackedCorpus of M synthetic documents over the model's vocabulary
+    gendoc(model, laplace_smooth=0.0, seed=0)       -> Document (1-based terms, like every Document)
+
+for LDA / gpuLDA / fLDA (theta ~ Dirichlet(alpha)) and CTM / gpuCTM / fCTM (theta = additive_logistic(N(mu, sigma))).  The reference has no
+method for CTPF; neither has this module.  `gencorp_raw` is the C ABI call itself (tmvb_lda_gencorp / tmvb_ctm_gencorp, include/tmvb.h)
+with the diagnostics and the per-stage device times.  Terms of a document come out sorted ascending (the reference returns a Dict's key
+order).  The reference draws from Julia's global RNG; here `seed` names the corpus: same seed, same bytes, and documents [d0, d0 + m) of a
+corpus are `doc_offset=d0, M=m` of the same seed.  All compute goes through libtmvb_hip.so; there is no CPU fallback.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from ._lib import check, lib, P_dbl, P_i32, P_i64
+from .corpus import Document, PackedCorpus
+from .lda import DeviceContext
+
+
+class GenCorpResult(C.Structure):
+    """tmvb_gencorp_t"""
+    _fields_ = [("M", C.c_int64), ("nnz", C.c_int64), ("sum_counts", C.c_int64),
+                ("doc_ptr", P_i64), ("terms", P_i32), ("counts", P_i32),
+                ("log_theta", C.POINTER(C.c_float)), ("doc_topic", P_i32), ("topic_term", P_i64),
+                ("ms_tables", C.c_float), ("ms_docs", C.c_float), ("ms_tokens", C.c_float), ("ms_condense", C.c_float)]
+
+
+def _copy(ptr, n, dt):
+    n = int(n)
+    if n == 0 or not ptr:
+        return np.zeros(0, dtype=dt)
+    return np.ctypeslib.as_array(ptr, shape=(n,)).astype(dt, copy=True)
+
+
+def gencorp_raw(ctx, K, V, beta, M, mean_C, alpha=None, mu=None, sigma=None, laplace_smooth=0.0, seed=0, doc_offset=0, diagnostics=False):
+    """The ABI call.  alpha -> tmvb_lda_gencorp, (mu, sigma) -> tmvb_ctm_gencorp.  ctx: a DeviceContext, or None for a NULL context (the
+    library then answers TMVB_ENODEVICE on a machine without a GPU).  Returns (status, dict): nothing raises here."""
+    L = lib()
+    L.tmvb_gencorp_free.restype = None
+    f64 = lambda a: np.asfortranarray(np.asarray(a, dtype=np.float64))
+    beta = f64(beta)
+    out = GenCorpResult()
+    h = ctx.handle if ctx is not None else C.c_void_p(None)
+    tail = (C.c_int64(int(M)), C.c_int64(int(doc_offset)), C.c_double(mean_C), C.c_double(laplace_smooth),
+            C.c_int64(np.uint64(int(seed) % 2 ** 64).astype(np.int64)), C.c_int32(1 if diagnostics else 0), C.byref(out))
+    if alpha is not None:
+        alpha = f64(alpha)
+        rc = L.tmvb_lda_gencorp(h, C.c_int32(K), C.c_int64(V), alpha.ctypes.data_as(P_dbl), beta.ctypes.data_as(P_dbl), *tail)
+    else:
+        mu, sigma = f64(mu), f64(sigma)
+        rc = L.tmvb_ctm_gencorp(h, C.c_int32(K), C.c_int64(V), mu.ctypes.data_as(P_dbl), sigma.ctypes.data_as(P_dbl), beta.ctypes.data_as(P_dbl), *tail)
+    if rc != 0:
+        return rc, {"error": L.tmvb_last_error().decode("utf-8", "replace")}
+    try:
+        M = int(out.M)
+        res = {"M": M, "nnz": int(out.nnz), "sum_counts": int(out.sum_counts),
+               "doc_ptr": _copy(out.doc_ptr, M + 1, np.int64), "terms": _copy(out.terms, out.nnz, np.int32), "counts": _copy(out.counts, out.nnz, np.int32),
+               "ms": {s: float(getattr(out, "ms_" + s)) for s in ("tables", "docs", "tokens", "condense")}}
+        if diagnostics:
+            res["log_theta"] = _copy(out.log_theta, M * K, np.float32).reshape(M, K)
+            res["doc_topic"] = _copy(out.doc_topic, M * K, np.int32).reshape(M, K)
+            res["topic_term"] = _copy(out.topic_term, K * V, np.int64).reshape(K, V)
+    finally:
+        L.tmvb_gencorp_free(C.byref(out))
+    return rc, res
+
+
+def _family(model):
+    if hasattr(model, "alef"):
+        raise TypeError("gendoc / gencorp have no method for CTPF models (src/modelutils.jl:594-633 covers LDA, fLDA, CTM, fCTM and their gpu forms).")
+    if hasattr(model, "alpha"):
+        return {"alpha": model.alpha}
+    if hasattr(model, "mu") and hasattr(model, "sigma"):
+        return {"mu": model.mu, "sigma": model.sigma}
+    raise TypeError("gendoc / gencorp need an LDA, fLDA, CTM or fCTM model (or its gpu form).")
+
+
+def gencorp(model, M, laplace_smooth: float = 0.0, seed: int = 0, doc_offset: int = 0, device_id: int = 0) -> PackedCorpus:
+    """gencorp(model, M; laplace_smooth) (src/modelutils.jl:642-649)."""
+    if not (isinstance(M, (int, np.integer)) and not isinstance(M, bool) and M > 0):
+        raise ValueError("corp_size parameter must be a positive integer.")
+    if not laplace_smooth >= 0:
+        raise ValueError("laplace_smooth parameter must be nonnegative.")
+    fam = _family(model)
+    # like the reference, a gpu model is read through its HOST fields (alpha / mu / sigma / beta as train! left them)
+    own = getattr(model, "ctx", None) is None
+    ctx = DeviceContext(device_id) if own else model.ctx
+    try:
+        rc, res = gencorp_raw(ctx, model.K, model.V, model.beta, M, float(np.mean(model.C)), laplace_smooth=float(laplace_smooth), seed=seed,
+                              doc_offset=doc_offset, **fam)
+    finally:
+        if own:
+            ctx.close()
+    check(rc)
+    return PackedCorpus(res["doc_ptr"], res["terms"], res["counts"], model.V)
+
+
+def gendoc(model, laplace_smooth: float = 0.0, seed: int = 0, device_id: int = 0) -> Document:
+    """gendoc(model, laplace_smooth) (src/modelutils.jl:594-633): document 0 of the corpus `seed` names."""
+    if not laplace_smooth >= 0:
+        raise ValueError("laplace_smooth parameter must be nonnegative.")
+    pc = gencorp(model, 1, laplace_smooth, seed, 0, device_id)
+    return Document(terms=pc.terms.astype(np.int64) + 1, counts=pc.counts)

@@ -10,7 +10,7 @@
 #     update_xi!/update_phi!/update_zayin!/update_gimel! (CTPF) are reached through `update_estep!`;
 #   * train! has the signatures and defaults of src/gpuLDA.jl:347, src/gpuCTM.jl:487, src/gpuCTPF.jl:677; argument errors
 #     are ArgumentError, state errors TopicModelError, corpus errors CorpusError, with the reference's messages;
-#   * predict / topicdist methods for the hip types (src/modelutils.jl:831-913, :946-970);
+#   * predict / topicdist methods for the hip types (src/modelutils.jl:831-913, :946-970); gendoc / gencorp (:594-649) on the device;
 #   * NEW: document-sharded multi-GPU train! behind the same call -- `hipComm` wraps the library's communicator (RCCL
 #     over xGMI, or a host all-reduce callback), `train!(::Vector{hipLDA})` drives n GPUs from one host thread.
 #
@@ -811,4 +811,73 @@ end
 function topicdist(model::hipfCTM, d::Integer)      # src/modelutils.jl:953-958
 	(d <= length(model.corp)) || throw(CorpusError("document index outside corpus range."))
 	return additive_logistic(model.lambda[d] + 0.5 * model.vsq[d])
+end
+
+# ---------------------------------------------------------------------------------------------- gendoc / gencorp
+# gendoc / gencorp (src/modelutils.jl:594-649) on the device (tmvb_lda_gencorp / tmvb_ctm_gencorp): Poisson lengths, Dirichlet or
+# logistic-normal theta, two categorical draws per token, condensed on the device.  Methods for the hip types only, like predict's: the
+# package's own gendoc / gencorp keep serving the host models (its CTM method throws at :626; `gencorp(hipCTM(model), M)` is the way round).
+# The reference draws from Julia's global RNG;
+# here `seed` names the corpus (same seed, same documents; documents d0+1 .. d0+m of a corpus are `doc_offset=d0, M=m`).  Terms of a document
+# come out sorted ascending.
+
+"tmvb_gencorp_t (include/tmvb.h), field for field."
+mutable struct TmvbGencorp
+	M::Int64; nnz::Int64; sum_counts::Int64
+	doc_ptr::Ptr{Int64}; terms::Ptr{Int32}; counts::Ptr{Int32}
+	log_theta::Ptr{Float32}; doc_topic::Ptr{Int32}; topic_term::Ptr{Int64}
+	ms_tables::Float32; ms_docs::Float32; ms_tokens::Float32; ms_condense::Float32
+	TmvbGencorp() = new(0, 0, 0, C_NULL, C_NULL, C_NULL, C_NULL, C_NULL, C_NULL, 0f0, 0f0, 0f0, 0f0)
+end
+
+const DirichletModels = Union{hipLDA, hipfLDA}
+const LogisticNormalModels = Union{hipCTM, hipfCTM}
+
+function gencorp_docs(out::TmvbGencorp)
+	doc_ptr = unsafe_wrap(Array, out.doc_ptr, out.M + 1)
+	terms = unsafe_wrap(Array, out.terms, out.nnz); counts = unsafe_wrap(Array, out.counts, out.nnz)
+	[Document(terms=Int.(terms[doc_ptr[d]+1:doc_ptr[d+1]]) .+ 1, counts=Int.(counts[doc_ptr[d]+1:doc_ptr[d+1]])) for d in 1:out.M]
+end
+
+function hip_gencorp(model::DirichletModels, M::Integer, laplace_smooth::Real, seed::Integer, doc_offset::Integer)
+	ctx = model.ctx
+	out = TmvbGencorp()
+	alpha = Vector{Float64}(model.alpha); beta = Matrix{Float64}(model.beta)
+	GC.@preserve out alpha beta begin
+		tmvb_check(ccall((:tmvb_lda_gencorp, LIBTMVB), Cint,
+			(Ptr{Cvoid}, Int32, Int64, Ptr{Float64}, Ptr{Float64}, Int64, Int64, Float64, Float64, Int64, Int32, Ptr{Cvoid}),
+			ctx, model.K, model.V, alpha, beta, M, doc_offset, mean(model.C), laplace_smooth, seed, 0, pointer_from_objref(out)))
+		docs = gencorp_docs(out)
+		ccall((:tmvb_gencorp_free, LIBTMVB), Cvoid, (Ptr{Cvoid},), pointer_from_objref(out))
+		return docs
+	end
+end
+
+function hip_gencorp(model::LogisticNormalModels, M::Integer, laplace_smooth::Real, seed::Integer, doc_offset::Integer)
+	ctx = model.ctx
+	out = TmvbGencorp()
+	mu = Vector{Float64}(model.mu); sigma = Matrix{Float64}(model.sigma); beta = Matrix{Float64}(model.beta)
+	GC.@preserve out mu sigma beta begin
+		tmvb_check(ccall((:tmvb_ctm_gencorp, LIBTMVB), Cint,
+			(Ptr{Cvoid}, Int32, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Int64, Float64, Float64, Int64, Int32, Ptr{Cvoid}),
+			ctx, model.K, model.V, mu, sigma, beta, M, doc_offset, mean(model.C), laplace_smooth, seed, 0, pointer_from_objref(out)))
+		docs = gencorp_docs(out)
+		ccall((:tmvb_gencorp_free, LIBTMVB), Cvoid, (Ptr{Cvoid},), pointer_from_objref(out))
+		return docs
+	end
+end
+
+"gendoc (src/modelutils.jl:594-633) on the device: document 1 of the corpus `seed` names."
+function gendoc(model::Union{DirichletModels, LogisticNormalModels}, laplace_smooth::Real=0.0; seed::Integer=rand(Int64))
+	(laplace_smooth >= 0) || throw(ArgumentError("laplace_smooth parameter must be nonnegative."))
+	return hip_gencorp(model, 1, laplace_smooth, seed, 0)[1]
+end
+
+"gencorp (src/modelutils.jl:642-649) on the device."
+function gencorp(model::Union{DirichletModels, LogisticNormalModels}, M::Integer; laplace_smooth::Real=0.0, seed::Integer=rand(Int64), doc_offset::Integer=0)
+	(M > 0)					|| throw(ArgumentError("corp_size parameter must be a positive integer."))
+	(laplace_smooth >= 0)	|| throw(ArgumentError("laplace_smooth parameter must be nonnegative."))
+	corp = Corpus(vocab=model.corp.vocab, users=model.corp.users)
+	corp.docs = hip_gencorp(model, M, laplace_smooth, seed, doc_offset)
+	return corp
 end
