@@ -517,6 +517,45 @@ void tmvb_gencorp_free(tmvb_gencorp_t* g);
 /* Diagnostics: one block of the generator behind gencorp (Philox4x32-10; Salmon et al., SC'11), on the host: counter[4], key[2] -> out[4]. */
 int  tmvb_philox4x32_10(const uint32_t* counter, const uint32_t* key, uint32_t* out);
 
+/* ============================== held-out evaluation: token split, predictive log-likelihood ==============================
+ * Document completion (the reference has no such function): split the tokens of unseen documents into an
+ * observed and a held-out part, fold the observed part in with predict, score the held-out part under the predicted topic proportions.
+ *
+ * tmvb_corpus_split: the host CSR of tmvb_corpus_create (doc_ptr[M+1], terms[nnz], counts[nnz]) -> two host CSRs over the same M and V.
+ * Draw rule: the token occurrences of document d are numbered t = 0 .. C_d - 1 in CSR order (entry j's counts[j] occurrences are
+ * consecutive); the 32-bit word of occurrence t is x[t & 3] of Philox4x32-10 with key = seed and counter = (doc_offset + d, stage
+ * TMVB_RNG_SPLIT = 5, draw t >> 2) (csrc/tmvb_philox.h: tmvb_rng); occurrence t is HELD OUT iff word < floor(frac * 2^32) (as 64-bit
+ * integers: frac = 0 holds out nothing, frac = 1 everything).  Entries whose count became 0 are dropped, the order of terms inside a
+ * document is kept, a document may be empty on either side, obs + held reproduces the input exactly, and documents [d0, d0 + m) of a
+ * large call equal the call (M = m, doc_offset = d0).  Errors, judged before the device is touched: frac outside [0, 1] or not finite,
+ * M <= 0, V <= 0, doc_offset < 0, NULL argument, 2^31 - 1 or more entries, a document of 2^31 or more tokens -> TMVB_EINVAL; doc_ptr
+ * not non-decreasing from 0, a term outside [0, V), a count < 1 -> TMVB_ESHAPE; then ctx == NULL without a visible device ->
+ * TMVB_ENODEVICE.  The arrays of *out are allocated by the library: tmvb_split_free.  ms_draw / ms_compact: device time of the draw
+ * (scan of the counts + draw kernel) and of the compaction (flags, two scans, scatter), HIP events around kernels and scans only. */
+typedef struct {
+    int64_t M, nnz_obs, nnz_held, sum_obs, sum_held;
+    int64_t* obs_ptr;  int32_t* obs_terms;  int32_t* obs_counts;     /* [M+1], [nnz_obs], [nnz_obs] */
+    int64_t* held_ptr; int32_t* held_terms; int32_t* held_counts;    /* [M+1], [nnz_held], [nnz_held] */
+    float    ms_draw, ms_compact;
+} tmvb_split_t;
+int  tmvb_corpus_split(tmvb_ctx* ctx, int64_t M, int64_t V, const int64_t* doc_ptr, const int32_t* terms, const int32_t* counts,
+                       double frac, int64_t seed, int64_t doc_offset, tmvb_split_t* out);
+void tmvb_split_free(tmvb_split_t* s);
+
+/* tmvb_heldout_loglik: ll[d] = sum_n c_n log( sum_k theta[k,d] beta'[k,w_n] ) over the entries (w_n, c_n) of document d of the host CSR,
+ * beta' = (beta + laplace_smooth) / (1 + laplace_smooth V) (gendoc's smoothing, src/modelutils.jl:601-607); tokens[d] = sum_n c_n; an
+ * empty document has ll = 0.  An entry whose mixture probability is exactly 0 makes ll[d] = -inf and adds its count to
+ * *zero_prob_tokens; no epsilon is added.  theta[K*M] and beta[K*V] are column-major fp64 on the HOST; the device holds both in fp32
+ * (beta' in the gather layout [V][KP], KP = 4 * odd >= K), the dot products are fp32 FMAs, the logarithm and the per-document sum fp64.
+ * No atomics: two calls give the same bits.  Errors: K outside [1, 1024], laplace_smooth < 0 or not finite, M <= 0, V <= 0, NULL
+ * argument, 2^31 - 1 or more entries -> TMVB_EINVAL; bad CSR (as above), beta not right stochastic ("beta must be a right stochastic
+ * matrix.", check_model's wording), a theta column with a negative or non-finite entry or a sum further than 1e-6 from 1 -> TMVB_ESHAPE;
+ * arguments are judged before the device, then ctx == NULL without a visible device -> TMVB_ENODEVICE.  ms_kernel (or NULL): device
+ * time of the scoring kernels. */
+int tmvb_heldout_loglik(tmvb_ctx* ctx, int32_t K, int64_t V, int64_t M, const double* theta, const double* beta, const int64_t* doc_ptr,
+                        const int32_t* terms, const int32_t* counts, double laplace_smooth, double* ll, int64_t* tokens,
+                        int64_t* zero_prob_tokens, float* ms_kernel);
+
 #ifdef __cplusplus
 }
 #endif

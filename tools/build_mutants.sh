@@ -1,5 +1,5 @@
 #!/bin/bash
-# The seven deliberately WRONG libraries of tests/test_mutants_gpu.py (negative controls of the parity suite), each = the shipped objects with one
+# The deliberately WRONG libraries of tests/test_mutants_gpu.py and tests/test_heldout_mutant_gpu.py (negative controls of the parity suite), each = the shipped objects with one
 # translation unit recompiled under a -DTMVB_MUTANT_* flag (csrc/tmvb_internal.h lists them):
 #   topicmodelsvb.jl_amd/libtmvb_hip_mut_lda_eps.so     epsilon dropped from LDA's phi / gamma            (src/LDA.jl:152, :145)
 #   topicmodelsvb.jl_amd/libtmvb_hip_mut_ctpf_bet.so    log bet for log vav in CTPF's xi                   (src/CTPF.jl:336 vs src/gpuCTPF.jl:624)
@@ -8,6 +8,7 @@
 #   topicmodelsvb.jl_amd/libtmvb_hip_mut_fctm_order.so  fCTM's sweep in CTM's order, vsq before lambda     (src/fCTM.jl:239-240)
 #   topicmodelsvb.jl_amd/libtmvb_hip_mut_lda_stats_eps.so  LDA's statistics pass without eps * sum w      (src/LDA.jl:152)
 #   topicmodelsvb.jl_amd/libtmvb_hip_mut_flda_entropy.so   fLDA's ELBO without the 0 < tau < 1 guard of H(tau) (src/fLDA.jl:94-97)
+#   topicmodelsvb.jl_amd/libtmvb_hip_mut_heldout_tail.so   held-out scoring kernel without the last partial 16-byte chunk of a beta row (tests/test_heldout_mutant_gpu.py)
 # Needs the shipped build first (python -c "import __graft_entry__ as g; g.build()").  ~4 minutes; in parallel (the two builds of tmvb_ctm.hip one after the other: they share a temporary).
 cd "$(dirname "$0")/.." || exit 1
 tools/build_variant.sh mut_lda_eps tmvb_lda.hip -DTMVB_MUTANT_LDA_NO_EPS=1 &
@@ -18,5 +19,6 @@ wait
 tools/build_variant.sh mut_fctm_order tmvb_ctm.hip -DTMVB_MUTANT_FCTM_VSQ_FIRST=1 &
 tools/build_variant.sh mut_lda_stats_eps tmvb_lda.hip -DTMVB_MUTANT_LDA_STATS_NO_EPS=1 &
 tools/build_variant.sh mut_flda_entropy tmvb_flda.hip -DTMVB_MUTANT_FLDA_H_NO_GUARD=1 &
+tools/build_variant.sh mut_heldout_tail tmvb_heldout.hip -DTMVB_MUTANT_HELDOUT_DROP_TAIL=1 &
 wait
 ls -la topicmodelsvb.jl_amd/libtmvb_hip_mut_*.so

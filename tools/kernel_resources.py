@@ -34,6 +34,8 @@ BENCHED = {
     # config 5: CTPF K = 50
     "ctpf_estep_grid_narrow_kernel<13>": 0, "ctpf_estep_grid_wide_kernel<13>": 0, "ctpf_estep_grid_long2_kernel<13>": 0, "termstats_recompute2_kernel<13": 0,
     "ctpf_mstep_kernel": 0,
+    # held-out evaluation (tools/heldout_bench.py): the scoring kernel's two workgroup sizes and the split's draw kernel
+    "heldout_loglik_kernel<64>": 0, "heldout_loglik_kernel<256>": 0, "split_draw_kernel": 0,
 }
 
 

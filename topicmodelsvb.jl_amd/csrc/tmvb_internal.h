@@ -162,6 +162,8 @@ int tmvb_corpus_reader_index(tmvb_corpus* c);
 //   TMVB_MUTANT_LDA_STATS_NO_EPS    LDA's statistics pass without the eps * sum w term of beta_temp (src/LDA.jl:152); phi and gamma keep theirs
 //   TMVB_MUTANT_FLDA_H_NO_GUARD     fLDA's update_elbo! without the 0 < tau < 1 guard of the Bernoulli entropy (0 log 0 = NaN at tau = 0 or 1,
 //                                   src/fLDA.jl:94-97), in both ELBO forms; only a trained state holds tau = 1.0f
+//   TMVB_MUTANT_HELDOUT_DROP_TAIL   the held-out scoring kernel (tmvb_heldout.hip) drops the last, partial 16-byte chunk of a beta row (K not a multiple of 4);
+//                                   tests/test_heldout_mutant_gpu.py
 #ifdef TMVB_MUTANT_FLDA_H_NO_GUARD
 #define TMVB_FLDA_H_GUARD(cond) true
 #else

@@ -881,3 +881,86 @@ function gencorp(model::Union{DirichletModels, LogisticNormalModels}, M::Integer
 	corp.docs = hip_gencorp(model, M, laplace_smooth, seed, doc_offset)
 	return corp
 end
+
+# ---------------------------------------------------------------------------------------------- held-out evaluation
+# Document-completion perplexity (the reference has no such function; SURVEY section 8(f) item 1 names it as the purpose of predict):
+# split_corp holds every token occurrence of a corpus out with probability frac (tmvb_corpus_split: a pure function of seed, document and
+# occurrence, Philox4x32-10 -- the same seed gives the same split, doc_offset reproduces a slice), heldout_loglik folds the observed side in
+# with the hip model's predict, takes topicdist of every document as theta and scores the held-out side under model.beta on the device
+# (tmvb_heldout_loglik).  The filtered models' kappa / tau take no part in the score, as in the reference's gendoc.
+
+"tmvb_split_t (include/tmvb.h), field for field."
+mutable struct TmvbSplit
+	M::Int64; nnz_obs::Int64; nnz_held::Int64; sum_obs::Int64; sum_held::Int64
+	obs_ptr::Ptr{Int64}; obs_terms::Ptr{Int32}; obs_counts::Ptr{Int32}
+	held_ptr::Ptr{Int64}; held_terms::Ptr{Int32}; held_counts::Ptr{Int32}
+	ms_draw::Float32; ms_compact::Float32
+	TmvbSplit() = new(0, 0, 0, 0, 0, C_NULL, C_NULL, C_NULL, C_NULL, C_NULL, C_NULL, 0f0, 0f0)
+end
+
+function corp_csr(corp::Corpus)
+	doc_ptr = Int64[0; cumsum([length(doc.terms) for doc in corp])]
+	terms   = Int32.(reduce(vcat, [doc.terms for doc in corp]; init=Int[]) .- 1)
+	counts  = Int32.(reduce(vcat, [doc.counts for doc in corp]; init=Int[]))
+	return doc_ptr, terms, counts
+end
+
+function split_docs(p::Ptr{Int64}, t::Ptr{Int32}, c::Ptr{Int32}, M::Integer, nnz::Integer)
+	doc_ptr = unsafe_wrap(Array, p, M + 1)
+	terms = unsafe_wrap(Array, t, nnz); counts = unsafe_wrap(Array, c, nnz)
+	[Document(terms=Int.(terms[doc_ptr[d]+1:doc_ptr[d+1]]) .+ 1, counts=Int.(counts[doc_ptr[d]+1:doc_ptr[d+1]])) for d in 1:M]
+end
+
+"(observed, heldout): two corpora over the vocabulary of `corp`; every token occurrence is held out with probability frac."
+function split_corp(corp::Corpus; frac::Real=0.5, seed::Integer=0, doc_offset::Integer=0, device::Integer=0)
+	check_corp(corp)
+	M, V, U = size(corp)
+	doc_ptr, terms, counts = corp_csr(corp)
+	ctx = tmvb_context(device)
+	out = TmvbSplit()
+	GC.@preserve out doc_ptr terms counts begin
+		rc = ccall((:tmvb_corpus_split, LIBTMVB), Cint,
+			(Ptr{Cvoid}, Int64, Int64, Ptr{Int64}, Ptr{Int32}, Ptr{Int32}, Float64, Int64, Int64, Ptr{Cvoid}),
+			ctx, M, V, doc_ptr, terms, counts, frac, seed, doc_offset, pointer_from_objref(out))
+		tmvb_destroy_context(ctx)
+		tmvb_check(rc)
+		observed = Corpus(vocab=corp.vocab, users=corp.users); heldout = Corpus(vocab=corp.vocab, users=corp.users)
+		observed.docs = split_docs(out.obs_ptr, out.obs_terms, out.obs_counts, out.M, out.nnz_obs)
+		heldout.docs = split_docs(out.held_ptr, out.held_terms, out.held_counts, out.M, out.nnz_held)
+		ccall((:tmvb_split_free, LIBTMVB), Cvoid, (Ptr{Cvoid},), pointer_from_objref(out))
+		return observed, heldout
+	end
+end
+
+"""
+(ll, tokens, zero_prob_tokens, perplexity) of the held-out words: ll[d] = sum_n c_n log(sum_k theta[k,d] beta'[k,w_n]) with theta the
+topicdist of predict(observed, model) and beta' = (beta + laplace_smooth) / (1 + laplace_smooth V); perplexity = exp(-sum(ll) / sum(tokens)).
+"""
+function heldout_loglik(model::Union{DirichletModels, LogisticNormalModels}, observed::Corpus, heldout::Corpus; laplace_smooth::Real=0.0, kwargs...)
+	(heldout.vocab == model.corp.vocab)		|| throw(CorpusError("predict corpus and train_model corpus must have identical vocabularies."))
+	(length(observed) == length(heldout))	|| throw(CorpusError("observed and heldout corpora must hold the same documents."))
+	(laplace_smooth >= 0)					|| throw(ArgumentError("laplace_smooth parameter must be nonnegative."))
+	pred = predict(observed, model; kwargs...)
+	M = length(heldout)
+	theta = Matrix{Float64}(undef, model.K, M)
+	for d in 1:M
+		theta[:,d] = topicdist(pred, d)
+	end
+	beta = Matrix{Float64}(model.beta)
+	doc_ptr, terms, counts = corp_csr(heldout)
+	ll = zeros(Float64, M); tokens = zeros(Int64, M); zero_prob = Ref{Int64}(0); ms = Ref{Float32}(0f0)
+	GC.@preserve theta beta doc_ptr terms counts ll tokens begin
+		tmvb_check(ccall((:tmvb_heldout_loglik, LIBTMVB), Cint,
+			(Ptr{Cvoid}, Int32, Int64, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Int32}, Ptr{Int32}, Float64, Ptr{Float64}, Ptr{Int64}, Ref{Int64}, Ref{Float32}),
+			model.ctx, model.K, model.V, M, theta, beta, doc_ptr, terms, counts, laplace_smooth, ll, tokens, zero_prob, ms))
+	end
+	n = sum(tokens)
+	ppl = n == 0 ? NaN : (any(isinf, ll) ? Inf : exp(-sum(ll) / n))
+	return (ll=ll, tokens=tokens, zero_prob_tokens=zero_prob[], perplexity=ppl)
+end
+
+"Document-completion perplexity of `corp` (unseen documents) under `model`: split_corp, then heldout_loglik."
+function perplexity(model::Union{DirichletModels, LogisticNormalModels}, corp::Corpus; frac::Real=0.5, seed::Integer=0, kwargs...)
+	observed, heldout = split_corp(corp; frac=frac, seed=seed)
+	return heldout_loglik(model, observed, heldout; kwargs...).perplexity
+end
