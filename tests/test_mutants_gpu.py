@@ -1,7 +1,7 @@
 """
 NEGATIVE CONTROLS of the parity suite (round-4 review: "there is no deliberately wrong variant that must fail").
 
-Seven mutant libraries (three of round 5, two of round 6 for the SURVEY.md section 8(f) rows, two for the trained-state tests) -- the shipped objects with ONE translation unit recompiled under a -DTMVB_MUTANT_* flag (csrc/tmvb_internal.h, tools/build_mutants.sh) -- each
+Eight mutant libraries (three of round 5, two of round 6 for the SURVEY.md section 8(f) rows, two for the trained-state tests, one for the train loop's flags) -- the shipped objects with ONE translation unit recompiled under a -DTMVB_MUTANT_* flag (csrc/tmvb_internal.h, tools/build_mutants.sh) -- each
 wrong in one operator, in a way a careless port of the reference would be:
   mut_lda_eps    epsilon dropped from LDA's update_phi! / update_gamma!            src/LDA.jl:152, :145
   mut_ctpf_bet   `log bet` where update_xi! needs `log vav`                         src/CTPF.jl:336 -- the reference's own OpenCL path has this bug, src/gpuCTPF.jl:624
@@ -10,6 +10,7 @@ wrong in one operator, in a way a careless port of the reference would be:
   mut_fctm_order fCTM's sweep in CTM's order (update_vsq! before update_lambda!)    src/fCTM.jl:239-240 against src/CTM.jl:198-199
   mut_lda_stats_eps  LDA's statistics pass without the eps * sum w term of beta_temp   src/LDA.jl:152 (phi and gamma keep their epsilon)
   mut_flda_entropy   fLDA's ELBO without the 0 < tau < 1 guard of H(tau) (0 log 0)     src/fLDA.jl:94-97 (both ELBO forms)
+  mut_lda_stale_parts  tmvb_lda_estep leaves the previous iteration's ELBO parts marked valid    csrc/tmvb_lda.hip (logz_valid, pw_diff): a flag of the host state machine, not arithmetic
 For each, a NAMED parity test is run in a fresh pytest process with TMVB_LIB_VARIANT=<mutant> and must FAIL with an assertion of that test (not an import
 error, not a crash), while the shipped library passes the same test in the ordinary suite.  A parity suite that stays green on these would have no teeth.
 """
@@ -40,6 +41,10 @@ MUTANTS = {
     # tau reaches 0 or 1 exactly only in a trained state: tests/test_flda_gpu.py and tests/test_flda_elbo_parts_gpu.py pass on this mutant
     "mut_flda_entropy": ("tmvb_flda.hip", "-DTMVB_MUTANT_FLDA_H_NO_GUARD=1",
                          ["tests/test_trained_state_parity_gpu.py::test_flda_trained_state[50]"]),
+    # a stepwise iteration behind a collecting train! evaluates the ELBO from the previous iteration's parts: off by a whole increment (scenario E); every test
+    # that sets the state between iterations, or checks every iteration, passes on this mutant
+    "mut_lda_stale_parts": ("tmvb_lda.hip", "-DTMVB_MUTANT_LDA_STALE_PARTS=1",
+                            ["tests/test_train_loop_gpu.py::test_e_stepwise_iteration_behind_a_collecting_train[lda_k20]"]),
 }
 
 

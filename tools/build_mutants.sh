@@ -8,8 +8,10 @@
 #   topicmodelsvb.jl_amd/libtmvb_hip_mut_fctm_order.so  fCTM's sweep in CTM's order, vsq before lambda     (src/fCTM.jl:239-240)
 #   topicmodelsvb.jl_amd/libtmvb_hip_mut_lda_stats_eps.so  LDA's statistics pass without eps * sum w      (src/LDA.jl:152)
 #   topicmodelsvb.jl_amd/libtmvb_hip_mut_flda_entropy.so   fLDA's ELBO without the 0 < tau < 1 guard of H(tau) (src/fLDA.jl:94-97)
+#   topicmodelsvb.jl_amd/libtmvb_hip_mut_lda_stale_parts.so  tmvb_lda_estep keeps the previous iteration's ELBO parts marked valid (tests/test_train_loop_gpu.py, scenario E)
 #   topicmodelsvb.jl_amd/libtmvb_hip_mut_heldout_tail.so   held-out scoring kernel without the last partial 16-byte chunk of a beta row (tests/test_heldout_mutant_gpu.py)
-# Needs the shipped build first (python -c "import __graft_entry__ as g; g.build()").  ~4 minutes; in parallel (the two builds of tmvb_ctm.hip one after the other: they share a temporary).
+# Needs the shipped build first (python -c "import __graft_entry__ as g; g.build()").  In parallel, but two builds of one translation unit never in the same batch (they share a temporary): tmvb_ctm.hip has two
+# variants, tmvb_lda.hip three, hence three batches, the third holding mut_lda_stale_parts alone.  About 4 minutes for the first two batches plus one more build of tmvb_lda.hip.
 cd "$(dirname "$0")/.." || exit 1
 tools/build_variant.sh mut_lda_eps tmvb_lda.hip -DTMVB_MUTANT_LDA_NO_EPS=1 &
 tools/build_variant.sh mut_ctpf_bet tmvb_ctpf.hip -DTMVB_MUTANT_CTPF_LOG_BET=1 &
@@ -20,5 +22,7 @@ tools/build_variant.sh mut_fctm_order tmvb_ctm.hip -DTMVB_MUTANT_FCTM_VSQ_FIRST=
 tools/build_variant.sh mut_lda_stats_eps tmvb_lda.hip -DTMVB_MUTANT_LDA_STATS_NO_EPS=1 &
 tools/build_variant.sh mut_flda_entropy tmvb_flda.hip -DTMVB_MUTANT_FLDA_H_NO_GUARD=1 &
 tools/build_variant.sh mut_heldout_tail tmvb_heldout.hip -DTMVB_MUTANT_HELDOUT_DROP_TAIL=1 &
+wait
+tools/build_variant.sh mut_lda_stale_parts tmvb_lda.hip -DTMVB_MUTANT_LDA_STALE_PARTS=1 &
 wait
 ls -la topicmodelsvb.jl_amd/libtmvb_hip_mut_*.so

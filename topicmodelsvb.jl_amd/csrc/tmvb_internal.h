@@ -164,6 +164,8 @@ int tmvb_corpus_reader_index(tmvb_corpus* c);
 //                                   src/fLDA.jl:94-97), in both ELBO forms; only a trained state holds tau = 1.0f
 //   TMVB_MUTANT_HELDOUT_DROP_TAIL   the held-out scoring kernel (tmvb_heldout.hip) drops the last, partial 16-byte chunk of a beta row (K not a multiple of 4);
 //                                   tests/test_heldout_mutant_gpu.py
+//   TMVB_MUTANT_LDA_STALE_PARTS     tmvb_lda_estep does not clear logz_valid / pw_diff at its start and keeps logz_valid when it does not collect: a stepwise
+//                                   iteration behind a collecting train! evaluates the ELBO from the previous iteration's parts (tests/test_train_loop_gpu.py, scenario E)
 #ifdef TMVB_MUTANT_FLDA_H_NO_GUARD
 #define TMVB_FLDA_H_GUARD(cond) true
 #else

@@ -1744,7 +1744,9 @@ static int lda_estep_impl(tmvb_lda* h, int32_t viter, double vtol)
             h->logz_cap = need;
         }
     }
+#ifndef TMVB_MUTANT_LDA_STALE_PARTS     // MUTANT (tests/test_mutants_gpu.py, never in a shipped build): the previous iteration's parts stay marked valid
     h->logz_valid = false; h->pw_diff = false;
+#endif
     auto with_logz = [&](TermStatsParams t, int q) { t.logz = collect ? h->d_logz + logz_off[(size_t)q] : nullptr; return t; };
     // Round 5: the passes before the last accumulate in order in d_stats on aux[0]; the LAST pass, on the context's stream behind the last document
     // kernel, used to wait for them (round 4's timeline: last document kernel done at 589 us, pass 2 + its combine at 625 us, one cross-queue hop, last
@@ -1921,7 +1923,11 @@ static int lda_estep_impl(tmvb_lda* h, int32_t viter, double vtol)
         h->esum_fresh = true; h->esum_side = true;
     }
     h->stats_fresh = !(p.debug & 1); h->pw_valid = false;
+#ifdef TMVB_MUTANT_LDA_STALE_PARTS
+    if (collect) { h->logz_valid = true; h->n_logz = logz_off[(size_t)P]; }     // MUTANT: an E-step that does not collect leaves the old flag and count alone
+#else
     h->logz_valid = collect; h->n_logz = collect ? logz_off[(size_t)P] : 0;
+#endif
     if (h->timing) TMVB_HIP(hipEventRecord(h->ev1, ctx->stream));
     h->timed = true;
     return TMVB_OK;
