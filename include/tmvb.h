@@ -124,7 +124,14 @@ int tmvb_rccl_version(void);
 /* ---- corpus upload: the corpus half of update_buffer! (src/modelutils.jl:370-388, :438-472) ----
  * doc_ptr[M+1], terms[nnz], counts[nnz]; rdr_ptr/readers/ratings may be NULL when U == 0.
  * Validates the check_doc / check_corp rules (src/Corpus.jl:41-50, :111-122): ids in range,
- * counts and ratings positive, offsets monotone. */
+ * counts and ratings positive, offsets monotone.
+ * PRESENTATION: inside a document the term (and reader) ids need be neither sorted nor unique, and documents and ids may come in
+ * any order.  A repeated id ACCUMULATES: every model computes what it computes on the condensed document (unique ids, counts
+ * summed; condense_corp!, src/Corpus.jl:523), up to the fp32 summation order -- the reference's CPU path differs there, it
+ * overwrites (quirk Q1).  Per-entry outputs (tau) hold one value per ENTRY, equal for the repeats of an id; a
+ * document's length (tmvb_corpus_info.max_doc_len, the kernel it runs on) is its number of entries.  One quantity is not additive
+ * in a count: CTPF's ELBO holds -lgamma(count + 1) per entry, so splitting an entry shifts it by a constant of the corpus.
+ * tests/test_corpus_presentations_gpu.py holds every model to this. */
 int tmvb_corpus_create(tmvb_ctx* ctx, int64_t M, int64_t V, int64_t U,
                        const int64_t* doc_ptr, const int32_t* terms, const int32_t* counts,
                        const int64_t* rdr_ptr, const int32_t* readers, const int32_t* ratings,

@@ -548,6 +548,15 @@ class CTPF:
     def _phi(gimel, dalet, bet, alef, terms):
         return additive_logistic_cols((digamma(gimel) - np.log(dalet) - np.log(bet))[:, None] + digamma(alef[:, terms]))
 
+    # :274-277 and :259-262 (duplicate ids: last write wins, quirk Q1)
+    def update_he_doc(self, d):
+        readers, ratings = self.docs[d][2], self.docs[d][3]
+        self.he_temp[:, readers] = self.he_temp[:, readers] + (self.xi[:self.K, :] + self.xi[self.K:, :]) * ratings[None, :]
+
+    def update_alef_doc(self, d):
+        terms, counts = self.docs[d][0], self.docs[d][1]
+        self.alef_temp[:, terms] = self.alef_temp[:, terms] + self.phi * counts[None, :]
+
     def train(self, iter=150, tol=1.0, viter=10, vtol=None, checkelbo=1):   # :344-376
         K = self.K
         vtol = 1.0 / K ** 2 if vtol is None else vtol
@@ -568,8 +577,8 @@ class CTPF:
                     self.gimel[d] = self.c + self.phi @ counts + self.xi[:K, :] @ ratings                                # :309
                     if np.linalg.norm(self.gimel[d] - self.gimel_old[d]) < vtol:
                         break
-                self.he_temp[:, readers] = self.he_temp[:, readers] + (self.xi[:K, :] + self.xi[K:, :]) * ratings[None, :]   # :274
-                self.alef_temp[:, terms] = self.alef_temp[:, terms] + self.phi * counts[None, :]                            # :259
+                self.update_he_doc(d)
+                self.update_alef_doc(d)
             # :366-371
             self.he_old = self.he; self.he = self.he_temp; self.he_temp = np.full((K, self.U), self.e)
             self.alef_old = self.alef; self.alef = self.alef_temp; self.alef_temp = np.full((K, self.V), self.a)

@@ -1,7 +1,7 @@
 """
 NEGATIVE CONTROLS of the parity suite (round-4 review: "there is no deliberately wrong variant that must fail").
 
-Eight mutant libraries (three of round 5, two of round 6 for the SURVEY.md section 8(f) rows, two for the trained-state tests, one for the train loop's flags) -- the shipped objects with ONE translation unit recompiled under a -DTMVB_MUTANT_* flag (csrc/tmvb_internal.h, tools/build_mutants.sh) -- each
+Nine mutant libraries (three of round 5, two of round 6 for the SURVEY.md section 8(f) rows, two for the trained-state tests, one for the train loop's flags, one for the inverted index) -- the shipped objects with ONE translation unit recompiled under a -DTMVB_MUTANT_* flag (csrc/tmvb_internal.h, tools/build_mutants.sh) -- each
 wrong in one operator, in a way a careless port of the reference would be:
   mut_lda_eps    epsilon dropped from LDA's update_phi! / update_gamma!            src/LDA.jl:152, :145
   mut_ctpf_bet   `log bet` where update_xi! needs `log vav`                         src/CTPF.jl:336 -- the reference's own OpenCL path has this bug, src/gpuCTPF.jl:624
@@ -11,6 +11,8 @@ wrong in one operator, in a way a careless port of the reference would be:
   mut_lda_stats_eps  LDA's statistics pass without the eps * sum w term of beta_temp   src/LDA.jl:152 (phi and gamma keep their epsilon)
   mut_flda_entropy   fLDA's ELBO without the 0 < tau < 1 guard of H(tau) (0 log 0)     src/fLDA.jl:94-97 (both ELBO forms)
   mut_lda_stale_parts  tmvb_lda_estep leaves the previous iteration's ELBO parts marked valid    csrc/tmvb_lda.hip (logz_valid, pw_diff): a flag of the host state machine, not arithmetic
+  mut_index_repeat   tmvb_build_inv_index drops a posting whose (id, document) equals the previous posting of that id      csrc/tmvb_core.hip (host code): a repeated id inside a document
+                     counts once -- the reference's overwrite, quirk Q1, where the engine accumulates; only an un-condensed corpus (tests/presentations.py, P5) shows it
 For each, a NAMED parity test is run in a fresh pytest process with TMVB_LIB_VARIANT=<mutant> and must FAIL with an assertion of that test (not an import
 error, not a crash), while the shipped library passes the same test in the ordinary suite.  A parity suite that stays green on these would have no teeth.
 """
@@ -45,6 +47,9 @@ MUTANTS = {
     # that sets the state between iterations, or checks every iteration, passes on this mutant
     "mut_lda_stale_parts": ("tmvb_lda.hip", "-DTMVB_MUTANT_LDA_STALE_PARTS=1",
                             ["tests/test_train_loop_gpu.py::test_e_stepwise_iteration_behind_a_collecting_train[lda_k20]"]),
+    # every sorted, condensed corpus of the suite passes on this mutant (no document holds an id twice): the un-condensed presentation must not
+    "mut_index_repeat": ("tmvb_core.hip", "-DTMVB_MUTANT_INDEX_SKIP_REPEAT=1",
+                         ["tests/test_corpus_presentations_gpu.py::test_teacher_forced_fixed_sweeps[lda_k50-P5]"]),
 }
 
 
@@ -97,3 +102,8 @@ def test_the_same_tests_pass_on_the_shipped_library():
                     "tests/test_flda_gpu.py::test_epsilon_keeps_phi_defined_where_a_beta_column_is_zero", "tests/test_fctm_gpu.py::test_teacher_forced_fixed_sweeps[5]"):
         r = _run(test_id, "")
         assert r.returncode == 0, (test_id, r.stdout[-2000:], r.stderr[-1000:])
+    # ... and the index mutant is wrong for repeated ids only: the canonical presentation of the test it must fail passes on it
+    _ensure("mut_index_repeat")
+    test_id = "tests/test_corpus_presentations_gpu.py::test_teacher_forced_fixed_sweeps[lda_k50-P0]"
+    r = _run(test_id, "mut_index_repeat")
+    assert r.returncode == 0, (test_id, r.stdout[-2000:], r.stderr[-1000:])

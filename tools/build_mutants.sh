@@ -9,12 +9,14 @@
 #   topicmodelsvb.jl_amd/libtmvb_hip_mut_lda_stats_eps.so  LDA's statistics pass without eps * sum w      (src/LDA.jl:152)
 #   topicmodelsvb.jl_amd/libtmvb_hip_mut_flda_entropy.so   fLDA's ELBO without the 0 < tau < 1 guard of H(tau) (src/fLDA.jl:94-97)
 #   topicmodelsvb.jl_amd/libtmvb_hip_mut_lda_stale_parts.so  tmvb_lda_estep keeps the previous iteration's ELBO parts marked valid (tests/test_train_loop_gpu.py, scenario E)
+#   topicmodelsvb.jl_amd/libtmvb_hip_mut_index_repeat.so   tmvb_build_inv_index drops the repeated postings of an id inside a document (quirk Q1's overwrite; tests/test_corpus_presentations_gpu.py, P5)
 #   topicmodelsvb.jl_amd/libtmvb_hip_mut_heldout_tail.so   held-out scoring kernel without the last partial 16-byte chunk of a beta row (tests/test_heldout_mutant_gpu.py)
 # Needs the shipped build first (python -c "import __graft_entry__ as g; g.build()").  In parallel, but two builds of one translation unit never in the same batch (they share a temporary): tmvb_ctm.hip has two
-# variants, tmvb_lda.hip three, hence three batches, the third holding mut_lda_stale_parts alone.  About 4 minutes for the first two batches plus one more build of tmvb_lda.hip.
+# variants, tmvb_lda.hip three (tmvb_core.hip one: mut_index_repeat), hence three batches, the third holding mut_lda_stale_parts alone.  About 4 minutes for the first two batches plus one more build of tmvb_lda.hip.
 cd "$(dirname "$0")/.." || exit 1
 tools/build_variant.sh mut_lda_eps tmvb_lda.hip -DTMVB_MUTANT_LDA_NO_EPS=1 &
 tools/build_variant.sh mut_ctpf_bet tmvb_ctpf.hip -DTMVB_MUTANT_CTPF_LOG_BET=1 &
+tools/build_variant.sh mut_index_repeat tmvb_core.hip -DTMVB_MUTANT_INDEX_SKIP_REPEAT=1 &
 tools/build_variant.sh mut_ctm_mu tmvb_ctm.hip -DTMVB_MUTANT_CTM_SIGMA_NEW_MU=1 &
 tools/build_variant.sh mut_flda_eps tmvb_flda.hip -DTMVB_MUTANT_FLDA_NO_EPS=1 &
 wait

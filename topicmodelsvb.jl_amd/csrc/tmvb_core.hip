@@ -356,9 +356,18 @@ int tmvb_build_inv_index(tmvb_ctx* ctx, int64_t M, int64_t n_ids, const int64_t*
     auto count_range = [&](int t) {
         std::vector<int32_t>& H = hist[(size_t)t];
         H.assign((size_t)n_ids, 0);
+#ifdef TMVB_MUTANT_INDEX_SKIP_REPEAT
+        std::vector<int64_t> last((size_t)n_ids, -1);                  // a document lies in one range: its repeats of an id never cross ranges
+#endif
         for (int64_t d = dcut[(size_t)t]; d < dcut[(size_t)t + 1]; ++d)
             if (in_piece(d))
-                for (int64_t q = h_ptr[d]; q < h_ptr[d + 1]; ++q) H[(size_t)h_ids[q]]++;
+                for (int64_t q = h_ptr[d]; q < h_ptr[d + 1]; ++q) {
+#ifdef TMVB_MUTANT_INDEX_SKIP_REPEAT
+                    if (last[(size_t)h_ids[q]] == d) continue;
+                    last[(size_t)h_ids[q]] = d;
+#endif
+                    H[(size_t)h_ids[q]]++;
+                }
     };
     auto run_ranges = [&](auto&& fn) {
         std::vector<std::thread> workers;
@@ -387,9 +396,18 @@ int tmvb_build_inv_index(tmvb_ctx* ctx, int64_t M, int64_t n_ids, const int64_t*
         }
         auto scatter_range = [&](int t) {
             std::vector<int64_t>& cu = cur[(size_t)t];
+#ifdef TMVB_MUTANT_INDEX_SKIP_REPEAT
+            std::vector<int64_t> last((size_t)n_ids, -1);
+#endif
             for (int64_t d = dcut[(size_t)t]; d < dcut[(size_t)t + 1]; ++d) {
                 if (!in_piece(d)) continue;
                 for (int64_t q = h_ptr[d]; q < h_ptr[d + 1]; ++q) {
+#ifdef TMVB_MUTANT_INDEX_SKIP_REPEAT
+                    // the reference's overwrite (quirk Q1) instead of the engine's accumulation: a posting whose (id, document) equals the previous posting
+                    // of that id is dropped (the entry keeps pointing at the posting that stays)
+                    if (last[(size_t)h_ids[q]] == d) { if (!doc_piece) inv[q] = (int32_t)(cu[(size_t)h_ids[q]] - 1); continue; }
+                    last[(size_t)h_ids[q]] = d;
+#endif
                     const int64_t w = cu[(size_t)h_ids[q]]++;
                     doc[w] = (int32_t)d; pos[w] = (int32_t)q; val[w] = (float)h_vals[q];
                     if (!doc_piece) inv[q] = (int32_t)w;

@@ -166,6 +166,9 @@ int tmvb_corpus_reader_index(tmvb_corpus* c);
 //                                   tests/test_heldout_mutant_gpu.py
 //   TMVB_MUTANT_LDA_STALE_PARTS     tmvb_lda_estep does not clear logz_valid / pw_diff at its start and keeps logz_valid when it does not collect: a stepwise
 //                                   iteration behind a collecting train! evaluates the ELBO from the previous iteration's parts (tests/test_train_loop_gpu.py, scenario E)
+//   TMVB_MUTANT_INDEX_SKIP_REPEAT   tmvb_build_inv_index (tmvb_core.hip, host code) drops a posting whose (id, document) equals the previous posting of that id: a repeated id
+//                                   inside a document counts once, the reference's overwrite (quirk Q1) where the engine accumulates; only an un-condensed corpus shows it
+//                                   (tests/test_corpus_presentations_gpu.py, presentation P5)
 #ifdef TMVB_MUTANT_FLDA_H_NO_GUARD
 #define TMVB_FLDA_H_GUARD(cond) true
 #else
