@@ -563,6 +563,47 @@ int tmvb_heldout_loglik(tmvb_ctx* ctx, int32_t K, int64_t V, int64_t M, const do
                         const int32_t* terms, const int32_t* counts, double laplace_smooth, double* ll, int64_t* tokens,
                         int64_t* zero_prob_tokens, float* ms_kernel);
 
+/* ============================== topic coherence: co-document counts, UMass, NPMI ==============================
+ * Whether the top words of a topic occur together in documents (the reference has no such function).  Inputs: a reference corpus as the
+ * host CSR of tmvb_corpus_create (doc_ptr[M+1], terms[nnz], counts[nnz]) and top[K][N], row-major: for each topic its N top term ids,
+ * 0-based, in descending order of probability.  Only presence matters: document d CONTAINS term w iff any of its entries has term w; ids
+ * inside a document need be neither sorted nor unique, a repeated id counts the document once, counts are validated (>= 1) and otherwise
+ * ignored.
+ *
+ * tmvb_corpus_codocfreq: codf[K][N][N] (int64, row-major), codf[k][i][j] = number of documents that contain both top[k][i] and
+ * top[k][j]; symmetric; the diagonal is the document frequency df[k][i].  These integers are the whole device result, exact and the
+ * same bits on every call.  They are ADDITIVE over document shards: the codf of documents [0, m) plus the codf of [m, M) is the codf of
+ * the corpus, so a multi-rank host calls this on its shard, sums the integers by any means and scores once.
+ * Device path: the distinct ids of top (T <= K N) get slots; a bit matrix bits[T][W], W = ceil(M / 64) 64-bit words (bit d of row s set
+ * iff document d contains the term of slot s), is built with one atomic OR per selected CSR entry; the pair pass takes
+ * popcount(row_i & row_j) over chunks of TMVB_CODF_CHUNK_DOCS documents.  If T W 8 bytes exceed max_bitset_bytes (0 = the library's
+ * default, TMVB_CODF_DEFAULT_BITSET_BYTES = 1 GiB) the topics are processed in batches of consecutive topics whose distinct ids fit, each
+ * with its own build pass over the CSR; a single topic that does not fit (N W 8 bytes) is TMVB_EINVAL with the needed bytes in the
+ * message.  (The budget counts T W 8; the allocation rounds W up to an even number of words so that rows are 16-byte aligned.)
+ * info (or NULL): n_slots = T, n_batches, ms_bitset / ms_pairs = device time of the two kernels summed over the batches (HIP events
+ * around the kernels only).
+ * Errors, judged before the device is touched: K outside [1, 1024], N outside [2, 64] or N > V, M <= 0, V <= 0, NULL argument,
+ * 2^31 - 1 or more entries, max_bitset_bytes < 0 -> TMVB_EINVAL; doc_ptr not non-decreasing from 0, a term outside [0, V), a count < 1,
+ * an id of top outside [0, V), an id repeated inside one row of top -> TMVB_ESHAPE; then ctx == NULL without a visible device ->
+ * TMVB_ENODEVICE (there is no CPU path).
+ *
+ * tmvb_coherence_from_counts: host only, touches no device; fp64 arithmetic on the integers.  Per topic, over the pairs i > j (j is the
+ * higher-ranked word), D_ij = codf[k][i][j], D_i = codf[k][i][i], M = number of documents behind the counts:
+ *   umass[k]  (Mimno et al. 2011, as a mean) mean over the DEFINED pairs of log((D_ij + 1) / D_j); a pair with D_j = 0 is undefined,
+ *             skipped and counted in undefined_pairs[k]; NaN if no pair is defined;
+ *   npmi[k]   (document as the window; Lau et al. 2014) mean over all pairs of: -1 if D_ij = 0; 0 if D_ij = M; otherwise
+ *             log(D_ij M / (D_i D_j)) / -log(D_ij / M).
+ * No epsilon is added anywhere; the sums are compensated (Neumaier).  Errors: K outside [1, 1024], N outside [2, 64], M <= 0, NULL
+ * argument -> TMVB_EINVAL; codf not symmetric, a negative entry, an off-diagonal entry above either of its diagonal entries, a diagonal
+ * entry above M -> TMVB_ESHAPE. */
+#define TMVB_CODF_CHUNK_DOCS 4096                           /* documents per workgroup of the pair pass: 64 words of a bit-matrix row */
+#define TMVB_CODF_DEFAULT_BITSET_BYTES 1073741824           /* 1 GiB */
+typedef struct { int64_t n_slots; int32_t n_batches; float ms_bitset, ms_pairs; } tmvb_codf_info_t;
+int tmvb_corpus_codocfreq(tmvb_ctx* ctx, int64_t M, int64_t V, const int64_t* doc_ptr, const int32_t* terms, const int32_t* counts,
+                          int32_t K, int32_t N, const int32_t* top, int64_t max_bitset_bytes, int64_t* codf, tmvb_codf_info_t* info);
+int tmvb_coherence_from_counts(int32_t K, int32_t N, int64_t M, const int64_t* codf, double* umass, double* npmi,
+                               int32_t* undefined_pairs);
+
 #ifdef __cplusplus
 }
 #endif

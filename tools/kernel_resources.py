@@ -36,6 +36,8 @@ BENCHED = {
     "ctpf_mstep_kernel": 0,
     # held-out evaluation (tools/heldout_bench.py): the scoring kernel's two workgroup sizes and the split's draw kernel
     "heldout_loglik_kernel<64>": 0, "heldout_loglik_kernel<256>": 0, "split_draw_kernel": 0,
+    # topic coherence (tools/coherence_bench.py): the bit-matrix build and the pair pass of the co-document counts
+    "codf_bitset_kernel": 0, "codf_pairs_kernel": 0,
 }
 
 

@@ -16,10 +16,12 @@ from .flda import fLDA, check_model_flda, gpufLDA, gpu_train_flda, predict_flda
 from .fctm import fCTM, check_model_fctm, gpufCTM, gpu_train_fctm, predict_fctm
 from .gencorp import gencorp, gencorp_raw, gendoc
 from .heldout import HeldoutResult, heldout_loglik, heldout_loglik_raw, perplexity, split_corpus, split_corpus_raw
+from .coherence import CoherenceResult, coherence, coherence_from_counts, coherence_from_counts_raw, codocfreq_raw
 
 __all__ = ["CorpusError", "DocumentError", "EngineError", "TopicModelError", "build", "exported_symbols", "lib", "LIB_PATH",
            "Corpus", "Document", "PackedCorpus", "check_corp", "check_doc", "dirichlet_rows", "readcorp", "readcorp_packed", "writecorp",
            "syn_citeu", "syn_nsf", "synthetic_lda_corpus", "LDA", "DeviceContext", "DeviceCorpus", "check_model", "gpuLDA",
            "gpu_train", "predict", "topicdist", "predict_ctm", "topicdist_ctm", "CTM", "check_model_ctm", "gpuCTM", "gpu_train_ctm", "CTPF", "check_model_ctpf", "gpuCTPF", "gpu_train_ctpf", "Communicator", "rccl_version", "fLDA", "check_model_flda", "gpufLDA", "gpu_train_flda", "fCTM", "check_model_fctm", "gpufCTM", "gpu_train_fctm", "predict_flda", "predict_fctm", "topicdist_ctpf",
            "gencorp", "gencorp_raw", "gendoc",
-           "HeldoutResult", "heldout_loglik", "heldout_loglik_raw", "perplexity", "split_corpus", "split_corpus_raw"]
+           "HeldoutResult", "heldout_loglik", "heldout_loglik_raw", "perplexity", "split_corpus", "split_corpus_raw",
+           "CoherenceResult", "coherence", "coherence_from_counts", "coherence_from_counts_raw", "codocfreq_raw"]

@@ -168,6 +168,39 @@ static __global__ __launch_bounds__(WG) void heldout_loglik_kernel(int K, int KP
 }
 
 // ------------------------------------------------------------------------------------------------------------------ host
+// shared with tmvb_coherence.hip (declared in tmvb_internal.h)
+// the check_doc / check_corp rules of tmvb_corpus_create on a host CSR; doc_tokens_limit: a document must stay below 2^31 tokens
+int tmvb_check_host_csr(const char* fn, int64_t M, int64_t V, const int64_t* doc_ptr, const int32_t* terms, const int32_t* counts, bool doc_tokens_limit)
+{
+    TMVB_REQUIRE(M > 0, TMVB_EINVAL, "%s: M must be a positive integer", fn);
+    TMVB_REQUIRE(V > 0, TMVB_EINVAL, "%s: V must be a positive integer", fn);
+    TMVB_REQUIRE(M < (int64_t)INT32_MAX, TMVB_EINVAL, "%s: M = %lld above 2^31 - 2 documents per call", fn, (long long)M);
+    TMVB_REQUIRE(doc_ptr && terms && counts, TMVB_EINVAL, "%s: NULL argument", fn);
+    TMVB_REQUIRE(doc_ptr[0] == 0, TMVB_ESHAPE, "%s: doc_ptr must start at 0", fn);
+    for (int64_t d = 0; d < M; d++) TMVB_REQUIRE(doc_ptr[d + 1] >= doc_ptr[d], TMVB_ESHAPE, "%s: doc_ptr decreases at document %lld", fn, (long long)d);
+    TMVB_REQUIRE(doc_ptr[M] < HO_MAX_NNZ, TMVB_EINVAL, "%s: %lld entries in one call (limit 2^31 - 2); split the corpus by documents", fn, (long long)doc_ptr[M]);
+    for (int64_t d = 0; d < M; d++) {
+        int64_t C = 0;
+        for (int64_t j = doc_ptr[d]; j < doc_ptr[d + 1]; j++) {
+            TMVB_REQUIRE(terms[j] >= 0 && terms[j] < V, TMVB_ESHAPE, "%s: document %lld holds term %d outside [0, %lld)", fn, (long long)d, terms[j], (long long)V);
+            TMVB_REQUIRE(counts[j] >= 1, TMVB_ESHAPE, "%s: document %lld holds a count below 1 (all counts must be positive integers)", fn, (long long)d);
+            C += counts[j];
+        }
+        if (doc_tokens_limit)
+            TMVB_REQUIRE(C < ((int64_t)1 << 31), TMVB_EINVAL, "%s: document %lld has %lld tokens (limit 2^31 - 1)", fn, (long long)d, (long long)C);
+    }
+    return TMVB_OK;
+}
+
+// arguments are judged first, so a host without a device still gets the argument's own error; then: no device, no result
+int tmvb_check_ctx_or_device(const char* fn, tmvb_ctx* ctx)
+{
+    if (ctx) return TMVB_OK;
+    TMVB_REQUIRE(tmvb_device_count() > 0, TMVB_ENODEVICE, "%s: no HIP device visible (the HIP engine has no CPU fallback)", fn);
+    TMVB_REQUIRE(false, TMVB_EINVAL, "%s: ctx is NULL", fn);
+    return TMVB_OK;
+}
+
 namespace {
 struct ho_pool {                    // device allocations and events of one call
     std::vector<void*> ptrs;
@@ -203,38 +236,6 @@ int ho_host(T** p, size_t n)
 {
     *p = (T*)malloc(std::max<size_t>(n, 1) * sizeof(T));
     if (!*p) { tmvb_set_error("heldout: out of host memory"); return TMVB_ENOMEM; }
-    return TMVB_OK;
-}
-
-// the check_doc / check_corp rules of tmvb_corpus_create on a host CSR; doc_tokens_limit: a document must stay below 2^31 tokens
-int ho_check_csr(const char* fn, int64_t M, int64_t V, const int64_t* doc_ptr, const int32_t* terms, const int32_t* counts, bool doc_tokens_limit)
-{
-    TMVB_REQUIRE(M > 0, TMVB_EINVAL, "%s: M must be a positive integer", fn);
-    TMVB_REQUIRE(V > 0, TMVB_EINVAL, "%s: V must be a positive integer", fn);
-    TMVB_REQUIRE(M < (int64_t)INT32_MAX, TMVB_EINVAL, "%s: M = %lld above 2^31 - 2 documents per call", fn, (long long)M);
-    TMVB_REQUIRE(doc_ptr && terms && counts, TMVB_EINVAL, "%s: NULL argument", fn);
-    TMVB_REQUIRE(doc_ptr[0] == 0, TMVB_ESHAPE, "%s: doc_ptr must start at 0", fn);
-    for (int64_t d = 0; d < M; d++) TMVB_REQUIRE(doc_ptr[d + 1] >= doc_ptr[d], TMVB_ESHAPE, "%s: doc_ptr decreases at document %lld", fn, (long long)d);
-    TMVB_REQUIRE(doc_ptr[M] < HO_MAX_NNZ, TMVB_EINVAL, "%s: %lld entries in one call (limit 2^31 - 2); split the corpus by documents", fn, (long long)doc_ptr[M]);
-    for (int64_t d = 0; d < M; d++) {
-        int64_t C = 0;
-        for (int64_t j = doc_ptr[d]; j < doc_ptr[d + 1]; j++) {
-            TMVB_REQUIRE(terms[j] >= 0 && terms[j] < V, TMVB_ESHAPE, "%s: document %lld holds term %d outside [0, %lld)", fn, (long long)d, terms[j], (long long)V);
-            TMVB_REQUIRE(counts[j] >= 1, TMVB_ESHAPE, "%s: document %lld holds a count below 1 (all counts must be positive integers)", fn, (long long)d);
-            C += counts[j];
-        }
-        if (doc_tokens_limit)
-            TMVB_REQUIRE(C < ((int64_t)1 << 31), TMVB_EINVAL, "%s: document %lld has %lld tokens (limit 2^31 - 1)", fn, (long long)d, (long long)C);
-    }
-    return TMVB_OK;
-}
-
-// arguments are judged first, so a host without a device still gets the argument's own error; then: no device, no result
-int ho_check_ctx(const char* fn, tmvb_ctx* ctx)
-{
-    if (ctx) return TMVB_OK;
-    TMVB_REQUIRE(tmvb_device_count() > 0, TMVB_ENODEVICE, "%s: no HIP device visible (the HIP engine has no CPU fallback)", fn);
-    TMVB_REQUIRE(false, TMVB_EINVAL, "%s: ctx is NULL", fn);
     return TMVB_OK;
 }
 
@@ -412,9 +413,9 @@ extern "C" int tmvb_corpus_split(tmvb_ctx* ctx, int64_t M, int64_t V, const int6
     memset(out, 0, sizeof(*out));
     TMVB_REQUIRE(std::isfinite(frac) && frac >= 0.0 && frac <= 1.0, TMVB_EINVAL, "tmvb_corpus_split: frac must lie in [0, 1]");
     TMVB_REQUIRE(doc_offset >= 0, TMVB_EINVAL, "tmvb_corpus_split: doc_offset must be nonnegative");
-    int rc = ho_check_csr("tmvb_corpus_split", M, V, doc_ptr, terms, counts, true);
+    int rc = tmvb_check_host_csr("tmvb_corpus_split", M, V, doc_ptr, terms, counts, true);
     if (rc != TMVB_OK) return rc;
-    if ((rc = ho_check_ctx("tmvb_corpus_split", ctx)) != TMVB_OK) return rc;
+    if ((rc = tmvb_check_ctx_or_device("tmvb_corpus_split", ctx)) != TMVB_OK) return rc;
     const uint64_t thr = (uint64_t)std::floor(frac * 4294967296.0);
     return ho_split_run(ctx, M, doc_ptr, terms, counts, thr, (uint64_t)seed, doc_offset, out);
 }
@@ -427,7 +428,7 @@ extern "C" int tmvb_heldout_loglik(tmvb_ctx* ctx, int32_t K, int64_t V, int64_t 
     TMVB_REQUIRE(K >= 1 && K <= HO_MAX_K, TMVB_EINVAL, "%s: K = %d outside [1, %d]", fn, K, HO_MAX_K);
     TMVB_REQUIRE(laplace_smooth >= 0.0 && std::isfinite(laplace_smooth), TMVB_EINVAL, "laplace_smooth parameter must be nonnegative.");
     TMVB_REQUIRE(theta && beta && ll && tokens && zero_prob_tokens, TMVB_EINVAL, "%s: NULL argument", fn);
-    int rc = ho_check_csr(fn, M, V, doc_ptr, terms, counts, false);
+    int rc = tmvb_check_host_csr(fn, M, V, doc_ptr, terms, counts, false);
     if (rc != TMVB_OK) return rc;
     // isstochastic(beta, dims=2) (src/modelutils.jl:56) with gencorp's tolerance for the Float32-derived beta of a device model
     std::vector<double> rows((size_t)K, 0.0);
@@ -450,6 +451,6 @@ extern "C" int tmvb_heldout_loglik(tmvb_ctx* ctx, int32_t K, int64_t V, int64_t 
         }
         TMVB_REQUIRE(good && std::fabs(s - 1.0) <= 1e-6, TMVB_ESHAPE, "%s: \xce\xb8 not a probability vector (document %lld)", fn, (long long)d);
     }
-    if ((rc = ho_check_ctx(fn, ctx)) != TMVB_OK) return rc;
+    if ((rc = tmvb_check_ctx_or_device(fn, ctx)) != TMVB_OK) return rc;
     return ho_loglik_run(ctx, K, V, M, theta, beta, doc_ptr, terms, counts, laplace_smooth, ll, tokens, zero_prob_tokens, ms_kernel);
 }

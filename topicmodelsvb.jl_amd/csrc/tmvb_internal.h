@@ -150,6 +150,10 @@ int tmvb_corpus_term_index(tmvb_corpus* c);
 int tmvb_comm_allreduce_group(tmvb_comm* const* comms, void* const* dev_ptrs, const int64_t* counts, int n, int32_t dtype);
 int tmvb_comm_allreduce_on(tmvb_comm* c, void* dev_ptr, int64_t count, int32_t dtype, hipStream_t on);
 int tmvb_corpus_reader_index(tmvb_corpus* c);
+// Host CSR arguments of the entry points that take a corpus without a handle (tmvb_heldout.hip; also tmvb_coherence.hip): the check_doc /
+// check_corp rules of tmvb_corpus_create, and "arguments first, then: no device, no result" for a NULL context.
+int tmvb_check_host_csr(const char* fn, int64_t M, int64_t V, const int64_t* doc_ptr, const int32_t* terms, const int32_t* counts, bool doc_tokens_limit);
+int tmvb_check_ctx_or_device(const char* fn, tmvb_ctx* ctx);
 
 // EPSILON of the reference (src/utils.jl:3) = 2^-99, exactly representable in fp32.
 // MUTANTS (tests/test_mutants_gpu.py; never defined in a shipped build): deliberately wrong variants of seven operators, one -D flag each, built as
@@ -169,6 +173,8 @@ int tmvb_corpus_reader_index(tmvb_corpus* c);
 //   TMVB_MUTANT_INDEX_SKIP_REPEAT   tmvb_build_inv_index (tmvb_core.hip, host code) drops a posting whose (id, document) equals the previous posting of that id: a repeated id
 //                                   inside a document counts once, the reference's overwrite (quirk Q1) where the engine accumulates; only an un-condensed corpus shows it
 //                                   (tests/test_corpus_presentations_gpu.py, presentation P5)
+//   TMVB_MUTANT_CODF_DROP_TAIL      the pair kernel of the co-document counts (tmvb_coherence.hip) skips the last, partial 64-document word of the bit matrix
+//                                   (M not a multiple of 64); tests/test_coherence_mutant_gpu.py
 #ifdef TMVB_MUTANT_FLDA_H_NO_GUARD
 #define TMVB_FLDA_H_GUARD(cond) true
 #else

@@ -964,3 +964,53 @@ function perplexity(model::Union{DirichletModels, LogisticNormalModels}, corp::C
 	observed, heldout = split_corp(corp; frac=frac, seed=seed)
 	return heldout_loglik(model, observed, heldout; kwargs...).perplexity
 end
+
+# ---------------------------------------------------------------------------------------------- topic coherence
+# Whether the top words of a topic occur together in documents (the reference has no such function): tmvb_corpus_codocfreq counts, for
+# every topic, the documents of `corp` that contain both words of every pair of its topn top words (a bit matrix over the corpus on the
+# device, AND / popcount over pairs; exact integers, additive over document shards), tmvb_coherence_from_counts turns the counts into UMass
+# (Mimno et al. 2011, as a mean over the defined pairs) and NPMI with the document as the window (Lau et al. 2014) on the host.
+
+"tmvb_codf_info_t (include/tmvb.h), field for field."
+mutable struct TmvbCodfInfo
+	n_slots::Int64; n_batches::Int32
+	ms_bitset::Float32; ms_pairs::Float32
+	TmvbCodfInfo() = new(0, 0, 0f0, 0f0)
+end
+
+"""
+(codf, df, umass, npmi, undefined_pairs, diversity) of the first `topn` words of every topic of `model` against `corp`:
+codf[i,j,k] = documents that contain both the i-th and the j-th top word of topic k, df[i,k] its diagonal; umass[k] is NaN where no pair is
+defined; diversity = distinct top words / (K topn).
+"""
+function coherence(model::TopicModel, corp::Corpus; topn::Integer=10, device::Integer=0, max_bitset_bytes::Integer=0)
+	(2 <= topn <= 64)					|| throw(ArgumentError("topn must be an integer in [2, 64]."))
+	M, V, U = size(corp)
+	(V == model.V)						|| throw(CorpusError("coherence corpus and model must have identical vocabularies."))
+	(topn <= V)							|| throw(ArgumentError("topn = $topn above the vocabulary size."))
+	K = model.K
+	top = Matrix{Int32}(undef, topn, K)									# column k = row k of the C array top[K][N]
+	for k in 1:K
+		top[:,k] = Int32.(model.topics[k][1:topn] .- 1)
+	end
+	doc_ptr, terms, counts = corp_csr(corp)
+	codf = zeros(Int64, topn, topn, K)									# column-major (j, i, k) = C's codf[k][i][j]; symmetric in (i, j)
+	info = TmvbCodfInfo()
+	ctx = tmvb_context(device)
+	GC.@preserve info doc_ptr terms counts top codf begin
+		rc = ccall((:tmvb_corpus_codocfreq, LIBTMVB), Cint,
+			(Ptr{Cvoid}, Int64, Int64, Ptr{Int64}, Ptr{Int32}, Ptr{Int32}, Int32, Int32, Ptr{Int32}, Int64, Ptr{Int64}, Ptr{Cvoid}),
+			ctx, M, V, doc_ptr, terms, counts, K, topn, top, max_bitset_bytes, codf, pointer_from_objref(info))
+		tmvb_destroy_context(ctx)
+		tmvb_check(rc)
+	end
+	umass = zeros(Float64, K); npmi = zeros(Float64, K); undefined_pairs = zeros(Int32, K)
+	GC.@preserve codf umass npmi undefined_pairs begin
+		tmvb_check(ccall((:tmvb_coherence_from_counts, LIBTMVB), Cint,
+			(Int32, Int32, Int64, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}),
+			K, topn, M, codf, umass, npmi, undefined_pairs))
+	end
+	df = [codf[i,i,k] for i in 1:topn, k in 1:K]
+	return (codf=codf, df=df, umass=umass, npmi=npmi, undefined_pairs=Int.(undefined_pairs),
+			diversity=length(unique(top)) / (K * topn), ms=(bitset=info.ms_bitset, pairs=info.ms_pairs))
+end
