@@ -604,6 +604,43 @@ int tmvb_corpus_codocfreq(tmvb_ctx* ctx, int64_t M, int64_t V, const int64_t* do
 int tmvb_coherence_from_counts(int32_t K, int32_t N, int64_t M, const int64_t* codf, double* umass, double* npmi,
                                int32_t* undefined_pairs);
 
+/* ============================== nearest documents in topic space: fused scores and top-n ==============================
+ * Which rows of a database of topic proportions are closest to each query row (the reference stops at topicdist(model, d), one document's
+ * proportions).  xd is the database, column-major K x Md fp64 on the HOST (row e is xd[K e .. K e + K), as theta in tmvb_heldout_loglik);
+ * xq the queries, K x Mq, or NULL: the queries are then database rows [q0, q0 + Mq) and each excludes itself.
+ *
+ * Features: every row is transformed in fp64 and each value rounded ONCE to fp32.  TMVB_NB_DOT: the row as given.  TMVB_NB_HELLINGER: the
+ * rows are distributions, feature = sqrt(x); the score is the Bhattacharyya coefficient = 1 - H^2 (H the Hellinger distance).
+ * TMVB_NB_COSINE: rows nonnegative and not all zero, feature = x / ||x||_2 with the fp64 norm.  Rows are padded with zeros to kp (K rounded
+ * up to a multiple of 4: rows are 16-byte aligned and the MFMA's k-step of 2 divides them).
+ * Score: s(q, e) is the fp32 fmaf chain over k = 0 .. K - 1 in ascending order starting from 0 -- what v_mfma_f32_32x32x2_f32 computes when
+ * the K loop feeds its accumulator; padding contributes exactly nothing, so the score of a pair does not depend on tiling.
+ * Order: for each query the n best database rows under the TOTAL order (score descending, index ascending on equal scores), listed in that
+ * order in idx[Mq][n] (0-based) and score[Mq][n]; count[q] = min(n, number of candidates); slots beyond count[q] hold idx = -1 and
+ * score = -inf.  With xq == NULL row q0 + q is no candidate of query q; with xq given q0 must be 0 and nothing is excluded.
+ * Purity: the result is a pure function of the inputs -- independent of `splits` (0 = the library's choice: as many database splits as
+ * fill the device when there are few query tiles, 1 when there are many; > 0 forces that many, for tests), of tile sizes and of the order
+ * in which workgroups finish; two calls give the same bits; queries [q0, q0 + m) of a large call equal the call (Mq = m, q0), which is how
+ * a multi-rank host shards the queries.  No atomics on global memory.
+ * Device path: a feature kernel (fp64 in, fp32 [M][kp] out); a scan kernel -- a workgroup owns 128 queries and one database split (a run
+ * of whole tiles of TMVB_NB_TILE_DB rows), stages both operands through LDS, accumulates on the f32 MFMA and, instead of storing, tests every
+ * accumulator entry against its query's n-th best so far (kept in LDS) and inserts the survivors --; a merge kernel takes the splits x n
+ * partial lists of a query to the final n under the same order (skipped with one split).
+ * info (or NULL): splits = database splits used (at most the number of database tiles), kp, ms_prep / ms_scan / ms_merge = device time of
+ * the feature, scan and merge kernels (HIP events around the kernels only).
+ * Errors, judged before the device is touched: K outside [1, 1024], n outside [1, TMVB_NB_TOPN_MAX], Md <= 0, Mq <= 0, Md >= 2^31,
+ * splits < 0 or > Md, q0 < 0, q0 + Mq > Md with xq == NULL, q0 != 0 with xq given, an unknown metric, a NULL argument -> TMVB_EINVAL; a
+ * non-finite entry, HELLINGER: a negative entry or a column sum further than 1e-6 from 1 (the rule of tmvb_heldout_loglik's theta), COSINE:
+ * a negative entry or an all-zero row -> TMVB_ESHAPE; then ctx == NULL without a visible device -> TMVB_ENODEVICE (there is no CPU path). */
+#define TMVB_NB_DOT 0
+#define TMVB_NB_HELLINGER 1
+#define TMVB_NB_COSINE 2
+#define TMVB_NB_TOPN_MAX 64
+#define TMVB_NB_TILE_DB 128                                 /* database rows per tile of the scan kernel */
+typedef struct { int32_t splits, kp; float ms_prep, ms_scan, ms_merge; } tmvb_neighbors_info_t;
+int tmvb_topic_neighbors(tmvb_ctx* ctx, int32_t K, int32_t metric, int64_t Md, const double* xd, int64_t Mq, const double* xq, int64_t q0,
+                         int32_t n, int32_t splits, int32_t* idx, float* score, int32_t* count, tmvb_neighbors_info_t* info);
+
 #ifdef __cplusplus
 }
 #endif

@@ -38,6 +38,8 @@ BENCHED = {
     "heldout_loglik_kernel<64>": 0, "heldout_loglik_kernel<256>": 0, "split_draw_kernel": 0,
     # topic coherence (tools/coherence_bench.py): the bit-matrix build and the pair pass of the co-document counts
     "codf_bitset_kernel": 0, "codf_pairs_kernel": 0,
+    # nearest documents in topic space (tools/neighbors_bench.py): features, the fused MFMA scan / top-n, the merge of the splits' lists
+    "nb_feature_kernel": 0, "nb_scan_kernel": 0, "nb_merge_kernel": 0,
 }
 
 

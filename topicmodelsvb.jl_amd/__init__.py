@@ -17,6 +17,7 @@ from .fctm import fCTM, check_model_fctm, gpufCTM, gpu_train_fctm, predict_fctm
 from .gencorp import gencorp, gencorp_raw, gendoc
 from .heldout import HeldoutResult, heldout_loglik, heldout_loglik_raw, perplexity, split_corpus, split_corpus_raw
 from .coherence import CoherenceResult, coherence, coherence_from_counts, coherence_from_counts_raw, codocfreq_raw
+from .neighbors import NeighborsResult, docsim, neighbors_raw, topic_proportions
 
 __all__ = ["CorpusError", "DocumentError", "EngineError", "TopicModelError", "build", "exported_symbols", "lib", "LIB_PATH",
            "Corpus", "Document", "PackedCorpus", "check_corp", "check_doc", "dirichlet_rows", "readcorp", "readcorp_packed", "writecorp",
@@ -24,4 +25,5 @@ __all__ = ["CorpusError", "DocumentError", "EngineError", "TopicModelError", "bu
            "gpu_train", "predict", "topicdist", "predict_ctm", "topicdist_ctm", "CTM", "check_model_ctm", "gpuCTM", "gpu_train_ctm", "CTPF", "check_model_ctpf", "gpuCTPF", "gpu_train_ctpf", "Communicator", "rccl_version", "fLDA", "check_model_flda", "gpufLDA", "gpu_train_flda", "fCTM", "check_model_fctm", "gpufCTM", "gpu_train_fctm", "predict_flda", "predict_fctm", "topicdist_ctpf",
            "gencorp", "gencorp_raw", "gendoc",
            "HeldoutResult", "heldout_loglik", "heldout_loglik_raw", "perplexity", "split_corpus", "split_corpus_raw",
-           "CoherenceResult", "coherence", "coherence_from_counts", "coherence_from_counts_raw", "codocfreq_raw"]
+           "CoherenceResult", "coherence", "coherence_from_counts", "coherence_from_counts_raw", "codocfreq_raw",
+           "NeighborsResult", "docsim", "neighbors_raw", "topic_proportions"]

@@ -1014,3 +1014,56 @@ function coherence(model::TopicModel, corp::Corpus; topn::Integer=10, device::In
 	return (codf=codf, df=df, umass=umass, npmi=npmi, undefined_pairs=Int.(undefined_pairs),
 			diversity=length(unique(top)) / (K * topn), ms=(bitset=info.ms_bitset, pairs=info.ms_pairs))
 end
+
+# ---------------------------------------------------------------------------------------------- nearest documents in topic space
+# Which documents are about the same things as this one (the reference stops at topicdist(model, d)): tmvb_topic_neighbors scores every query
+# against every document of the model on the device (fp32 features, the f32 MFMA = the ascending fmaf chain) and keeps, per query, the topn
+# best under the total order (score descending, index ascending); the score matrix never exists.
+
+"tmvb_neighbors_info_t (include/tmvb.h), field for field."
+mutable struct TmvbNeighborsInfo
+	splits::Int32; kp::Int32
+	ms_prep::Float32; ms_scan::Float32; ms_merge::Float32
+	TmvbNeighborsInfo() = new(0, 0, 0f0, 0f0, 0f0)
+end
+
+"K x M topic proportions: column d is topicdist(model, d)."
+topic_proportions(model::DirichletModels) = hcat([g / sum(g) for g in model.gamma]...)
+topic_proportions(model::LogisticNormalModels) = hcat([additive_logistic(model.lambda[d] + 0.5 * model.vsq[d]) for d in 1:length(model.lambda)]...)
+topic_proportions(model::hipCTPF) = hcat([g / sum(g) for g in model.gimel]...)
+
+const NB_METRICS = Dict(:dot => 0, :hellinger => 1, :cosine => 2)
+
+"""
+(idx, score, distance, count) of the `topn` documents of `model` nearest to each document of `docs` (1-based like topicdist; a contiguous
+range, by default every document), the document itself excluded -- or, with `queries` (another model over other documents, what predict
+returned), nearest to each of ITS documents, nothing excluded.  idx[j, q] is 1-based, 0 past count[q]; metric = :hellinger (score =
+Bhattacharyya coefficient, distance = sqrt(max(0, 1 - score))), :cosine (distance = 1 - score) or :dot (distance = nothing).
+"""
+function docsim(model::TopicModel; docs::AbstractUnitRange{<:Integer}=1:0, topn::Integer=10, metric::Symbol=:hellinger, queries=nothing, device::Integer=0)
+	haskey(NB_METRICS, metric)			|| throw(ArgumentError("metric must be :dot, :hellinger or :cosine."))
+	(1 <= topn <= 64)					|| throw(ArgumentError("topn must be an integer in [1, 64]."))
+	xd = Matrix{Float64}(topic_proportions(model))
+	K, Md = size(xd)
+	src = queries === nothing ? xd : Matrix{Float64}(topic_proportions(queries))
+	(size(src, 1) == K)					|| throw(TopicModelError("queries and model must have the same number of topics."))
+	docs = isempty(docs) ? (1:size(src, 2)) : docs
+	(1 <= first(docs) && last(docs) <= size(src, 2))	|| throw(CorpusError("document index outside corpus range."))
+	Mq = length(docs)
+	xq = queries === nothing ? xd : src[:, docs]						# explicit query rows only with `queries`
+	idx = zeros(Int32, topn, Mq); score = zeros(Float32, topn, Mq); count = zeros(Int32, Mq)	# column-major (j, q) = C's [q][j]
+	info = TmvbNeighborsInfo()
+	ctx = tmvb_context(device)
+	GC.@preserve info xd xq idx score count begin
+		rc = ccall((:tmvb_topic_neighbors, LIBTMVB), Cint,
+			(Ptr{Cvoid}, Int32, Int32, Int64, Ptr{Float64}, Int64, Ptr{Float64}, Int64, Int32, Int32, Ptr{Int32}, Ptr{Float32}, Ptr{Int32}, Ptr{Cvoid}),
+			ctx, K, NB_METRICS[metric], Md, xd, Mq, queries === nothing ? Ptr{Float64}(C_NULL) : pointer(xq), queries === nothing ? first(docs) - 1 : 0,
+			topn, 0, idx, score, count, pointer_from_objref(info))
+		tmvb_destroy_context(ctx)
+		tmvb_check(rc)
+	end
+	s = Float64.(score)
+	distance = metric == :hellinger ? sqrt.(max.(0.0, 1.0 .- s)) : metric == :cosine ? 1.0 .- s : nothing
+	return (idx=Int.(idx) .+ 1, score=score, distance=distance, count=Int.(count),
+			ms=(prep=info.ms_prep, scan=info.ms_scan, merge=info.ms_merge), splits=Int(info.splits))
+end
