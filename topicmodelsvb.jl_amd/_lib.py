@@ -12,6 +12,8 @@ import os
 import subprocess
 import sys
 
+import numpy as np
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
 LIB_PATH = os.path.join(_HERE, "libtmvb_hip.so")
@@ -166,6 +168,24 @@ P_i64 = C.POINTER(C.c_int64)
 P_i32 = C.POINTER(C.c_int32)
 P_dbl = C.POINTER(C.c_double)
 VP = C.c_void_p
+
+
+# ---- argument and result plumbing of the entry points that work without a model handle (heldout, gencorp, coherence, neighbors)
+def _handle(ctx):
+    """the tmvb_ctx* of a DeviceContext; None: a NULL context"""
+    return ctx.handle if ctx is not None else C.c_void_p(None)
+
+
+def _csr(doc_ptr, terms, counts):
+    return (np.ascontiguousarray(doc_ptr, dtype=np.int64), np.ascontiguousarray(terms, dtype=np.int32), np.ascontiguousarray(counts, dtype=np.int32))
+
+
+def _copy(ptr, n, dt):
+    """numpy copy of n elements of a buffer the library owns (a result struct's, freed right after)"""
+    n = int(n)
+    if n == 0 or not ptr:
+        return np.zeros(0, dtype=dt)
+    return np.ctypeslib.as_array(ptr, shape=(n,)).astype(dt, copy=True)
 
 
 def exported_symbols():

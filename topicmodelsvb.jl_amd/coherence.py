@@ -17,8 +17,8 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import CorpusError, check, lib, P_dbl, P_i32, P_i64
-from .lda import DeviceContext, _packed
+from ._lib import CorpusError, _csr, _handle, check, lib, P_dbl, P_i32, P_i64
+from .lda import _packed, call_context
 
 CODF_CHUNK_DOCS = 4096              # TMVB_CODF_CHUNK_DOCS (include/tmvb.h): documents per workgroup of the pair pass
 TOPN_MIN, TOPN_MAX = 2, 64
@@ -63,17 +63,11 @@ class CoherenceResult:
         return f"CoherenceResult(K={K}, N={N}, mean_umass={self.mean_umass:.6g}, mean_npmi={self.mean_npmi:.6g}, diversity={self.diversity:.3g})"
 
 
-def _handle(ctx):
-    return ctx.handle if ctx is not None else C.c_void_p(None)
-
-
 def codocfreq_raw(ctx, M, V, doc_ptr, terms, counts, top, max_bitset_bytes=0):
     """The ABI call tmvb_corpus_codocfreq.  ctx: a DeviceContext, or None for a NULL context (the library then answers TMVB_ENODEVICE on a
     machine without a GPU); top: K x N 0-based term ids.  Returns (status, dict) or (status, message): nothing raises here."""
     L = lib()
-    doc_ptr = np.ascontiguousarray(doc_ptr, dtype=np.int64)
-    terms = np.ascontiguousarray(terms, dtype=np.int32)
-    counts = np.ascontiguousarray(counts, dtype=np.int32)
+    doc_ptr, terms, counts = _csr(doc_ptr, terms, counts)
     top = np.ascontiguousarray(top, dtype=np.int32)
     if top.ndim != 2:
         return 1, "codocfreq_raw: top must be a K x N array"
@@ -141,11 +135,8 @@ def coherence(model_or_top, corp, topn: int = 10, device_id: int = 0, max_bitset
     if hasattr(model_or_top, "topics") and pc.V != model_or_top.V:
         raise CorpusError("coherence corpus and model must have identical vocabularies.")
     top = _top_of(model_or_top, int(topn))
-    ctx = DeviceContext(device_id)
-    try:
+    with call_context(device_id) as ctx:
         rc, res = codocfreq_raw(ctx, pc.M, pc.V, pc.doc_ptr, pc.terms, pc.counts, top, max_bitset_bytes)
-    finally:
-        ctx.close()
     check(rc)
     umass, npmi, undef = coherence_from_counts(res["codf"], pc.M)
     return CoherenceResult(top, res["codf"], umass, npmi, undef, res["ms"], res["n_slots"], res["n_batches"])

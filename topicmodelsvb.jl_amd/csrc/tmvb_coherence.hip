@@ -20,6 +20,7 @@
 //
 // tmvb_coherence_from_counts.  fp64 on the host, compensated sums; touches no device.
 #include "tmvb_internal.h"
+#include "tmvb_call.h"
 
 #include <algorithm>
 #include <cstring>
@@ -90,35 +91,6 @@ static __global__ __launch_bounds__(CODF_WG) void codf_pairs_kernel(int64_t M, i
 
 // ------------------------------------------------------------------------------------------------------------------ host
 namespace {
-struct codf_pool {                  // device allocations and events of one call
-    std::vector<void*> ptrs;
-    std::vector<hipEvent_t> evs;
-    ~codf_pool()
-    {
-        for (void* p : ptrs) (void)hipFree(p);
-        for (hipEvent_t e : evs) (void)hipEventDestroy(e);
-    }
-    template <typename T>
-    int alloc(T** p, size_t n)
-    {
-        *p = nullptr;
-        const size_t bytes = std::max<size_t>(n, 1) * sizeof(T);
-        const hipError_t e = hipMalloc((void**)p, bytes);
-        if (e != hipSuccess) { tmvb_set_error("codocfreq: hipMalloc(%zu bytes) failed: %s", bytes, hipGetErrorString(e)); return TMVB_ENOMEM; }
-        ptrs.push_back(*p);
-        return TMVB_OK;
-    }
-    int events(int n)
-    {
-        for (int i = 0; i < n; i++) {
-            hipEvent_t e;
-            TMVB_HIP(hipEventCreate(&e));
-            evs.push_back(e);
-        }
-        return TMVB_OK;
-    }
-};
-
 // the K, N, M rules both entry points share
 int codf_check_shape(const char* fn, int32_t K, int32_t N, int64_t M)
 {
@@ -171,23 +143,23 @@ int codf_run(tmvb_ctx* ctx, int64_t M, int64_t V, const int64_t* doc_ptr, const 
             if (!seen[(size_t)top[q]]) { seen[(size_t)top[q]] = 1; T_all++; }
     }
 
-    TMVB_HIP(hipSetDevice(ctx->device));
+    // host staging, declared in front of the call's scope
+    std::vector<int32_t> h_map((size_t)V), h_slots((size_t)Kb_max * N);
+    std::vector<int64_t> h_codf((size_t)Kb_max * N * N);
+
     hipStream_t st = ctx->stream;
-    codf_pool pool;
-    int rc = pool.events(3);
-    if (rc != TMVB_OK) return rc;
+    tmvb_call c("codocfreq", ctx->device, st);
+    TMVB_CALL_TRY(c, c.begin());
+    TMVB_CALL_TRY(c, c.events(3));
     int64_t* d_ptr;
     int32_t *d_terms, *d_map, *d_slots;
     unsigned long long *d_bits, *d_codf;
-    if ((rc = pool.alloc(&d_ptr, (size_t)M + 1)) != TMVB_OK || (rc = pool.alloc(&d_terms, (size_t)nnz)) != TMVB_OK || (rc = pool.alloc(&d_map, (size_t)V)) != TMVB_OK ||
-        (rc = pool.alloc(&d_slots, (size_t)Kb_max * N)) != TMVB_OK || (rc = pool.alloc(&d_bits, (size_t)(T_max * Ws))) != TMVB_OK ||
-        (rc = pool.alloc(&d_codf, (size_t)Kb_max * N * N)) != TMVB_OK)
-        return rc;
-    TMVB_HIP(hipMemcpyAsync(d_ptr, doc_ptr, ((size_t)M + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
-    if (nnz > 0) TMVB_HIP(hipMemcpyAsync(d_terms, terms, (size_t)nnz * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    TMVB_CALL_TRY(c, c.alloc(&d_ptr, (size_t)M + 1)); TMVB_CALL_TRY(c, c.alloc(&d_terms, (size_t)nnz)); TMVB_CALL_TRY(c, c.alloc(&d_map, (size_t)V));
+    TMVB_CALL_TRY(c, c.alloc(&d_slots, (size_t)Kb_max * N)); TMVB_CALL_TRY(c, c.alloc(&d_bits, (size_t)(T_max * Ws)));
+    TMVB_CALL_TRY(c, c.alloc(&d_codf, (size_t)Kb_max * N * N));
+    TMVB_CALL_HIP(c, hipMemcpyAsync(d_ptr, doc_ptr, ((size_t)M + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    if (nnz > 0) TMVB_CALL_HIP(c, hipMemcpyAsync(d_terms, terms, (size_t)nnz * sizeof(int32_t), hipMemcpyHostToDevice, st));
     static_assert(sizeof(unsigned long long) == sizeof(int64_t), "counts travel as 64-bit integers");
-    std::vector<int32_t> h_map((size_t)V), h_slots((size_t)Kb_max * N);
-    std::vector<int64_t> h_codf((size_t)Kb_max * N * N);
     const int64_t chunks = (W + CODF_CHUNK_WORDS - 1) / CODF_CHUNK_WORDS;
     const unsigned build_blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>((nnz + CODF_WG - 1) / CODF_WG, (int64_t)ctx->num_cu * 8));
     float ms_bitset = 0.0f, ms_pairs = 0.0f;
@@ -200,27 +172,27 @@ int codf_run(tmvb_ctx* ctx, int64_t M, int64_t V, const int64_t* doc_ptr, const 
             if (s < 0) s = T++;
             h_slots[(size_t)q] = s;
         }
-        TMVB_HIP(hipMemcpyAsync(d_map, h_map.data(), (size_t)V * sizeof(int32_t), hipMemcpyHostToDevice, st));
-        TMVB_HIP(hipMemcpyAsync(d_slots, h_slots.data(), (size_t)Kb * N * sizeof(int32_t), hipMemcpyHostToDevice, st));
-        TMVB_HIP(hipMemsetAsync(d_bits, 0, (size_t)(T * Ws) * sizeof(unsigned long long), st));
-        TMVB_HIP(hipMemsetAsync(d_codf, 0, (size_t)Kb * N * N * sizeof(unsigned long long), st));
+        TMVB_CALL_HIP(c, hipMemcpyAsync(d_map, h_map.data(), (size_t)V * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        TMVB_CALL_HIP(c, hipMemcpyAsync(d_slots, h_slots.data(), (size_t)Kb * N * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        TMVB_CALL_HIP(c, hipMemsetAsync(d_bits, 0, (size_t)(T * Ws) * sizeof(unsigned long long), st));
+        TMVB_CALL_HIP(c, hipMemsetAsync(d_codf, 0, (size_t)Kb * N * N * sizeof(unsigned long long), st));
         // stage times: the events bracket the two kernels only; allocations, copies and memsets lie outside
-        TMVB_HIP(hipEventRecord(pool.evs[0], st));
+        TMVB_CALL_HIP(c, hipEventRecord(c.ev(0), st));
         if (nnz > 0)
             hipLaunchKernelGGL(codf_bitset_kernel, dim3(build_blocks), dim3(CODF_WG), 0, st, M, nnz, Ws, (const int64_t*)d_ptr, (const int32_t*)d_terms,
                                (const int32_t*)d_map, d_bits);
-        TMVB_HIP(hipGetLastError());
-        TMVB_HIP(hipEventRecord(pool.evs[1], st));
+        TMVB_CALL_HIP(c, hipGetLastError());
+        TMVB_CALL_HIP(c, hipEventRecord(c.ev(1), st));
         hipLaunchKernelGGL(codf_pairs_kernel, dim3((unsigned)chunks, (unsigned)Kb), dim3(CODF_WG), 0, st, M, Ws, (int)N, (const int32_t*)d_slots,
                            (const unsigned long long*)d_bits, d_codf);
-        TMVB_HIP(hipGetLastError());
-        TMVB_HIP(hipEventRecord(pool.evs[2], st));
-        TMVB_HIP(hipMemcpyAsync(h_codf.data(), d_codf, (size_t)Kb * N * N * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-        TMVB_HIP(hipStreamSynchronize(st));             // the next batch rewrites the map, the slot table and the bit matrix
-        float a = 0.0f, c = 0.0f;
-        TMVB_HIP(hipEventElapsedTime(&a, pool.evs[0], pool.evs[1]));
-        TMVB_HIP(hipEventElapsedTime(&c, pool.evs[1], pool.evs[2]));
-        ms_bitset += a; ms_pairs += c;
+        TMVB_CALL_HIP(c, hipGetLastError());
+        TMVB_CALL_HIP(c, hipEventRecord(c.ev(2), st));
+        TMVB_CALL_HIP(c, hipMemcpyAsync(h_codf.data(), d_codf, (size_t)Kb * N * N * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+        TMVB_CALL_HIP(c, hipStreamSynchronize(st));             // the next batch rewrites the map, the slot table and the bit matrix
+        float ms_b = 0.0f, ms_p = 0.0f;
+        TMVB_CALL_TRY(c, c.elapsed(&ms_b, 0, 1));
+        TMVB_CALL_TRY(c, c.elapsed(&ms_p, 1, 2));
+        ms_bitset += ms_b; ms_pairs += ms_p;
         for (int32_t k = 0; k < Kb; k++)                // mirror the lower triangle
             for (int i = 0; i < N; i++)
                 for (int j = 0; j <= i; j++) {

@@ -198,6 +198,56 @@ extern "C" int tmvb_ctx_synchronize(tmvb_ctx* ctx)
     return TMVB_OK;
 }
 
+// ---- host checks of the entry points that take their arguments without a handle (declared in tmvb_internal.h)
+#define TMVB_HOST_CSR_MAX_NNZ ((int64_t)INT32_MAX - 1)
+// the check_doc / check_corp rules of tmvb_corpus_create on a host CSR; doc_tokens_limit: a document must stay below 2^31 tokens
+int tmvb_check_host_csr(const char* fn, int64_t M, int64_t V, const int64_t* doc_ptr, const int32_t* terms, const int32_t* counts, bool doc_tokens_limit)
+{
+    TMVB_REQUIRE(M > 0, TMVB_EINVAL, "%s: M must be a positive integer", fn);
+    TMVB_REQUIRE(V > 0, TMVB_EINVAL, "%s: V must be a positive integer", fn);
+    TMVB_REQUIRE(M < (int64_t)INT32_MAX, TMVB_EINVAL, "%s: M = %lld above 2^31 - 2 documents per call", fn, (long long)M);
+    TMVB_REQUIRE(doc_ptr && terms && counts, TMVB_EINVAL, "%s: NULL argument", fn);
+    TMVB_REQUIRE(doc_ptr[0] == 0, TMVB_ESHAPE, "%s: doc_ptr must start at 0", fn);
+    for (int64_t d = 0; d < M; d++) TMVB_REQUIRE(doc_ptr[d + 1] >= doc_ptr[d], TMVB_ESHAPE, "%s: doc_ptr decreases at document %lld", fn, (long long)d);
+    TMVB_REQUIRE(doc_ptr[M] < TMVB_HOST_CSR_MAX_NNZ, TMVB_EINVAL, "%s: %lld entries in one call (limit 2^31 - 2); split the corpus by documents", fn, (long long)doc_ptr[M]);
+    for (int64_t d = 0; d < M; d++) {
+        int64_t C = 0;
+        for (int64_t j = doc_ptr[d]; j < doc_ptr[d + 1]; j++) {
+            TMVB_REQUIRE(terms[j] >= 0 && terms[j] < V, TMVB_ESHAPE, "%s: document %lld holds term %d outside [0, %lld)", fn, (long long)d, terms[j], (long long)V);
+            TMVB_REQUIRE(counts[j] >= 1, TMVB_ESHAPE, "%s: document %lld holds a count below 1 (all counts must be positive integers)", fn, (long long)d);
+            C += counts[j];
+        }
+        if (doc_tokens_limit)
+            TMVB_REQUIRE(C < ((int64_t)1 << 31), TMVB_EINVAL, "%s: document %lld has %lld tokens (limit 2^31 - 1)", fn, (long long)d, (long long)C);
+    }
+    return TMVB_OK;
+}
+
+// isstochastic(beta, dims=2) (src/modelutils.jl:56); the tolerance is isapprox's for the Float32-derived beta of a device model
+int tmvb_check_stochastic_beta(int32_t K, int64_t V, const double* beta)
+{
+    std::vector<double> rows((size_t)K, 0.0);
+    bool ok = true;
+    for (int64_t v = 0; v < V && ok; v++)
+        for (int k = 0; k < K; k++) {
+            const double x = beta[k + (int64_t)K * v];
+            if (!(x >= 0.0) || !std::isfinite(x)) { ok = false; break; }
+            rows[k] += x;
+        }
+    for (int k = 0; k < K && ok; k++) ok = std::fabs(rows[k] - 1.0) <= 5e-4;
+    TMVB_REQUIRE(ok, TMVB_ESHAPE, "beta must be a right stochastic matrix.");
+    return TMVB_OK;
+}
+
+// arguments are judged first, so a host without a device still gets the argument's own error; then: no device, no result
+int tmvb_check_ctx_or_device(const char* fn, tmvb_ctx* ctx)
+{
+    if (ctx) return TMVB_OK;
+    TMVB_REQUIRE(tmvb_device_count() > 0, TMVB_ENODEVICE, "%s: no HIP device visible (the HIP engine has no CPU fallback)", fn);
+    TMVB_REQUIRE(false, TMVB_EINVAL, "%s: ctx is NULL", fn);
+    return TMVB_OK;
+}
+
 template <typename T>
 static int upload(tmvb_ctx* ctx, T** dptr, const T* h, size_t n)
 {

@@ -17,6 +17,7 @@
 // The M x U matrix is written once per layout (HBM-bound: 2 x 4MU bytes) and sorted in place of the reference's
 // M + U host sortperm calls on a 754 MB fp64 matrix.
 #include "tmvb_internal.h"
+#include "tmvb_call.h"
 
 #include <cstring>
 #include <rocprim/rocprim.hpp>
@@ -107,7 +108,7 @@ struct tmvb_seg_offset {
     __host__ __device__ unsigned operator()(unsigned s) const { return s * n; }
 };
 
-static int sort_segments(tmvb_ctx* ctx, float* keys, float* keys_tmp, int32_t* out, unsigned n_seg, unsigned seg_len)
+static int sort_segments(tmvb_call& c, float* keys, float* keys_tmp, int32_t* out, unsigned n_seg, unsigned seg_len)
 {
     if (n_seg == 0 || seg_len == 0) return TMVB_OK;
     auto values = rocprim::make_transform_iterator(rocprim::make_counting_iterator(0u), tmvb_rev_index{seg_len});
@@ -115,14 +116,14 @@ static int sort_segments(tmvb_ctx* ctx, float* keys, float* keys_tmp, int32_t* o
     size_t tmp_bytes = 0;
     const unsigned size = n_seg * seg_len;
     hipError_t e = rocprim::segmented_radix_sort_pairs_desc(nullptr, tmp_bytes, keys, keys_tmp, values, out, size, n_seg,
-                                                            offsets, offsets + 1, 0, 32, ctx->stream);
+                                                            offsets, offsets + 1, 0, 32, c.stream);
     TMVB_REQUIRE(e == hipSuccess, TMVB_EHIP, "rocprim::segmented_radix_sort_pairs_desc (size query): %s", hipGetErrorString(e));
-    void* tmp = nullptr;
-    TMVB_HIP(hipMalloc(&tmp, std::max<size_t>(tmp_bytes, 16)));
-    e = rocprim::segmented_radix_sort_pairs_desc(tmp, tmp_bytes, keys, keys_tmp, values, out, size, n_seg, offsets, offsets + 1,
-                                                 0, 32, ctx->stream);
-    hipError_t e2 = hipStreamSynchronize(ctx->stream);
-    (void)hipFree(tmp);
+    char* tmp;
+    const int rc = c.alloc(&tmp, std::max<size_t>(tmp_bytes, 16));
+    if (rc != TMVB_OK) return rc;
+    e = rocprim::segmented_radix_sort_pairs_desc((void*)tmp, tmp_bytes, keys, keys_tmp, values, out, size, n_seg, offsets, offsets + 1,
+                                                 0, 32, c.stream);
+    hipError_t e2 = hipStreamSynchronize(c.stream);
     TMVB_REQUIRE(e == hipSuccess && e2 == hipSuccess, TMVB_EHIP, "rocprim::segmented_radix_sort_pairs_desc: %s",
                  hipGetErrorString(e != hipSuccess ? e : e2));
     return TMVB_OK;
@@ -135,37 +136,30 @@ extern "C" int tmvb_ctpf_recommend(tmvb_ctpf* h, double* scores, int32_t* drecs,
     int rc = tmvb_ctpf_view_of(h, &v);
     if (rc) return rc;
     tmvb_ctx* ctx = v.ctx;
-    TMVB_HIP(hipSetDevice(ctx->device));
     const int64_t M = v.M, U = v.U;
     const int K = v.K, KS = (K + 1) / 2 * 2;
     TMVB_REQUIRE((drecs == nullptr) == (urecs == nullptr), TMVB_EINVAL, "tmvb_ctpf_recommend: drecs and urecs come together");
     TMVB_REQUIRE(M * U < (int64_t)4294967295ll, TMVB_ESHAPE, "tmvb_ctpf_recommend: M * U = %lld exceeds the 32-bit sort size", (long long)(M * U));
     if (M == 0 || U == 0) return TMVB_OK;
     const bool rank = drecs != nullptr;
-    float *X = nullptr, *Y = nullptr, *keyD = nullptr, *keyU = nullptr, *ktmp = nullptr, *sc = nullptr;
-    int32_t *rankD = nullptr, *rankU = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
-    auto cleanup = [&]() {
-        (void)hipFree(X); (void)hipFree(Y); (void)hipFree(keyD); (void)hipFree(keyU); (void)hipFree(ktmp); (void)hipFree(sc);
-        (void)hipFree(rankD); (void)hipFree(rankU);
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-        if (e2) (void)hipEventDestroy(e2);
-    };
-#define RECS_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { tmvb_set_error("%s failed: %s", #expr, hipGetErrorString(e_)); cleanup(); return TMVB_EHIP; } } while (0)
     const size_t MU = (size_t)M * U;
-    RECS_TRY(hipMalloc((void**)&X, (size_t)M * KS * sizeof(float)));
-    RECS_TRY(hipMalloc((void**)&Y, (size_t)U * KS * sizeof(float)));
+    std::vector<float> h_sc;                             // staging of the scores' read-back: in front of the call's scope
+    tmvb_call c("ctpf_recommend", ctx->device, ctx->stream);
+    TMVB_CALL_TRY(c, c.begin());
+    float *X, *Y, *keyD = nullptr, *keyU = nullptr, *ktmp = nullptr, *sc = nullptr;
+    int32_t *rankD = nullptr, *rankU = nullptr;
+    TMVB_CALL_TRY(c, c.alloc(&X, (size_t)M * KS));
+    TMVB_CALL_TRY(c, c.alloc(&Y, (size_t)U * KS));
     if (rank) {
-        RECS_TRY(hipMalloc((void**)&keyD, MU * sizeof(float)));
-        RECS_TRY(hipMalloc((void**)&keyU, MU * sizeof(float)));
-        RECS_TRY(hipMalloc((void**)&ktmp, MU * sizeof(float)));
-        RECS_TRY(hipMalloc((void**)&rankD, MU * sizeof(int32_t)));
-        RECS_TRY(hipMalloc((void**)&rankU, MU * sizeof(int32_t)));
+        TMVB_CALL_TRY(c, c.alloc(&keyD, MU));
+        TMVB_CALL_TRY(c, c.alloc(&keyU, MU));
+        TMVB_CALL_TRY(c, c.alloc(&ktmp, MU));
+        TMVB_CALL_TRY(c, c.alloc(&rankD, MU));
+        TMVB_CALL_TRY(c, c.alloc(&rankU, MU));
     }
-    if (scores) RECS_TRY(hipMalloc((void**)&sc, MU * sizeof(float)));
-    RECS_TRY(hipEventCreate(&e0)); RECS_TRY(hipEventCreate(&e1)); RECS_TRY(hipEventCreate(&e2));
-    RECS_TRY(hipEventRecord(e0, ctx->stream));
+    if (scores) TMVB_CALL_TRY(c, c.alloc(&sc, MU));
+    TMVB_CALL_TRY(c, c.events(3));
+    TMVB_CALL_HIP(c, hipEventRecord(c.ev(0), ctx->stream));
     hipLaunchKernelGGL(ctpf_expect_docs_kernel, dim3((unsigned)((M * KS + 255) / 256)), dim3(256), 0, ctx->stream, v.gimel, v.zayin,
                        v.rates, K, KS, M, X);
     hipLaunchKernelGGL(ctpf_expect_users_kernel, dim3((unsigned)((U * KS + 255) / 256)), dim3(256), 0, ctx->stream, v.he, v.rates, K,
@@ -176,8 +170,8 @@ extern "C" int tmvb_ctpf_recommend(tmvb_ctpf* h, double* scores, int32_t* drecs,
     if (rank)
         hipLaunchKernelGGL(ctpf_mask_read_kernel, dim3((unsigned)M), dim3(256), 0, ctx->stream, v.corp->d_rdr_ptr, v.corp->d_readers, M, U,
                            keyD, keyU);
-    RECS_TRY(hipGetLastError());
-    RECS_TRY(hipEventRecord(e1, ctx->stream));
+    TMVB_CALL_HIP(c, hipGetLastError());
+    TMVB_CALL_HIP(c, hipEventRecord(c.ev(1), ctx->stream));
     if (rank) {
         // candidates per segment = segment length - distinct (document, reader) pairs masked above
         for (int64_t u = 0; u < U; ++u) urec_count[u] = (int32_t)M;
@@ -189,24 +183,22 @@ extern "C" int tmvb_ctpf_recommend(tmvb_ctpf* h, double* scores, int32_t* drecs,
             drec_count[d] = (int32_t)(U - (int64_t)rd.size());
             for (int32_t u : rd) urec_count[u]--;
         }
-        if ((rc = sort_segments(ctx, keyD, ktmp, rankD, (unsigned)M, (unsigned)U))) { cleanup(); return rc; }
-        if ((rc = sort_segments(ctx, keyU, ktmp, rankU, (unsigned)U, (unsigned)M))) { cleanup(); return rc; }
+        TMVB_CALL_TRY(c, sort_segments(c, keyD, ktmp, rankD, (unsigned)M, (unsigned)U));
+        TMVB_CALL_TRY(c, sort_segments(c, keyU, ktmp, rankU, (unsigned)U, (unsigned)M));
     }
-    RECS_TRY(hipEventRecord(e2, ctx->stream));
-    RECS_TRY(hipEventSynchronize(e2));
-    if (ms_scores) RECS_TRY(hipEventElapsedTime(ms_scores, e0, e1));
-    if (ms_rank) RECS_TRY(hipEventElapsedTime(ms_rank, e1, e2));
+    TMVB_CALL_HIP(c, hipEventRecord(c.ev(2), ctx->stream));
+    TMVB_CALL_HIP(c, hipEventSynchronize(c.ev(2)));
+    if (ms_scores) TMVB_CALL_TRY(c, c.elapsed(ms_scores, 0, 1));
+    if (ms_rank) TMVB_CALL_TRY(c, c.elapsed(ms_rank, 1, 2));
     if (scores) {
-        std::vector<float> tmp(MU);
-        RECS_TRY(hipMemcpyAsync(tmp.data(), sc, MU * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-        RECS_TRY(hipStreamSynchronize(ctx->stream));
-        for (size_t q = 0; q < MU; ++q) scores[q] = (double)tmp[q];
+        h_sc.resize(MU);
+        TMVB_CALL_HIP(c, hipMemcpyAsync(h_sc.data(), sc, MU * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+        TMVB_CALL_HIP(c, hipStreamSynchronize(ctx->stream));
+        for (size_t q = 0; q < MU; ++q) scores[q] = (double)h_sc[q];
     }
     if (rank) {
-        RECS_TRY(hipMemcpy(drecs, rankD, MU * sizeof(int32_t), hipMemcpyDeviceToHost));
-        RECS_TRY(hipMemcpy(urecs, rankU, MU * sizeof(int32_t), hipMemcpyDeviceToHost));
+        TMVB_CALL_HIP(c, hipMemcpy(drecs, rankD, MU * sizeof(int32_t), hipMemcpyDeviceToHost));
+        TMVB_CALL_HIP(c, hipMemcpy(urecs, rankU, MU * sizeof(int32_t), hipMemcpyDeviceToHost));
     }
-#undef RECS_TRY
-    cleanup();
     return TMVB_OK;
 }

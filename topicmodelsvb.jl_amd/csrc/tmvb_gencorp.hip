@@ -23,6 +23,7 @@
 //   condense  segmented radix sort of each document's term ids (rocPRIM through hipcub), run-length encode, scan, write.
 // No floating-point atomics; the diagnostic count matrices use integer atomics (order-independent).
 #include "tmvb_internal.h"
+#include "tmvb_call.h"
 #include "tmvb_philox.h"
 
 #include <algorithm>
@@ -281,34 +282,6 @@ static __global__ __launch_bounds__(64) void gencorp_rle_kernel(const int32_t* _
 
 // ------------------------------------------------------------------------------------------------------------------ host
 namespace {
-struct gc_pool {                    // device allocations and events of one call
-    std::vector<void*> ptrs;
-    std::vector<hipEvent_t> evs;
-    ~gc_pool()
-    {
-        for (void* p : ptrs) (void)hipFree(p);
-        for (hipEvent_t e : evs) (void)hipEventDestroy(e);
-    }
-    template <typename T>
-    int alloc(T** p, size_t n)
-    {
-        *p = nullptr;
-        const size_t bytes = std::max<size_t>(n, 1) * sizeof(T);
-        const hipError_t e = hipMalloc((void**)p, bytes);
-        if (e != hipSuccess) { tmvb_set_error("gencorp: hipMalloc(%zu bytes) failed: %s", bytes, hipGetErrorString(e)); return TMVB_ENOMEM; }
-        ptrs.push_back(*p);
-        return TMVB_OK;
-    }
-};
-
-template <typename T>
-int gc_host(T** p, size_t n)
-{
-    *p = (T*)malloc(std::max<size_t>(n, 1) * sizeof(T));
-    if (!*p) { tmvb_set_error("gencorp: out of host memory"); return TMVB_ENOMEM; }
-    return TMVB_OK;
-}
-
 // lower Cholesky factor of the column-major (symmetric) K x K sigma, row-major; false if sigma is not positive-definite
 bool gc_cholesky(const double* sigma, int K, std::vector<double>& L)
 {
@@ -340,93 +313,61 @@ int gc_check_common(const char* fn, int32_t K, int32_t maxK, int64_t V, const do
     // one 64-lane workgroup per document: the grid must stay below 2^32 threads
     TMVB_REQUIRE(M <= GC_MAX_M, TMVB_EINVAL, "%s: M = %lld above %lld documents per call; generate in shards through doc_offset", fn, (long long)M, (long long)GC_MAX_M);
     TMVB_REQUIRE(beta != nullptr, TMVB_EINVAL, "%s: NULL argument", fn);
-    // isstochastic(beta, dims=2) (src/modelutils.jl:56); the tolerance is isapprox's for the Float32-derived beta of a device model
-    std::vector<double> rows((size_t)K, 0.0);
-    bool ok = true;
-    for (int64_t v = 0; v < V && ok; v++)
-        for (int k = 0; k < K; k++) {
-            const double x = beta[k + (int64_t)K * v];
-            if (!(x >= 0.0) || !std::isfinite(x)) { ok = false; break; }
-            rows[k] += x;
-        }
-    for (int k = 0; k < K && ok; k++) ok = std::fabs(rows[k] - 1.0) <= 5e-4;
-    TMVB_REQUIRE(ok, TMVB_ESHAPE, "beta must be a right stochastic matrix.");
-    return TMVB_OK;
+    return tmvb_check_stochastic_beta(K, V, beta);
 }
-
-// arguments are judged first, so a host without a device still gets the argument's own error; then: no device, no result
-int gc_check_ctx(const char* fn, tmvb_ctx* ctx)
-{
-    if (ctx) return TMVB_OK;
-    TMVB_REQUIRE(tmvb_device_count() > 0, TMVB_ENODEVICE, "%s: no HIP device visible (the HIP engine has no CPU fallback)", fn);
-    TMVB_REQUIRE(false, TMVB_EINVAL, "%s: ctx is NULL", fn);
-    return TMVB_OK;
-}
-
-#define GC_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { tmvb_set_error("%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
-                                                                          tmvb_gencorp_free(out); return TMVB_EHIP; } } while (0)
-#define GC_TRY(expr) do { const int rc_ = (expr); if (rc_ != TMVB_OK) { tmvb_gencorp_free(out); return rc_; } } while (0)
 
 // par: alpha (chol == NULL) or mu; chol: row-major lower factor of sigma
 int gc_run(tmvb_ctx* ctx, int32_t K, int64_t V, const double* par, const double* chol, const double* beta, int64_t M, int64_t doc_offset, double mean_C,
            double a, uint64_t seed, int32_t flags, tmvb_gencorp_t* out)
 {
-    GC_HIP(hipSetDevice(ctx->device));
+    tmvb_result_guard<tmvb_gencorp_t, tmvb_gencorp_free> guard{out};
+    int64_t T = 0, nnz = 0;         // read back from the device: in front of the call's scope
     hipStream_t st = ctx->stream;
-    gc_pool pool;
+    tmvb_call c("gencorp", ctx->device, st);
+    TMVB_CALL_TRY(c, c.begin());
     const bool diag = (flags & 1) != 0;
     const int nb = (int)((V + GC_BLOCK - 1) / GC_BLOCK);
     const int64_t KV = (int64_t)K * V, Knb = (int64_t)K * nb;
-    for (int i = 0; i < 8; i++) {
-        hipEvent_t e;
-        GC_HIP(hipEventCreate(&e));
-        pool.evs.push_back(e);
-    }
+    TMVB_CALL_TRY(c, c.events(8));
     double *d_beta, *d_bsum, *d_bcdf, *d_par, *d_chol = nullptr;
     float *d_wcdf, *d_lt;
     int64_t *d_C, *d_tokptr, *d_nu, *d_docptr;
-    GC_TRY(pool.alloc(&d_beta, (size_t)KV)); GC_TRY(pool.alloc(&d_bsum, (size_t)Knb)); GC_TRY(pool.alloc(&d_bcdf, (size_t)Knb));
-    GC_TRY(pool.alloc(&d_wcdf, (size_t)Knb * GC_BLOCK)); GC_TRY(pool.alloc(&d_par, (size_t)K)); GC_TRY(pool.alloc(&d_lt, (size_t)M * K));
-    GC_TRY(pool.alloc(&d_C, (size_t)M + 1)); GC_TRY(pool.alloc(&d_tokptr, (size_t)M + 1)); GC_TRY(pool.alloc(&d_nu, (size_t)M + 1));
-    GC_TRY(pool.alloc(&d_docptr, (size_t)M + 1));
-    if (chol) GC_TRY(pool.alloc(&d_chol, (size_t)K * K));
-    GC_HIP(hipMemcpyAsync(d_beta, beta, (size_t)KV * sizeof(double), hipMemcpyHostToDevice, st));
-    GC_HIP(hipMemcpyAsync(d_par, par, (size_t)K * sizeof(double), hipMemcpyHostToDevice, st));
-    if (chol) GC_HIP(hipMemcpyAsync(d_chol, chol, (size_t)K * K * sizeof(double), hipMemcpyHostToDevice, st));
-    GC_HIP(hipMemsetAsync(d_C, 0, ((size_t)M + 1) * sizeof(int64_t), st));
-    GC_HIP(hipMemsetAsync(d_nu, 0, ((size_t)M + 1) * sizeof(int64_t), st));
+    TMVB_CALL_TRY(c, c.alloc(&d_beta, (size_t)KV)); TMVB_CALL_TRY(c, c.alloc(&d_bsum, (size_t)Knb)); TMVB_CALL_TRY(c, c.alloc(&d_bcdf, (size_t)Knb));
+    TMVB_CALL_TRY(c, c.alloc(&d_wcdf, (size_t)Knb * GC_BLOCK)); TMVB_CALL_TRY(c, c.alloc(&d_par, (size_t)K)); TMVB_CALL_TRY(c, c.alloc(&d_lt, (size_t)M * K));
+    TMVB_CALL_TRY(c, c.alloc(&d_C, (size_t)M + 1)); TMVB_CALL_TRY(c, c.alloc(&d_tokptr, (size_t)M + 1)); TMVB_CALL_TRY(c, c.alloc(&d_nu, (size_t)M + 1));
+    TMVB_CALL_TRY(c, c.alloc(&d_docptr, (size_t)M + 1));
+    if (chol) TMVB_CALL_TRY(c, c.alloc(&d_chol, (size_t)K * K));
+    TMVB_CALL_HIP(c, hipMemcpyAsync(d_beta, beta, (size_t)KV * sizeof(double), hipMemcpyHostToDevice, st));
+    TMVB_CALL_HIP(c, hipMemcpyAsync(d_par, par, (size_t)K * sizeof(double), hipMemcpyHostToDevice, st));
+    if (chol) TMVB_CALL_HIP(c, hipMemcpyAsync(d_chol, chol, (size_t)K * K * sizeof(double), hipMemcpyHostToDevice, st));
+    TMVB_CALL_HIP(c, hipMemsetAsync(d_C, 0, ((size_t)M + 1) * sizeof(int64_t), st));
+    TMVB_CALL_HIP(c, hipMemsetAsync(d_nu, 0, ((size_t)M + 1) * sizeof(int64_t), st));
     size_t scan_bytes = 0;
-    GC_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, (const int64_t*)d_C, d_tokptr, (int)(M + 1), st));
-    void* d_scan;
-    {
-        char* p;
-        GC_TRY(pool.alloc(&p, std::max<size_t>(scan_bytes, 16)));
-        d_scan = p;
-    }
+    TMVB_CALL_HIP(c, hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, (const int64_t*)d_C, d_tokptr, (int)(M + 1), st));
+    char* d_scan;
+    TMVB_CALL_TRY(c, c.alloc(&d_scan, std::max<size_t>(scan_bytes, 16)));
 
     // Stage times: every pair of events brackets kernels and hipcub calls only; allocations, memsets, the two 8-byte read-backs and
     // their stream synchronisations lie outside the pairs (ms_condense adds its two pairs).
     // ---- tables
-    GC_HIP(hipEventRecord(pool.evs[0], st));
+    TMVB_CALL_HIP(c, hipEventRecord(c.ev(0), st));
     hipLaunchKernelGGL(gencorp_blocks_kernel, dim3((unsigned)nb, (unsigned)K), dim3(64), 0, st, (const double*)d_beta, (int)K, V, nb, a, 1.0 + a * (double)V, d_bsum, d_wcdf);
     hipLaunchKernelGGL(gencorp_blockcdf_kernel, dim3((unsigned)((K + 63) / 64)), dim3(64), 0, st, (const double*)d_bsum, (int)K, nb, d_bcdf);
-    GC_HIP(hipGetLastError());
+    TMVB_CALL_HIP(c, hipGetLastError());
     // ---- documents: theta and C_d, then the token offsets
-    GC_HIP(hipEventRecord(pool.evs[1], st));
+    TMVB_CALL_HIP(c, hipEventRecord(c.ev(1), st));
     if (chol)
         hipLaunchKernelGGL(gencorp_docs_kernel<true>, dim3((unsigned)M), dim3(64), 0, st, (int)K, doc_offset, seed, mean_C, (const double*)d_par, (const double*)d_chol, d_lt, d_C);
     else
         hipLaunchKernelGGL(gencorp_docs_kernel<false>, dim3((unsigned)M), dim3(64), 0, st, (int)K, doc_offset, seed, mean_C, (const double*)d_par, (const double*)nullptr, d_lt, d_C);
-    GC_HIP(hipGetLastError());
-    GC_HIP(hipcub::DeviceScan::ExclusiveSum(d_scan, scan_bytes, (const int64_t*)d_C, d_tokptr, (int)(M + 1), st));
-    GC_HIP(hipEventRecord(pool.evs[2], st));
-    int64_t T = 0;
-    GC_HIP(hipMemcpyAsync(&T, d_tokptr + M, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    GC_HIP(hipStreamSynchronize(st));
+    TMVB_CALL_HIP(c, hipGetLastError());
+    TMVB_CALL_HIP(c, hipcub::DeviceScan::ExclusiveSum(d_scan, scan_bytes, (const int64_t*)d_C, d_tokptr, (int)(M + 1), st));
+    TMVB_CALL_HIP(c, hipEventRecord(c.ev(2), st));
+    TMVB_CALL_HIP(c, hipMemcpyAsync(&T, d_tokptr + M, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    TMVB_CALL_HIP(c, hipStreamSynchronize(st));
     if (T >= (int64_t)INT32_MAX) {
         tmvb_set_error("gencorp: %lld tokens in one call; generate in shards of fewer than 2^31 tokens through doc_offset", (long long)T);
-        tmvb_gencorp_free(out);
-        return TMVB_EINVAL;
+        return c.fail(TMVB_EINVAL);
     }
 
     // ---- tokens
@@ -435,64 +376,68 @@ int gc_run(tmvb_ctx* ctx, int32_t K, int64_t V, const double* par, const double*
     int* d_off;
     char* d_tmp = nullptr;
     size_t sort_bytes = 0;
-    GC_TRY(pool.alloc(&d_tok, (size_t)T)); GC_TRY(pool.alloc(&d_sorted, (size_t)T)); GC_TRY(pool.alloc(&d_off, (size_t)M + 1));
+    TMVB_CALL_TRY(c, c.alloc(&d_tok, (size_t)T)); TMVB_CALL_TRY(c, c.alloc(&d_sorted, (size_t)T)); TMVB_CALL_TRY(c, c.alloc(&d_off, (size_t)M + 1));
     int end_bit = 1;
     while (end_bit < 31 && ((int64_t)1 << end_bit) < V) end_bit++;
     if (T > 0) {
-        GC_HIP(hipcub::DeviceSegmentedRadixSort::SortKeys(nullptr, sort_bytes, (const int32_t*)d_tok, d_sorted, (int)T, (int)M, (const int*)d_off, (const int*)d_off + 1, 0, end_bit, st));
-        GC_TRY(pool.alloc(&d_tmp, std::max<size_t>(sort_bytes, 16)));
+        TMVB_CALL_HIP(c, hipcub::DeviceSegmentedRadixSort::SortKeys(nullptr, sort_bytes, (const int32_t*)d_tok, d_sorted, (int)T, (int)M, (const int*)d_off, (const int*)d_off + 1, 0, end_bit, st));
+        TMVB_CALL_TRY(c, c.alloc(&d_tmp, std::max<size_t>(sort_bytes, 16)));
     }
     if (diag) {
-        GC_TRY(pool.alloc(&d_dt, (size_t)M * K)); GC_TRY(pool.alloc(&d_tt, (size_t)KV));
-        GC_HIP(hipMemsetAsync(d_dt, 0, (size_t)M * K * sizeof(int32_t), st));
-        GC_HIP(hipMemsetAsync(d_tt, 0, (size_t)KV * sizeof(unsigned long long), st));
+        TMVB_CALL_TRY(c, c.alloc(&d_dt, (size_t)M * K)); TMVB_CALL_TRY(c, c.alloc(&d_tt, (size_t)KV));
+        TMVB_CALL_HIP(c, hipMemsetAsync(d_dt, 0, (size_t)M * K * sizeof(int32_t), st));
+        TMVB_CALL_HIP(c, hipMemsetAsync(d_tt, 0, (size_t)KV * sizeof(unsigned long long), st));
     }
-    GC_HIP(hipEventRecord(pool.evs[3], st));
+    TMVB_CALL_HIP(c, hipEventRecord(c.ev(3), st));
     hipLaunchKernelGGL(gencorp_tokens_kernel, dim3((unsigned)M), dim3(64), 0, st, (int)K, V, nb, doc_offset, seed, (const float*)d_lt, (const int64_t*)d_tokptr,
                        (const double*)d_bcdf, (const float*)d_wcdf, d_tok, d_dt, d_tt);
-    GC_HIP(hipGetLastError());
-    GC_HIP(hipEventRecord(pool.evs[4], st));
+    TMVB_CALL_HIP(c, hipGetLastError());
+    TMVB_CALL_HIP(c, hipEventRecord(c.ev(4), st));
 
     // ---- condense
     hipLaunchKernelGGL(gencorp_offsets32_kernel, dim3((unsigned)((M + 256) / 256)), dim3(256), 0, st, (const int64_t*)d_tokptr, M + 1, d_off);
     if (T > 0)
-        GC_HIP(hipcub::DeviceSegmentedRadixSort::SortKeys((void*)d_tmp, sort_bytes, (const int32_t*)d_tok, d_sorted, (int)T, (int)M, (const int*)d_off, (const int*)d_off + 1, 0, end_bit, st));
+        TMVB_CALL_HIP(c, hipcub::DeviceSegmentedRadixSort::SortKeys((void*)d_tmp, sort_bytes, (const int32_t*)d_tok, d_sorted, (int)T, (int)M, (const int*)d_off, (const int*)d_off + 1, 0, end_bit, st));
     hipLaunchKernelGGL(gencorp_unique_kernel, dim3((unsigned)M), dim3(64), 0, st, (const int32_t*)d_sorted, (const int64_t*)d_tokptr, d_nu);
-    GC_HIP(hipGetLastError());
-    GC_HIP(hipcub::DeviceScan::ExclusiveSum(d_scan, scan_bytes, (const int64_t*)d_nu, d_docptr, (int)(M + 1), st));
-    GC_HIP(hipEventRecord(pool.evs[5], st));
-    int64_t nnz = 0;
-    GC_HIP(hipMemcpyAsync(&nnz, d_docptr + M, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    GC_HIP(hipStreamSynchronize(st));
+    TMVB_CALL_HIP(c, hipGetLastError());
+    TMVB_CALL_HIP(c, hipcub::DeviceScan::ExclusiveSum(d_scan, scan_bytes, (const int64_t*)d_nu, d_docptr, (int)(M + 1), st));
+    TMVB_CALL_HIP(c, hipEventRecord(c.ev(5), st));
+    TMVB_CALL_HIP(c, hipMemcpyAsync(&nnz, d_docptr + M, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    TMVB_CALL_HIP(c, hipStreamSynchronize(st));
     int32_t *d_terms, *d_counts;
-    GC_TRY(pool.alloc(&d_terms, (size_t)nnz)); GC_TRY(pool.alloc(&d_counts, (size_t)nnz));
-    GC_HIP(hipEventRecord(pool.evs[6], st));
+    TMVB_CALL_TRY(c, c.alloc(&d_terms, (size_t)nnz)); TMVB_CALL_TRY(c, c.alloc(&d_counts, (size_t)nnz));
+    TMVB_CALL_HIP(c, hipEventRecord(c.ev(6), st));
     hipLaunchKernelGGL(gencorp_rle_kernel, dim3((unsigned)M), dim3(64), 0, st, (const int32_t*)d_sorted, (const int64_t*)d_tokptr, (const int64_t*)d_docptr, d_terms, d_counts);
-    GC_HIP(hipGetLastError());
-    GC_HIP(hipEventRecord(pool.evs[7], st));
+    TMVB_CALL_HIP(c, hipGetLastError());
+    TMVB_CALL_HIP(c, hipEventRecord(c.ev(7), st));
 
     // ---- results
     out->M = M; out->nnz = nnz; out->sum_counts = T;
-    GC_TRY(gc_host(&out->doc_ptr, (size_t)M + 1)); GC_TRY(gc_host(&out->terms, (size_t)nnz)); GC_TRY(gc_host(&out->counts, (size_t)nnz));
-    GC_HIP(hipMemcpyAsync(out->doc_ptr, d_docptr, ((size_t)M + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    TMVB_CALL_TRY(c, tmvb_host_alloc("gencorp", &out->doc_ptr, (size_t)M + 1));
+    TMVB_CALL_TRY(c, tmvb_host_alloc("gencorp", &out->terms, (size_t)nnz));
+    TMVB_CALL_TRY(c, tmvb_host_alloc("gencorp", &out->counts, (size_t)nnz));
+    TMVB_CALL_HIP(c, hipMemcpyAsync(out->doc_ptr, d_docptr, ((size_t)M + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, st));
     if (nnz > 0) {
-        GC_HIP(hipMemcpyAsync(out->terms, d_terms, (size_t)nnz * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        GC_HIP(hipMemcpyAsync(out->counts, d_counts, (size_t)nnz * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        TMVB_CALL_HIP(c, hipMemcpyAsync(out->terms, d_terms, (size_t)nnz * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        TMVB_CALL_HIP(c, hipMemcpyAsync(out->counts, d_counts, (size_t)nnz * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     }
     if (diag) {
-        GC_TRY(gc_host(&out->log_theta, (size_t)M * K)); GC_TRY(gc_host(&out->doc_topic, (size_t)M * K)); GC_TRY(gc_host(&out->topic_term, (size_t)KV));
-        GC_HIP(hipMemcpyAsync(out->log_theta, d_lt, (size_t)M * K * sizeof(float), hipMemcpyDeviceToHost, st));
-        GC_HIP(hipMemcpyAsync(out->doc_topic, d_dt, (size_t)M * K * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        GC_HIP(hipMemcpyAsync(out->topic_term, d_tt, (size_t)KV * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+        TMVB_CALL_TRY(c, tmvb_host_alloc("gencorp", &out->log_theta, (size_t)M * K));
+        TMVB_CALL_TRY(c, tmvb_host_alloc("gencorp", &out->doc_topic, (size_t)M * K));
+        TMVB_CALL_TRY(c, tmvb_host_alloc("gencorp", &out->topic_term, (size_t)KV));
+        TMVB_CALL_HIP(c, hipMemcpyAsync(out->log_theta, d_lt, (size_t)M * K * sizeof(float), hipMemcpyDeviceToHost, st));
+        TMVB_CALL_HIP(c, hipMemcpyAsync(out->doc_topic, d_dt, (size_t)M * K * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        TMVB_CALL_HIP(c, hipMemcpyAsync(out->topic_term, d_tt, (size_t)KV * sizeof(int64_t), hipMemcpyDeviceToHost, st));
     }
-    GC_HIP(hipStreamSynchronize(st));
-    GC_HIP(hipEventElapsedTime(&out->ms_tables, pool.evs[0], pool.evs[1]));
-    GC_HIP(hipEventElapsedTime(&out->ms_docs, pool.evs[1], pool.evs[2]));
-    GC_HIP(hipEventElapsedTime(&out->ms_tokens, pool.evs[3], pool.evs[4]));
+    TMVB_CALL_HIP(c, hipStreamSynchronize(st));
+    TMVB_CALL_TRY(c, c.elapsed(&out->ms_tables, 0, 1));
+    TMVB_CALL_TRY(c, c.elapsed(&out->ms_docs, 1, 2));
+    TMVB_CALL_TRY(c, c.elapsed(&out->ms_tokens, 3, 4));
     float ms_sort = 0.0f, ms_rle = 0.0f;
-    GC_HIP(hipEventElapsedTime(&ms_sort, pool.evs[4], pool.evs[5]));
-    GC_HIP(hipEventElapsedTime(&ms_rle, pool.evs[6], pool.evs[7]));
+    TMVB_CALL_TRY(c, c.elapsed(&ms_sort, 4, 5));
+    TMVB_CALL_TRY(c, c.elapsed(&ms_rle, 6, 7));
     out->ms_condense = ms_sort + ms_rle;
+    guard.release();
     return TMVB_OK;
 }
 }  // namespace
@@ -511,7 +456,7 @@ extern "C" int tmvb_lda_gencorp(tmvb_ctx* ctx, int32_t K, int64_t V, const doubl
     if (rc != TMVB_OK) return rc;
     TMVB_REQUIRE(alpha != nullptr, TMVB_EINVAL, "tmvb_lda_gencorp: NULL argument");
     for (int k = 0; k < K; k++) TMVB_REQUIRE(std::isfinite(alpha[k]) && alpha[k] > 0.0, TMVB_ESHAPE, "alpha must be positive.");     // src/modelutils.jl:47
-    if ((rc = gc_check_ctx("tmvb_lda_gencorp", ctx)) != TMVB_OK) return rc;
+    if ((rc = tmvb_check_ctx_or_device("tmvb_lda_gencorp", ctx)) != TMVB_OK) return rc;
     return gc_run(ctx, K, V, alpha, nullptr, beta, M, doc_offset, mean_C, laplace_smooth, (uint64_t)seed, flags, out);
 }
 
@@ -524,6 +469,6 @@ extern "C" int tmvb_ctm_gencorp(tmvb_ctx* ctx, int32_t K, int64_t V, const doubl
     for (int k = 0; k < K; k++) TMVB_REQUIRE(std::isfinite(mu[k]), TMVB_ESHAPE, "mu must be finite.");                                // src/modelutils.jl:114
     std::vector<double> L;
     TMVB_REQUIRE(gc_cholesky(sigma, K, L), TMVB_ESHAPE, "sigma must be positive-definite.");                                          // :116
-    if ((rc = gc_check_ctx("tmvb_ctm_gencorp", ctx)) != TMVB_OK) return rc;
+    if ((rc = tmvb_check_ctx_or_device("tmvb_ctm_gencorp", ctx)) != TMVB_OK) return rc;
     return gc_run(ctx, K, V, mu, L.data(), beta, M, doc_offset, mean_C, laplace_smooth, (uint64_t)seed, flags, out);
 }

@@ -19,6 +19,7 @@
 //   ones (host-built lists), so a 5 000-entry document is spread over four waves.  fp32 dot, fp64 log and fp64 sums, reduced in a fixed order:
 //   no atomics, bitwise reproducible.
 #include "tmvb_internal.h"
+#include "tmvb_call.h"
 #include "tmvb_philox.h"
 
 #include <algorithm>
@@ -29,7 +30,6 @@
 #define HO_MAX_K 1024
 #define HO_MAX_KP 1028              // tmvb_kpad(1024)
 #define HO_SHORT_TRIPS 4            // documents of at most this many trips of a wave stay on one wave
-#define HO_MAX_NNZ ((int64_t)INT32_MAX - 1)
 
 // ------------------------------------------------------------------------------------------------------------------ split: draw
 struct ho_widen {
@@ -168,161 +168,90 @@ static __global__ __launch_bounds__(WG) void heldout_loglik_kernel(int K, int KP
 }
 
 // ------------------------------------------------------------------------------------------------------------------ host
-// shared with tmvb_coherence.hip (declared in tmvb_internal.h)
-// the check_doc / check_corp rules of tmvb_corpus_create on a host CSR; doc_tokens_limit: a document must stay below 2^31 tokens
-int tmvb_check_host_csr(const char* fn, int64_t M, int64_t V, const int64_t* doc_ptr, const int32_t* terms, const int32_t* counts, bool doc_tokens_limit)
-{
-    TMVB_REQUIRE(M > 0, TMVB_EINVAL, "%s: M must be a positive integer", fn);
-    TMVB_REQUIRE(V > 0, TMVB_EINVAL, "%s: V must be a positive integer", fn);
-    TMVB_REQUIRE(M < (int64_t)INT32_MAX, TMVB_EINVAL, "%s: M = %lld above 2^31 - 2 documents per call", fn, (long long)M);
-    TMVB_REQUIRE(doc_ptr && terms && counts, TMVB_EINVAL, "%s: NULL argument", fn);
-    TMVB_REQUIRE(doc_ptr[0] == 0, TMVB_ESHAPE, "%s: doc_ptr must start at 0", fn);
-    for (int64_t d = 0; d < M; d++) TMVB_REQUIRE(doc_ptr[d + 1] >= doc_ptr[d], TMVB_ESHAPE, "%s: doc_ptr decreases at document %lld", fn, (long long)d);
-    TMVB_REQUIRE(doc_ptr[M] < HO_MAX_NNZ, TMVB_EINVAL, "%s: %lld entries in one call (limit 2^31 - 2); split the corpus by documents", fn, (long long)doc_ptr[M]);
-    for (int64_t d = 0; d < M; d++) {
-        int64_t C = 0;
-        for (int64_t j = doc_ptr[d]; j < doc_ptr[d + 1]; j++) {
-            TMVB_REQUIRE(terms[j] >= 0 && terms[j] < V, TMVB_ESHAPE, "%s: document %lld holds term %d outside [0, %lld)", fn, (long long)d, terms[j], (long long)V);
-            TMVB_REQUIRE(counts[j] >= 1, TMVB_ESHAPE, "%s: document %lld holds a count below 1 (all counts must be positive integers)", fn, (long long)d);
-            C += counts[j];
-        }
-        if (doc_tokens_limit)
-            TMVB_REQUIRE(C < ((int64_t)1 << 31), TMVB_EINVAL, "%s: document %lld has %lld tokens (limit 2^31 - 1)", fn, (long long)d, (long long)C);
-    }
-    return TMVB_OK;
-}
-
-// arguments are judged first, so a host without a device still gets the argument's own error; then: no device, no result
-int tmvb_check_ctx_or_device(const char* fn, tmvb_ctx* ctx)
-{
-    if (ctx) return TMVB_OK;
-    TMVB_REQUIRE(tmvb_device_count() > 0, TMVB_ENODEVICE, "%s: no HIP device visible (the HIP engine has no CPU fallback)", fn);
-    TMVB_REQUIRE(false, TMVB_EINVAL, "%s: ctx is NULL", fn);
-    return TMVB_OK;
-}
-
 namespace {
-struct ho_pool {                    // device allocations and events of one call
-    std::vector<void*> ptrs;
-    std::vector<hipEvent_t> evs;
-    ~ho_pool()
-    {
-        for (void* p : ptrs) (void)hipFree(p);
-        for (hipEvent_t e : evs) (void)hipEventDestroy(e);
-    }
-    template <typename T>
-    int alloc(T** p, size_t n)
-    {
-        *p = nullptr;
-        const size_t bytes = std::max<size_t>(n, 1) * sizeof(T);
-        const hipError_t e = hipMalloc((void**)p, bytes);
-        if (e != hipSuccess) { tmvb_set_error("heldout: hipMalloc(%zu bytes) failed: %s", bytes, hipGetErrorString(e)); return TMVB_ENOMEM; }
-        ptrs.push_back(*p);
-        return TMVB_OK;
-    }
-    int events(int n)
-    {
-        for (int i = 0; i < n; i++) {
-            hipEvent_t e;
-            TMVB_HIP(hipEventCreate(&e));
-            evs.push_back(e);
-        }
-        return TMVB_OK;
-    }
-};
-
-template <typename T>
-int ho_host(T** p, size_t n)
-{
-    *p = (T*)malloc(std::max<size_t>(n, 1) * sizeof(T));
-    if (!*p) { tmvb_set_error("heldout: out of host memory"); return TMVB_ENOMEM; }
-    return TMVB_OK;
-}
-
-#define HO_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { tmvb_set_error("%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
-                                                                          tmvb_split_free(out); return TMVB_EHIP; } } while (0)
-#define HO_TRY(expr) do { const int rc_ = (expr); if (rc_ != TMVB_OK) { tmvb_split_free(out); return rc_; } } while (0)
-
 int ho_split_run(tmvb_ctx* ctx, int64_t M, const int64_t* doc_ptr, const int32_t* terms, const int32_t* counts, uint64_t thr, uint64_t seed,
                  int64_t doc_offset, tmvb_split_t* out)
 {
-    HO_HIP(hipSetDevice(ctx->device));
+    tmvb_result_guard<tmvb_split_t, tmvb_split_free> guard{out};
     hipStream_t st = ctx->stream;
-    ho_pool pool;
-    HO_TRY(pool.events(4));
+    tmvb_call c("heldout", ctx->device, st);
+    TMVB_CALL_TRY(c, c.begin());
+    TMVB_CALL_TRY(c, c.events(4));
     const int64_t n = doc_ptr[M];
     int64_t *d_ptr, *d_cum, *d_optr, *d_hptr;
     int32_t *d_terms, *d_counts, *d_held, *d_fo, *d_fh, *d_po, *d_ph, *d_ot, *d_oc, *d_ht, *d_hc;
-    HO_TRY(pool.alloc(&d_ptr, (size_t)M + 1)); HO_TRY(pool.alloc(&d_cum, (size_t)n + 1)); HO_TRY(pool.alloc(&d_optr, (size_t)M + 1));
-    HO_TRY(pool.alloc(&d_hptr, (size_t)M + 1)); HO_TRY(pool.alloc(&d_terms, (size_t)n)); HO_TRY(pool.alloc(&d_counts, (size_t)n + 1));
-    HO_TRY(pool.alloc(&d_held, (size_t)n)); HO_TRY(pool.alloc(&d_fo, (size_t)n + 1)); HO_TRY(pool.alloc(&d_fh, (size_t)n + 1));
-    HO_TRY(pool.alloc(&d_po, (size_t)n + 1)); HO_TRY(pool.alloc(&d_ph, (size_t)n + 1)); HO_TRY(pool.alloc(&d_ot, (size_t)n));
-    HO_TRY(pool.alloc(&d_oc, (size_t)n)); HO_TRY(pool.alloc(&d_ht, (size_t)n)); HO_TRY(pool.alloc(&d_hc, (size_t)n));
-    HO_HIP(hipMemcpyAsync(d_ptr, doc_ptr, ((size_t)M + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
-    HO_HIP(hipMemsetAsync(d_counts, 0, ((size_t)n + 1) * sizeof(int32_t), st));        // entry n of the scanned array is read as 0
+    TMVB_CALL_TRY(c, c.alloc(&d_ptr, (size_t)M + 1)); TMVB_CALL_TRY(c, c.alloc(&d_cum, (size_t)n + 1)); TMVB_CALL_TRY(c, c.alloc(&d_optr, (size_t)M + 1));
+    TMVB_CALL_TRY(c, c.alloc(&d_hptr, (size_t)M + 1)); TMVB_CALL_TRY(c, c.alloc(&d_terms, (size_t)n)); TMVB_CALL_TRY(c, c.alloc(&d_counts, (size_t)n + 1));
+    TMVB_CALL_TRY(c, c.alloc(&d_held, (size_t)n)); TMVB_CALL_TRY(c, c.alloc(&d_fo, (size_t)n + 1)); TMVB_CALL_TRY(c, c.alloc(&d_fh, (size_t)n + 1));
+    TMVB_CALL_TRY(c, c.alloc(&d_po, (size_t)n + 1)); TMVB_CALL_TRY(c, c.alloc(&d_ph, (size_t)n + 1)); TMVB_CALL_TRY(c, c.alloc(&d_ot, (size_t)n));
+    TMVB_CALL_TRY(c, c.alloc(&d_oc, (size_t)n)); TMVB_CALL_TRY(c, c.alloc(&d_ht, (size_t)n)); TMVB_CALL_TRY(c, c.alloc(&d_hc, (size_t)n));
+    TMVB_CALL_HIP(c, hipMemcpyAsync(d_ptr, doc_ptr, ((size_t)M + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    TMVB_CALL_HIP(c, hipMemsetAsync(d_counts, 0, ((size_t)n + 1) * sizeof(int32_t), st));        // entry n of the scanned array is read as 0
     if (n > 0) {
-        HO_HIP(hipMemcpyAsync(d_terms, terms, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, st));
-        HO_HIP(hipMemcpyAsync(d_counts, counts, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        TMVB_CALL_HIP(c, hipMemcpyAsync(d_terms, terms, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        TMVB_CALL_HIP(c, hipMemcpyAsync(d_counts, counts, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, st));
     }
-    HO_HIP(hipMemsetAsync(d_held, 0, std::max<size_t>((size_t)n, 1) * sizeof(int32_t), st));
+    TMVB_CALL_HIP(c, hipMemsetAsync(d_held, 0, std::max<size_t>((size_t)n, 1) * sizeof(int32_t), st));
     hipcub::TransformInputIterator<int64_t, ho_widen, const int32_t*> wide((const int32_t*)d_counts, ho_widen());
     size_t b1 = 0, b2 = 0;
-    HO_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, b1, wide, d_cum, (int)(n + 1), st));
-    HO_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, b2, (const int32_t*)d_fo, d_po, (int)(n + 1), st));
+    TMVB_CALL_HIP(c, hipcub::DeviceScan::ExclusiveSum(nullptr, b1, wide, d_cum, (int)(n + 1), st));
+    TMVB_CALL_HIP(c, hipcub::DeviceScan::ExclusiveSum(nullptr, b2, (const int32_t*)d_fo, d_po, (int)(n + 1), st));
     char* d_scan;
     const size_t scan_bytes = std::max<size_t>(std::max(b1, b2), 16);
-    HO_TRY(pool.alloc(&d_scan, scan_bytes));
+    TMVB_CALL_TRY(c, c.alloc(&d_scan, scan_bytes));
 
     // Stage times: each pair of events brackets kernels and hipcub calls only; allocations, copies and memsets lie outside.
     // ---- draw
-    HO_HIP(hipEventRecord(pool.evs[0], st));
+    TMVB_CALL_HIP(c, hipEventRecord(c.ev(0), st));
     b1 = scan_bytes;
-    HO_HIP(hipcub::DeviceScan::ExclusiveSum((void*)d_scan, b1, wide, d_cum, (int)(n + 1), st));
+    TMVB_CALL_HIP(c, hipcub::DeviceScan::ExclusiveSum((void*)d_scan, b1, wide, d_cum, (int)(n + 1), st));
     hipLaunchKernelGGL(split_draw_kernel, dim3((unsigned)M), dim3(64), 0, st, doc_offset, seed, thr, (const int64_t*)d_ptr, (const int64_t*)d_cum, d_held);
-    HO_HIP(hipGetLastError());
-    HO_HIP(hipEventRecord(pool.evs[1], st));
+    TMVB_CALL_HIP(c, hipGetLastError());
+    TMVB_CALL_HIP(c, hipEventRecord(c.ev(1), st));
     // ---- compact
     const unsigned nb = (unsigned)((n + 256) / 256);
-    HO_HIP(hipEventRecord(pool.evs[2], st));
+    TMVB_CALL_HIP(c, hipEventRecord(c.ev(2), st));
     hipLaunchKernelGGL(split_flags_kernel, dim3(nb), dim3(256), 0, st, n, (const int32_t*)d_counts, (const int32_t*)d_held, d_fo, d_fh);
-    HO_HIP(hipGetLastError());
+    TMVB_CALL_HIP(c, hipGetLastError());
     b2 = scan_bytes;
-    HO_HIP(hipcub::DeviceScan::ExclusiveSum((void*)d_scan, b2, (const int32_t*)d_fo, d_po, (int)(n + 1), st));
+    TMVB_CALL_HIP(c, hipcub::DeviceScan::ExclusiveSum((void*)d_scan, b2, (const int32_t*)d_fo, d_po, (int)(n + 1), st));
     b2 = scan_bytes;
-    HO_HIP(hipcub::DeviceScan::ExclusiveSum((void*)d_scan, b2, (const int32_t*)d_fh, d_ph, (int)(n + 1), st));
+    TMVB_CALL_HIP(c, hipcub::DeviceScan::ExclusiveSum((void*)d_scan, b2, (const int32_t*)d_fh, d_ph, (int)(n + 1), st));
     hipLaunchKernelGGL(split_scatter_kernel, dim3(nb), dim3(256), 0, st, n, (const int32_t*)d_terms, (const int32_t*)d_counts, (const int32_t*)d_held,
                        (const int32_t*)d_po, (const int32_t*)d_ph, d_ot, d_oc, d_ht, d_hc);
     hipLaunchKernelGGL(split_ptr_kernel, dim3((unsigned)((M + 256) / 256)), dim3(256), 0, st, M, (const int64_t*)d_ptr, (const int32_t*)d_po, (const int32_t*)d_ph,
                        d_optr, d_hptr);
-    HO_HIP(hipGetLastError());
-    HO_HIP(hipEventRecord(pool.evs[3], st));
+    TMVB_CALL_HIP(c, hipGetLastError());
+    TMVB_CALL_HIP(c, hipEventRecord(c.ev(3), st));
 
     // ---- results
     out->M = M;
-    HO_TRY(ho_host(&out->obs_ptr, (size_t)M + 1)); HO_TRY(ho_host(&out->held_ptr, (size_t)M + 1));
-    HO_HIP(hipMemcpyAsync(out->obs_ptr, d_optr, ((size_t)M + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    HO_HIP(hipMemcpyAsync(out->held_ptr, d_hptr, ((size_t)M + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    HO_HIP(hipStreamSynchronize(st));
+    TMVB_CALL_TRY(c, tmvb_host_alloc("heldout", &out->obs_ptr, (size_t)M + 1));
+    TMVB_CALL_TRY(c, tmvb_host_alloc("heldout", &out->held_ptr, (size_t)M + 1));
+    TMVB_CALL_HIP(c, hipMemcpyAsync(out->obs_ptr, d_optr, ((size_t)M + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    TMVB_CALL_HIP(c, hipMemcpyAsync(out->held_ptr, d_hptr, ((size_t)M + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    TMVB_CALL_HIP(c, hipStreamSynchronize(st));
     out->nnz_obs = out->obs_ptr[M]; out->nnz_held = out->held_ptr[M];
-    HO_TRY(ho_host(&out->obs_terms, (size_t)out->nnz_obs)); HO_TRY(ho_host(&out->obs_counts, (size_t)out->nnz_obs));
-    HO_TRY(ho_host(&out->held_terms, (size_t)out->nnz_held)); HO_TRY(ho_host(&out->held_counts, (size_t)out->nnz_held));
+    TMVB_CALL_TRY(c, tmvb_host_alloc("heldout", &out->obs_terms, (size_t)out->nnz_obs));
+    TMVB_CALL_TRY(c, tmvb_host_alloc("heldout", &out->obs_counts, (size_t)out->nnz_obs));
+    TMVB_CALL_TRY(c, tmvb_host_alloc("heldout", &out->held_terms, (size_t)out->nnz_held));
+    TMVB_CALL_TRY(c, tmvb_host_alloc("heldout", &out->held_counts, (size_t)out->nnz_held));
     if (out->nnz_obs > 0) {
-        HO_HIP(hipMemcpyAsync(out->obs_terms, d_ot, (size_t)out->nnz_obs * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        HO_HIP(hipMemcpyAsync(out->obs_counts, d_oc, (size_t)out->nnz_obs * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        TMVB_CALL_HIP(c, hipMemcpyAsync(out->obs_terms, d_ot, (size_t)out->nnz_obs * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        TMVB_CALL_HIP(c, hipMemcpyAsync(out->obs_counts, d_oc, (size_t)out->nnz_obs * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     }
     if (out->nnz_held > 0) {
-        HO_HIP(hipMemcpyAsync(out->held_terms, d_ht, (size_t)out->nnz_held * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        HO_HIP(hipMemcpyAsync(out->held_counts, d_hc, (size_t)out->nnz_held * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        TMVB_CALL_HIP(c, hipMemcpyAsync(out->held_terms, d_ht, (size_t)out->nnz_held * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        TMVB_CALL_HIP(c, hipMemcpyAsync(out->held_counts, d_hc, (size_t)out->nnz_held * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     }
-    HO_HIP(hipStreamSynchronize(st));
+    TMVB_CALL_HIP(c, hipStreamSynchronize(st));
     for (int64_t j = 0; j < out->nnz_obs; j++) out->sum_obs += out->obs_counts[j];
     for (int64_t j = 0; j < out->nnz_held; j++) out->sum_held += out->held_counts[j];
-    HO_HIP(hipEventElapsedTime(&out->ms_draw, pool.evs[0], pool.evs[1]));
-    HO_HIP(hipEventElapsedTime(&out->ms_compact, pool.evs[2], pool.evs[3]));
+    TMVB_CALL_TRY(c, c.elapsed(&out->ms_draw, 0, 1));
+    TMVB_CALL_TRY(c, c.elapsed(&out->ms_compact, 2, 3));
+    guard.release();
     return TMVB_OK;
 }
-#undef HO_HIP
-#undef HO_TRY
 
 // lanes per nonzero: the smallest power of two that leaves a lane at most four 16-byte chunks of the row, at most a wave
 int ho_log_lanes(int K)
@@ -336,15 +265,11 @@ int ho_log_lanes(int K)
 int ho_loglik_run(tmvb_ctx* ctx, int32_t K, int64_t V, int64_t M, const double* theta, const double* beta, const int64_t* doc_ptr, const int32_t* terms,
                   const int32_t* counts, double a, double* ll, int64_t* tokens, int64_t* zero_prob_tokens, float* ms_kernel)
 {
-    TMVB_HIP(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    ho_pool pool;
-    int rc = pool.events(2);
-    if (rc != TMVB_OK) return rc;
     const int KP = tmvb_kpad(K), logL = ho_log_lanes(K);
     const int64_t n = doc_ptr[M];
-    // host staging: fp32 theta [M][KP], smoothed fp32 beta [V][KP], the two document lists
+    // host staging, declared in front of the call's scope: fp32 theta [M][KP], smoothed fp32 beta [V][KP], the two document lists, the read-back
     std::vector<float> h_theta((size_t)M * KP, 0.0f), h_beta((size_t)V * KP, 0.0f);
+    std::vector<long long> h_zero((size_t)M);
     const double denom = 1.0 + a * (double)V;
     for (int64_t d = 0; d < M; d++)
         for (int k = 0; k < K; k++) h_theta[(size_t)d * KP + k] = (float)theta[k + (int64_t)K * d];
@@ -358,43 +283,44 @@ int ho_loglik_run(tmvb_ctx* ctx, int32_t K, int64_t V, int64_t M, const double* 
     for (int64_t d = 0; d < M; d++)
         if (doc_ptr[d + 1] - doc_ptr[d] > short_max) h_docs[(size_t)(n_short + n_long++)] = (int32_t)d;
 
+    hipStream_t st = ctx->stream;
+    tmvb_call c("heldout", ctx->device, st);
+    TMVB_CALL_TRY(c, c.begin());
+    TMVB_CALL_TRY(c, c.events(2));
     float *d_theta, *d_beta;
     int64_t* d_ptr;
     int32_t *d_terms, *d_counts, *d_docs;
     double* d_ll;
     long long *d_tok, *d_zero;
-    if ((rc = pool.alloc(&d_theta, h_theta.size())) != TMVB_OK || (rc = pool.alloc(&d_beta, h_beta.size())) != TMVB_OK ||
-        (rc = pool.alloc(&d_ptr, (size_t)M + 1)) != TMVB_OK || (rc = pool.alloc(&d_terms, (size_t)n)) != TMVB_OK ||
-        (rc = pool.alloc(&d_counts, (size_t)n)) != TMVB_OK || (rc = pool.alloc(&d_docs, (size_t)M)) != TMVB_OK ||
-        (rc = pool.alloc(&d_ll, (size_t)M)) != TMVB_OK || (rc = pool.alloc(&d_tok, (size_t)M)) != TMVB_OK || (rc = pool.alloc(&d_zero, (size_t)M)) != TMVB_OK)
-        return rc;
-    TMVB_HIP(hipMemcpyAsync(d_theta, h_theta.data(), h_theta.size() * sizeof(float), hipMemcpyHostToDevice, st));
-    TMVB_HIP(hipMemcpyAsync(d_beta, h_beta.data(), h_beta.size() * sizeof(float), hipMemcpyHostToDevice, st));
-    TMVB_HIP(hipMemcpyAsync(d_ptr, doc_ptr, ((size_t)M + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
-    TMVB_HIP(hipMemcpyAsync(d_docs, h_docs.data(), (size_t)M * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    TMVB_CALL_TRY(c, c.alloc(&d_theta, h_theta.size())); TMVB_CALL_TRY(c, c.alloc(&d_beta, h_beta.size())); TMVB_CALL_TRY(c, c.alloc(&d_ptr, (size_t)M + 1));
+    TMVB_CALL_TRY(c, c.alloc(&d_terms, (size_t)n)); TMVB_CALL_TRY(c, c.alloc(&d_counts, (size_t)n)); TMVB_CALL_TRY(c, c.alloc(&d_docs, (size_t)M));
+    TMVB_CALL_TRY(c, c.alloc(&d_ll, (size_t)M)); TMVB_CALL_TRY(c, c.alloc(&d_tok, (size_t)M)); TMVB_CALL_TRY(c, c.alloc(&d_zero, (size_t)M));
+    TMVB_CALL_HIP(c, hipMemcpyAsync(d_theta, h_theta.data(), h_theta.size() * sizeof(float), hipMemcpyHostToDevice, st));
+    TMVB_CALL_HIP(c, hipMemcpyAsync(d_beta, h_beta.data(), h_beta.size() * sizeof(float), hipMemcpyHostToDevice, st));
+    TMVB_CALL_HIP(c, hipMemcpyAsync(d_ptr, doc_ptr, ((size_t)M + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    TMVB_CALL_HIP(c, hipMemcpyAsync(d_docs, h_docs.data(), (size_t)M * sizeof(int32_t), hipMemcpyHostToDevice, st));
     if (n > 0) {
-        TMVB_HIP(hipMemcpyAsync(d_terms, terms, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, st));
-        TMVB_HIP(hipMemcpyAsync(d_counts, counts, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        TMVB_CALL_HIP(c, hipMemcpyAsync(d_terms, terms, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        TMVB_CALL_HIP(c, hipMemcpyAsync(d_counts, counts, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, st));
     }
-    TMVB_HIP(hipEventRecord(pool.evs[0], st));
+    TMVB_CALL_HIP(c, hipEventRecord(c.ev(0), st));
     if (n_short > 0)
         hipLaunchKernelGGL(heldout_loglik_kernel<64>, dim3((unsigned)n_short), dim3(64), 0, st, (int)K, KP, logL, (const int32_t*)d_docs, (const float*)d_theta,
                            (const float*)d_beta, (const int64_t*)d_ptr, (const int32_t*)d_terms, (const int32_t*)d_counts, d_ll, d_tok, d_zero);
     if (n_long > 0)
         hipLaunchKernelGGL(heldout_loglik_kernel<256>, dim3((unsigned)n_long), dim3(256), 0, st, (int)K, KP, logL, (const int32_t*)d_docs + n_short,
                            (const float*)d_theta, (const float*)d_beta, (const int64_t*)d_ptr, (const int32_t*)d_terms, (const int32_t*)d_counts, d_ll, d_tok, d_zero);
-    TMVB_HIP(hipGetLastError());
-    TMVB_HIP(hipEventRecord(pool.evs[1], st));
-    std::vector<long long> h_zero((size_t)M);
+    TMVB_CALL_HIP(c, hipGetLastError());
+    TMVB_CALL_HIP(c, hipEventRecord(c.ev(1), st));
     static_assert(sizeof(long long) == sizeof(int64_t), "tokens travel as 64-bit integers");
-    TMVB_HIP(hipMemcpyAsync(ll, d_ll, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, st));
-    TMVB_HIP(hipMemcpyAsync(tokens, d_tok, (size_t)M * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    TMVB_HIP(hipMemcpyAsync(h_zero.data(), d_zero, (size_t)M * sizeof(long long), hipMemcpyDeviceToHost, st));
-    TMVB_HIP(hipStreamSynchronize(st));
+    TMVB_CALL_HIP(c, hipMemcpyAsync(ll, d_ll, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, st));
+    TMVB_CALL_HIP(c, hipMemcpyAsync(tokens, d_tok, (size_t)M * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    TMVB_CALL_HIP(c, hipMemcpyAsync(h_zero.data(), d_zero, (size_t)M * sizeof(long long), hipMemcpyDeviceToHost, st));
+    TMVB_CALL_HIP(c, hipStreamSynchronize(st));
     int64_t z = 0;
     for (int64_t d = 0; d < M; d++) z += h_zero[(size_t)d];
     *zero_prob_tokens = z;
-    if (ms_kernel) TMVB_HIP(hipEventElapsedTime(ms_kernel, pool.evs[0], pool.evs[1]));
+    if (ms_kernel) TMVB_CALL_TRY(c, c.elapsed(ms_kernel, 0, 1));
     return TMVB_OK;
 }
 }  // namespace
@@ -430,17 +356,7 @@ extern "C" int tmvb_heldout_loglik(tmvb_ctx* ctx, int32_t K, int64_t V, int64_t 
     TMVB_REQUIRE(theta && beta && ll && tokens && zero_prob_tokens, TMVB_EINVAL, "%s: NULL argument", fn);
     int rc = tmvb_check_host_csr(fn, M, V, doc_ptr, terms, counts, false);
     if (rc != TMVB_OK) return rc;
-    // isstochastic(beta, dims=2) (src/modelutils.jl:56) with gencorp's tolerance for the Float32-derived beta of a device model
-    std::vector<double> rows((size_t)K, 0.0);
-    bool ok = true;
-    for (int64_t v = 0; v < V && ok; v++)
-        for (int k = 0; k < K; k++) {
-            const double x = beta[k + (int64_t)K * v];
-            if (!(x >= 0.0) || !std::isfinite(x)) { ok = false; break; }
-            rows[k] += x;
-        }
-    for (int k = 0; k < K && ok; k++) ok = std::fabs(rows[k] - 1.0) <= 5e-4;
-    TMVB_REQUIRE(ok, TMVB_ESHAPE, "beta must be a right stochastic matrix.");
+    if ((rc = tmvb_check_stochastic_beta(K, V, beta)) != TMVB_OK) return rc;
     for (int64_t d = 0; d < M; d++) {
         double s = 0.0;
         bool good = true;

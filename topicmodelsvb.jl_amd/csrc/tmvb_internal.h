@@ -150,9 +150,10 @@ int tmvb_corpus_term_index(tmvb_corpus* c);
 int tmvb_comm_allreduce_group(tmvb_comm* const* comms, void* const* dev_ptrs, const int64_t* counts, int n, int32_t dtype);
 int tmvb_comm_allreduce_on(tmvb_comm* c, void* dev_ptr, int64_t count, int32_t dtype, hipStream_t on);
 int tmvb_corpus_reader_index(tmvb_corpus* c);
-// Host CSR arguments of the entry points that take a corpus without a handle (tmvb_heldout.hip; also tmvb_coherence.hip): the check_doc /
-// check_corp rules of tmvb_corpus_create, and "arguments first, then: no device, no result" for a NULL context.
+// Host checks of the entry points that work without a handle (tmvb_core.hip): the check_doc / check_corp rules of tmvb_corpus_create on a host CSR,
+// isstochastic(beta, dims=2) on a column-major K x V beta, and "arguments first, then: no device, no result" for a NULL context.
 int tmvb_check_host_csr(const char* fn, int64_t M, int64_t V, const int64_t* doc_ptr, const int32_t* terms, const int32_t* counts, bool doc_tokens_limit);
+int tmvb_check_stochastic_beta(int32_t K, int64_t V, const double* beta);
 int tmvb_check_ctx_or_device(const char* fn, tmvb_ctx* ctx);
 
 // EPSILON of the reference (src/utils.jl:3) = 2^-99, exactly representable in fp32.

@@ -26,6 +26,7 @@
 //             insertion; a partial list is left at its first entry that does not beat the threshold.  Skipped with one split.
 // No atomics on global memory (the append counter is LDS), no scratch: the 64 accumulator entries are walked by a fully unrolled loop.
 #include "tmvb_internal.h"
+#include "tmvb_call.h"
 
 #include <algorithm>
 #include <climits>
@@ -259,35 +260,6 @@ static __global__ __launch_bounds__(NB_WG) void nb_merge_kernel(int n, int split
 
 // ------------------------------------------------------------------------------------------------------------------ host
 namespace {
-struct nb_pool {                    // device allocations and events of one call
-    std::vector<void*> ptrs;
-    std::vector<hipEvent_t> evs;
-    ~nb_pool()
-    {
-        for (void* p : ptrs) (void)hipFree(p);
-        for (hipEvent_t e : evs) (void)hipEventDestroy(e);
-    }
-    template <typename T>
-    int alloc(T** p, size_t n)
-    {
-        *p = nullptr;
-        const size_t bytes = std::max<size_t>(n, 1) * sizeof(T);
-        const hipError_t e = hipMalloc((void**)p, bytes);
-        if (e != hipSuccess) { tmvb_set_error("topic_neighbors: hipMalloc(%zu bytes) failed: %s", bytes, hipGetErrorString(e)); return TMVB_ENOMEM; }
-        ptrs.push_back(*p);
-        return TMVB_OK;
-    }
-    int events(int n)
-    {
-        for (int i = 0; i < n; i++) {
-            hipEvent_t e;
-            TMVB_HIP(hipEventCreate(&e));
-            evs.push_back(e);
-        }
-        return TMVB_OK;
-    }
-};
-
 // the rows of one side, judged on the host
 int nb_check_rows(const char* fn, const char* side, int32_t K, int32_t metric, int64_t M, const double* x)
 {
@@ -333,48 +305,46 @@ int nb_run(tmvb_ctx* ctx, int32_t K, int32_t metric, int64_t Md, const double* x
     const int64_t tps = (ntiles + splits - 1) / splits;
     splits = (ntiles + tps - 1) / tps;                  // no empty split
 
-    TMVB_HIP(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    nb_pool pool;
-    int rc = pool.events(6);
-    if (rc != TMVB_OK) return rc;
+    tmvb_call c("topic_neighbors", ctx->device, st);
+    TMVB_CALL_TRY(c, c.begin());
+    TMVB_CALL_TRY(c, c.events(6));
     double *d_xd, *d_xq = nullptr;
     float *d_fd, *d_fq = nullptr, *d_ps, *d_os = nullptr;
     int32_t *d_pi, *d_oi = nullptr;
     const size_t out_n = (size_t)Mq * n;
-    if ((rc = pool.alloc(&d_xd, (size_t)Md * K)) != TMVB_OK || (rc = pool.alloc(&d_fd, (size_t)Md * kp)) != TMVB_OK ||
-        (rc = pool.alloc(&d_ps, (size_t)splits * out_n)) != TMVB_OK || (rc = pool.alloc(&d_pi, (size_t)splits * out_n)) != TMVB_OK)
-        return rc;
-    if (xq && ((rc = pool.alloc(&d_xq, (size_t)Mq * K)) != TMVB_OK || (rc = pool.alloc(&d_fq, (size_t)Mq * kp)) != TMVB_OK)) return rc;
-    if (splits > 1 && ((rc = pool.alloc(&d_os, out_n)) != TMVB_OK || (rc = pool.alloc(&d_oi, out_n)) != TMVB_OK)) return rc;
-    TMVB_HIP(hipMemcpyAsync(d_xd, xd, (size_t)Md * K * sizeof(double), hipMemcpyHostToDevice, st));
-    if (xq) TMVB_HIP(hipMemcpyAsync(d_xq, xq, (size_t)Mq * K * sizeof(double), hipMemcpyHostToDevice, st));
+    TMVB_CALL_TRY(c, c.alloc(&d_xd, (size_t)Md * K)); TMVB_CALL_TRY(c, c.alloc(&d_fd, (size_t)Md * kp));
+    TMVB_CALL_TRY(c, c.alloc(&d_ps, (size_t)splits * out_n)); TMVB_CALL_TRY(c, c.alloc(&d_pi, (size_t)splits * out_n));
+    if (xq) { TMVB_CALL_TRY(c, c.alloc(&d_xq, (size_t)Mq * K)); TMVB_CALL_TRY(c, c.alloc(&d_fq, (size_t)Mq * kp)); }
+    if (splits > 1) { TMVB_CALL_TRY(c, c.alloc(&d_os, out_n)); TMVB_CALL_TRY(c, c.alloc(&d_oi, out_n)); }
+    TMVB_CALL_HIP(c, hipMemcpyAsync(d_xd, xd, (size_t)Md * K * sizeof(double), hipMemcpyHostToDevice, st));
+    if (xq) TMVB_CALL_HIP(c, hipMemcpyAsync(d_xq, xq, (size_t)Mq * K * sizeof(double), hipMemcpyHostToDevice, st));
     const size_t lds = nb_scan_lds(kc, n);
-    if (lds > 48 * 1024) TMVB_HIP(hipFuncSetAttribute((const void*)nb_scan_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if (lds > 48 * 1024) TMVB_CALL_HIP(c, hipFuncSetAttribute((const void*)nb_scan_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
 
     // stage times: the events bracket the kernels only; allocations and copies lie outside
-    TMVB_HIP(hipEventRecord(pool.evs[0], st));
+    TMVB_CALL_HIP(c, hipEventRecord(c.ev(0), st));
     hipLaunchKernelGGL(nb_feature_kernel, dim3((unsigned)((Md + 3) / 4)), dim3(NB_WG), 0, st, (int)K, kp, (int)metric, Md, (const double*)d_xd, d_fd);
     if (xq) hipLaunchKernelGGL(nb_feature_kernel, dim3((unsigned)((Mq + 3) / 4)), dim3(NB_WG), 0, st, (int)K, kp, (int)metric, Mq, (const double*)d_xq, d_fq);
-    TMVB_HIP(hipGetLastError());
-    TMVB_HIP(hipEventRecord(pool.evs[1], st));
+    TMVB_CALL_HIP(c, hipGetLastError());
+    TMVB_CALL_HIP(c, hipEventRecord(c.ev(1), st));
     const float* fq = xq ? d_fq : d_fd + q0 * kp;
     const int64_t self0 = xq ? -((int64_t)1 << 40) : q0;
-    TMVB_HIP(hipEventRecord(pool.evs[2], st));
+    TMVB_CALL_HIP(c, hipEventRecord(c.ev(2), st));
     hipLaunchKernelGGL(nb_scan_kernel, dim3((unsigned)qtiles, (unsigned)splits), dim3(NB_WG), lds, st, kp, kc, (int)n, Mq, Md, self0, tps, fq, (const float*)d_fd,
                        d_ps, d_pi);
-    TMVB_HIP(hipGetLastError());
-    TMVB_HIP(hipEventRecord(pool.evs[3], st));
-    TMVB_HIP(hipEventRecord(pool.evs[4], st));
+    TMVB_CALL_HIP(c, hipGetLastError());
+    TMVB_CALL_HIP(c, hipEventRecord(c.ev(3), st));
+    TMVB_CALL_HIP(c, hipEventRecord(c.ev(4), st));
     if (splits > 1) {
         hipLaunchKernelGGL(nb_merge_kernel, dim3((unsigned)((Mq + 3) / 4)), dim3(NB_WG), 0, st, (int)n, (int)splits, Mq, (const float*)d_ps, (const int32_t*)d_pi, d_os,
                            d_oi);
-        TMVB_HIP(hipGetLastError());
+        TMVB_CALL_HIP(c, hipGetLastError());
     }
-    TMVB_HIP(hipEventRecord(pool.evs[5], st));
-    TMVB_HIP(hipMemcpyAsync(score, splits > 1 ? d_os : d_ps, out_n * sizeof(float), hipMemcpyDeviceToHost, st));
-    TMVB_HIP(hipMemcpyAsync(idx, splits > 1 ? d_oi : d_pi, out_n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    TMVB_HIP(hipStreamSynchronize(st));
+    TMVB_CALL_HIP(c, hipEventRecord(c.ev(5), st));
+    TMVB_CALL_HIP(c, hipMemcpyAsync(score, splits > 1 ? d_os : d_ps, out_n * sizeof(float), hipMemcpyDeviceToHost, st));
+    TMVB_CALL_HIP(c, hipMemcpyAsync(idx, splits > 1 ? d_oi : d_pi, out_n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    TMVB_CALL_HIP(c, hipStreamSynchronize(st));
     for (int64_t q = 0; q < Mq; q++) {                  // empty slots: idx = -1, score = -inf (the device's sentinel index is INT32_MAX)
         int32_t c = 0;
         for (int j = 0; j < n; j++) {
@@ -386,9 +356,9 @@ int nb_run(tmvb_ctx* ctx, int32_t K, int32_t metric, int64_t Md, const double* x
     }
     if (info) {
         info->splits = (int32_t)splits; info->kp = kp;
-        TMVB_HIP(hipEventElapsedTime(&info->ms_prep, pool.evs[0], pool.evs[1]));
-        TMVB_HIP(hipEventElapsedTime(&info->ms_scan, pool.evs[2], pool.evs[3]));
-        if (splits > 1) TMVB_HIP(hipEventElapsedTime(&info->ms_merge, pool.evs[4], pool.evs[5]));
+        TMVB_CALL_TRY(c, c.elapsed(&info->ms_prep, 0, 1));
+        TMVB_CALL_TRY(c, c.elapsed(&info->ms_scan, 2, 3));
+        if (splits > 1) TMVB_CALL_TRY(c, c.elapsed(&info->ms_merge, 4, 5));
     }
     return TMVB_OK;
 }

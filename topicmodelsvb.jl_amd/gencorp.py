@@ -16,9 +16,9 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import check, lib, P_dbl, P_i32, P_i64
+from ._lib import _copy, _handle, check, lib, P_dbl, P_i32, P_i64
 from .corpus import Document, PackedCorpus
-from .lda import DeviceContext
+from .lda import call_context
 
 
 class GenCorpResult(C.Structure):
@@ -29,13 +29,6 @@ class GenCorpResult(C.Structure):
                 ("ms_tables", C.c_float), ("ms_docs", C.c_float), ("ms_tokens", C.c_float), ("ms_condense", C.c_float)]
 
 
-def _copy(ptr, n, dt):
-    n = int(n)
-    if n == 0 or not ptr:
-        return np.zeros(0, dtype=dt)
-    return np.ctypeslib.as_array(ptr, shape=(n,)).astype(dt, copy=True)
-
-
 def gencorp_raw(ctx, K, V, beta, M, mean_C, alpha=None, mu=None, sigma=None, laplace_smooth=0.0, seed=0, doc_offset=0, diagnostics=False):
     """The ABI call.  alpha -> tmvb_lda_gencorp, (mu, sigma) -> tmvb_ctm_gencorp.  ctx: a DeviceContext, or None for a NULL context (the
     library then answers TMVB_ENODEVICE on a machine without a GPU).  Returns (status, dict): nothing raises here."""
@@ -44,7 +37,7 @@ def gencorp_raw(ctx, K, V, beta, M, mean_C, alpha=None, mu=None, sigma=None, lap
     f64 = lambda a: np.asfortranarray(np.asarray(a, dtype=np.float64))
     beta = f64(beta)
     out = GenCorpResult()
-    h = ctx.handle if ctx is not None else C.c_void_p(None)
+    h = _handle(ctx)
     tail = (C.c_int64(int(M)), C.c_int64(int(doc_offset)), C.c_double(mean_C), C.c_double(laplace_smooth),
             C.c_int64(np.uint64(int(seed) % 2 ** 64).astype(np.int64)), C.c_int32(1 if diagnostics else 0), C.byref(out))
     if alpha is not None:
@@ -87,14 +80,9 @@ def gencorp(model, M, laplace_smooth: float = 0.0, seed: int = 0, doc_offset: in
         raise ValueError("laplace_smooth parameter must be nonnegative.")
     fam = _family(model)
     # like the reference, a gpu model is read through its HOST fields (alpha / mu / sigma / beta as train! left them)
-    own = getattr(model, "ctx", None) is None
-    ctx = DeviceContext(device_id) if own else model.ctx
-    try:
+    with call_context(device_id, getattr(model, "ctx", None)) as ctx:
         rc, res = gencorp_raw(ctx, model.K, model.V, model.beta, M, float(np.mean(model.C)), laplace_smooth=float(laplace_smooth), seed=seed,
                               doc_offset=doc_offset, **fam)
-    finally:
-        if own:
-            ctx.close()
     check(rc)
     return PackedCorpus(res["doc_ptr"], res["terms"], res["counts"], model.V)
 

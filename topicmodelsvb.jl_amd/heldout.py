@@ -17,9 +17,9 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import CorpusError, TopicModelError, check, lib, P_dbl, P_i32, P_i64
+from ._lib import CorpusError, TopicModelError, _copy, _csr, _handle, check, lib, P_dbl, P_i32, P_i64
 from .corpus import PackedCorpus
-from .lda import DeviceContext, _packed
+from .lda import _packed, call_context
 
 
 class SplitResult(C.Structure):
@@ -51,21 +51,6 @@ class HeldoutResult:
 
     def __repr__(self):
         return f"HeldoutResult(M={len(self.ll)}, tokens={int(self.tokens.sum())}, zero_prob_tokens={self.zero_prob_tokens}, perplexity={self.perplexity:.6g})"
-
-
-def _copy(ptr, n, dt):
-    n = int(n)
-    if n == 0 or not ptr:
-        return np.zeros(0, dtype=dt)
-    return np.ctypeslib.as_array(ptr, shape=(n,)).astype(dt, copy=True)
-
-
-def _handle(ctx):
-    return ctx.handle if ctx is not None else C.c_void_p(None)
-
-
-def _csr(doc_ptr, terms, counts):
-    return (np.ascontiguousarray(doc_ptr, dtype=np.int64), np.ascontiguousarray(terms, dtype=np.int32), np.ascontiguousarray(counts, dtype=np.int32))
 
 
 def split_corpus_raw(ctx, M, V, doc_ptr, terms, counts, frac=0.5, seed=0, doc_offset=0):
@@ -116,11 +101,8 @@ def split_corpus(corp, frac: float = 0.5, seed: int = 0, doc_offset: int = 0, de
     `frac`, by the draw rule above.  Both sides keep M and V, entries whose count became 0 are dropped, a document may be empty on either
     side, observed + heldout is the input.  Readers / ratings do not travel."""
     pc = _packed(corp)
-    ctx = DeviceContext(device_id)
-    try:
+    with call_context(device_id) as ctx:
         rc, res = split_corpus_raw(ctx, pc.M, pc.V, pc.doc_ptr, pc.terms, pc.counts, float(frac), seed, doc_offset)
-    finally:
-        ctx.close()
     check(rc)
     return (PackedCorpus(res["obs_ptr"], res["obs_terms"], res["obs_counts"], pc.V),
             PackedCorpus(res["held_ptr"], res["held_terms"], res["held_counts"], pc.V))
@@ -167,11 +149,8 @@ def heldout_loglik(model, observed, heldout, iter: int = 10, tol=None, niter: in
     if not laplace_smooth >= 0:
         raise ValueError("laplace_smooth parameter must be nonnegative.")
     theta = predicted_theta(model, obs, iter, tol, niter, ntol, device_id)
-    ctx = DeviceContext(device_id)
-    try:
+    with call_context(device_id) as ctx:
         rc, res = heldout_loglik_raw(ctx, model.K, model.V, theta, model.beta, held, float(laplace_smooth))
-    finally:
-        ctx.close()
     check(rc)
     res.theta = theta
     return res

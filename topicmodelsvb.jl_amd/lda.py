@@ -15,6 +15,7 @@ All compute goes through libtmvb_hip.so; there is no CPU fallback in this module
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import math
 
@@ -129,6 +130,20 @@ class DeviceContext:
             self.close()
         except Exception:
             pass
+
+
+@contextlib.contextmanager
+def call_context(device_id: int = 0, ctx=None):
+    """A DeviceContext for the length of one call of a stateless entry point, closed on the way out; a model's own `ctx` is handed
+    through and stays open."""
+    own = ctx is None
+    if own:
+        ctx = DeviceContext(device_id)
+    try:
+        yield ctx
+    finally:
+        if own:
+            ctx.close()
 
 
 class TimingEvent:

@@ -15,8 +15,8 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import CorpusError, TopicModelError, check, lib, P_dbl, P_i32
-from .lda import DeviceContext
+from ._lib import CorpusError, TopicModelError, _handle, check, lib, P_dbl, P_i32
+from .lda import call_context
 
 DOT, HELLINGER, COSINE = 0, 1, 2        # TMVB_NB_* (include/tmvb.h)
 METRICS = {"dot": DOT, "hellinger": HELLINGER, "cosine": COSINE}
@@ -52,10 +52,6 @@ class NeighborsResult:
 
     def __repr__(self):
         return f"NeighborsResult(Mq={self.idx.shape[0]}, n={self.idx.shape[1]}, metric={self.metric!r})"
-
-
-def _handle(ctx):
-    return ctx.handle if ctx is not None else C.c_void_p(None)
 
 
 def neighbors_raw(ctx, K, metric, xd, xq=None, q0=0, n=10, splits=0, Mq=None):
@@ -131,8 +127,7 @@ def docsim(model, docs=None, topn: int = 10, metric: str = "hellinger", queries=
             raise CorpusError("document index outside corpus range.")
     contiguous = bool(np.all(np.diff(sel) == 1))
     n = int(topn)
-    ctx = DeviceContext(device_id)
-    try:
+    with call_context(device_id) as ctx:
         if queries is not None:
             rc, res = neighbors_raw(ctx, K, METRICS[metric], xd, src[:, sel], 0, n)
         elif contiguous:
@@ -152,8 +147,6 @@ def docsim(model, docs=None, topn: int = 10, metric: str = "hellinger", queries=
                 res = {"idx": np.concatenate([p["idx"] for p in parts]), "score": np.concatenate([p["score"] for p in parts]),
                        "count": np.concatenate([p["count"] for p in parts]), "splits": parts[0]["splits"],
                        "ms": {k: sum(p["ms"][k] for p in parts) for k in ("prep", "scan", "merge")}}
-    finally:
-        ctx.close()
     check(rc)
     return NeighborsResult(res["idx"], res["score"], res["count"], metric, res["ms"], res["splits"])
 
