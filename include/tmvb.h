@@ -641,6 +641,74 @@ typedef struct { int32_t splits, kp; float ms_prep, ms_scan, ms_merge; } tmvb_ne
 int tmvb_topic_neighbors(tmvb_ctx* ctx, int32_t K, int32_t metric, int64_t Md, const double* xd, int64_t Mq, const double* xq, int64_t q0,
                          int32_t n, int32_t splits, int32_t* idx, float* score, int32_t* count, tmvb_neighbors_info_t* info);
 
+/* ============================== held-out recommendation metrics for CTPF: reader split, fused ranks, metrics ==============================
+ * Hold out part of the (document, reader) entries, train on the rest, ask where each held-out document lands in its user's ranking (the
+ * reference stops at showdrecs / showurecs).
+ *
+ * tmvb_readers_split: HOST ONLY, touches no device.  The reader CSR of tmvb_corpus_create (rdr_ptr[M+1], readers[nR] in [0, U), ratings[nR])
+ * -> two reader CSRs over the same M, observed and held out.  The order inside a document is kept and obs + held reproduces the input exactly.
+ * Draw rule, Philox4x32-10 with key = seed (csrc/tmvb_philox.h: tmvb_rng).  mode TMVB_RSPLIT_ENTRY (in-matrix): entry j of document d takes
+ * word x[j & 3] of counter (doc_offset + d, stage TMVB_RNG_RSPLIT_ENTRY = 6, draw j >> 2) and is HELD OUT iff word < floor(frac * 2^32) (as
+ * 64-bit integers: frac = 0 holds out nothing, frac = 1 everything).  mode TMVB_RSPLIT_DOCUMENT (out-of-matrix / cold start): document d takes
+ * word x[0] of counter (doc_offset + d, stage TMVB_RNG_RSPLIT_DOCUMENT = 7, draw 0); if held, all of its readers go to the held-out side.
+ * Documents [d0, d0 + m) of a large call equal the call (M = m, doc_offset = d0).
+ * Errors: out == NULL, frac outside [0, 1] or not finite, doc_offset < 0, an unknown mode, M <= 0, U <= 0, a NULL argument -> TMVB_EINVAL;
+ * rdr_ptr not non-decreasing from 0, a reader outside [0, U), a rating < 1 -> TMVB_ESHAPE.  The arrays of *out are allocated by the
+ * library: tmvb_rsplit_free.
+ *
+ * tmvb_score_ranks: K in [1, 1024]; database xd, column-major K x Md fp64, queries xq, K x Mq fp64, both on the HOST; per query two lists of
+ * 0-based database ids in CSR form, exclusions (excl_ptr[Mq+1], excl_idx) and targets (tgt_ptr[Mq+1], tgt_idx), each strictly ascending
+ * within a query and the two disjoint.  Outputs: rank[nT] (nT = tgt_ptr[Mq], in the order of tgt_idx), n_cand[Mq] = Md - |excl(q)|,
+ * score[nT] (fp32, or NULL).
+ * Features: the rows as given, each value rounded ONCE to fp32, padded to kp exactly as in tmvb_topic_neighbors (TMVB_NB_DOT).
+ * Score: s(q, e) is the fp32 fmaf chain over k = 0 .. K - 1 in ascending order starting from 0 -- what v_mfma_f32_32x32x2_f32 computes when
+ * the K loop feeds its accumulator.
+ * Order: the reference's reverse(sortperm(.)): e comes BEFORE t iff s_e > s_t, or s_e == s_t and e > t -- descending index on ties, NOT the
+ * order of tmvb_topic_neighbors.
+ * Rank: for target t of query q, rank = #{ e in [0, Md) : e not in excl(q), e != t, e before t }.  The other targets of q are candidates like
+ * any other row.  With X = gimel / dalet + zayin / het and Y = he / vav of a CTPF state, users as queries and their observed libraries as
+ * exclusions, rank is the 0-based position of t in urecs[u] of tmvb_ctpf_recommend (up to that unit's own rounding of the scores).
+ * Purity: the result is a pure function of the inputs -- independent of `splits` (0 = the library's choice, > 0 forces that many database
+ * splits, as in tmvb_topic_neighbors), of tile sizes, of the number of target slots in LDS and of the order in which workgroups finish; two
+ * calls give the same bits; queries [a, b) of a call equal the call on that slice.
+ * Device path: a feature kernel (the layout of tmvb_topic_neighbors); a pair kernel -- the score of every listed (query, id) pair, targets
+ * and exclusions alike: one wave takes 32 pairs, feeds the same MFMA the same operand values in the same k order and keeps the diagonal of its
+ * 32 x 32 tile, so a pair's score has the same bits here as in the scan --, followed by a sort of each query's targets; a scan kernel -- the
+ * tile loop of tmvb_topic_neighbors (a workgroup owns 128 queries and one database split) whose epilogue, instead of storing, counts for every
+ * target of a query the rows that come before it (ballot and popcount per 32 rows, integer adds in LDS, then one global integer add per
+ * target and split; a tile with more targets than LDS slots runs in passes) --; a fix kernel: rank = count - #{o in excl(q) : o before t},
+ * a loop over the query's excluded scores, which keeps every membership test out of the scan.
+ * info (or NULL): splits, kp, ms_prep / ms_pairs / ms_scan / ms_fix = device time of the stages (HIP events around the kernels only).
+ * Errors, judged before the device is touched: K outside [1, 1024], Md <= 0, Mq <= 0, Md >= 2^31, splits < 0 or > Md, a NULL argument,
+ * 2^31 - 1 or more listed ids -> TMVB_EINVAL; a list pointer not non-decreasing from 0, a non-finite entry, ids out of range, not strictly
+ * ascending or shared between the two lists of a query -> TMVB_ESHAPE; then ctx == NULL without a visible device -> TMVB_ENODEVICE (there
+ * is no CPU path).
+ *
+ * tmvb_rank_metrics: HOST ONLY, fp64 arithmetic on the integers.  Per query with T >= 1 targets and for each cut-off N of Ns[nN]:
+ *   hits@N = #{rank < N};  recall[q][a] = hits / T;  precision[q][a] = hits / N;
+ *   ndcg[q][a] = sum_{rank < N} 1 / log2(rank + 2)  /  sum_{i < min(T, N)} 1 / log2(i + 2);
+ *   mrr[q] = 1 / (min rank + 1);  pct_rank[q] = mean rank / max(n_cand[q] - 1, 1).
+ * A query without targets gets NaN everywhere and is left out of the means.  mean[3 nN + 2]: the means over the queries with targets of
+ * recall@Ns, precision@Ns, ndcg@Ns, mrr, pct_rank, in that order (NaN if there is no such query); counts[2]: the number of such queries
+ * and the number of targets.  Errors: Mq <= 0, nN < 1, an N < 1, a NULL argument -> TMVB_EINVAL; tgt_ptr not non-decreasing from 0, a rank
+ * outside [0, n_cand[q]) -> TMVB_ESHAPE. */
+#define TMVB_RSPLIT_ENTRY 0
+#define TMVB_RSPLIT_DOCUMENT 1
+typedef struct {
+    int64_t M, n_obs, n_held;
+    int64_t* obs_ptr;  int32_t* obs_readers;  int32_t* obs_ratings;      /* [M+1], [n_obs], [n_obs] */
+    int64_t* held_ptr; int32_t* held_readers; int32_t* held_ratings;     /* [M+1], [n_held], [n_held] */
+} tmvb_rsplit_t;
+int  tmvb_readers_split(int64_t M, int64_t U, const int64_t* rdr_ptr, const int32_t* readers, const int32_t* ratings, double frac, int64_t seed,
+                        int64_t doc_offset, int32_t mode, tmvb_rsplit_t* out);
+void tmvb_rsplit_free(tmvb_rsplit_t* s);
+typedef struct { int32_t splits, kp; float ms_prep, ms_pairs, ms_scan, ms_fix; } tmvb_recranks_info_t;
+int tmvb_score_ranks(tmvb_ctx* ctx, int32_t K, int64_t Md, const double* xd, int64_t Mq, const double* xq, const int64_t* excl_ptr,
+                     const int32_t* excl_idx, const int64_t* tgt_ptr, const int32_t* tgt_idx, int32_t splits, int32_t* rank, int32_t* n_cand,
+                     float* score, tmvb_recranks_info_t* info);
+int tmvb_rank_metrics(int64_t Mq, const int64_t* tgt_ptr, const int32_t* rank, const int32_t* n_cand, int32_t nN, const int32_t* Ns, double* recall,
+                      double* precision, double* ndcg, double* mrr, double* pct_rank, double* mean, int64_t* counts);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,5 +1,5 @@
 #!/bin/bash
-# The deliberately WRONG libraries of tests/test_mutants_gpu.py, tests/test_heldout_mutant_gpu.py, tests/test_coherence_mutant_gpu.py and tests/test_neighbors_mutant_gpu.py (negative controls of the parity suite), each = the shipped objects with one
+# The deliberately WRONG libraries of tests/test_mutants_gpu.py, tests/test_heldout_mutant_gpu.py, tests/test_coherence_mutant_gpu.py, tests/test_neighbors_mutant_gpu.py and tests/test_recranks_mutant_gpu.py (negative controls of the parity suite), each = the shipped objects with one
 # translation unit recompiled under a -DTMVB_MUTANT_* flag (csrc/tmvb_internal.h lists them):
 #   topicmodelsvb.jl_amd/libtmvb_hip_mut_lda_eps.so     epsilon dropped from LDA's phi / gamma            (src/LDA.jl:152, :145)
 #   topicmodelsvb.jl_amd/libtmvb_hip_mut_ctpf_bet.so    log bet for log vav in CTPF's xi                   (src/CTPF.jl:336 vs src/gpuCTPF.jl:624)
@@ -13,6 +13,7 @@
 #   topicmodelsvb.jl_amd/libtmvb_hip_mut_heldout_tail.so   held-out scoring kernel without the last partial 16-byte chunk of a beta row (tests/test_heldout_mutant_gpu.py)
 #   topicmodelsvb.jl_amd/libtmvb_hip_mut_coherence_tail.so  pair kernel of the co-document counts without the last partial 64-document word (tests/test_coherence_mutant_gpu.py)
 #   topicmodelsvb.jl_amd/libtmvb_hip_mut_neighbors_tail.so  scan kernel of the nearest-document search without the last partial database tile (tests/test_neighbors_mutant_gpu.py)
+#   topicmodelsvb.jl_amd/libtmvb_hip_mut_recranks_tail.so  scan kernel of the held-out ranks without the last partial database tile (tests/test_recranks_mutant_gpu.py)
 # Needs the shipped build first (python -c "import __graft_entry__ as g; g.build()").  In parallel, but two builds of one translation unit never in the same batch (they share a temporary): tmvb_ctm.hip has two
 # variants, tmvb_lda.hip three (tmvb_core.hip one: mut_index_repeat), hence three batches, the third holding mut_lda_stale_parts alone.  About 4 minutes for the first two batches plus one more build of tmvb_lda.hip.
 cd "$(dirname "$0")/.." || exit 1
@@ -30,5 +31,6 @@ wait
 tools/build_variant.sh mut_lda_stale_parts tmvb_lda.hip -DTMVB_MUTANT_LDA_STALE_PARTS=1 &
 tools/build_variant.sh mut_coherence_tail tmvb_coherence.hip -DTMVB_MUTANT_CODF_DROP_TAIL=1 &
 tools/build_variant.sh mut_neighbors_tail tmvb_neighbors.hip -DTMVB_MUTANT_NB_DROP_TAIL=1 &
+tools/build_variant.sh mut_recranks_tail tmvb_recranks.hip -DTMVB_MUTANT_RK_DROP_TAIL=1 &
 wait
 ls -la topicmodelsvb.jl_amd/libtmvb_hip_mut_*.so

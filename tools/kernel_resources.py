@@ -40,6 +40,8 @@ BENCHED = {
     "codf_bitset_kernel": 0, "codf_pairs_kernel": 0,
     # nearest documents in topic space (tools/neighbors_bench.py): features, the fused MFMA scan / top-n, the merge of the splits' lists
     "nb_feature_kernel": 0, "nb_scan_kernel": 0, "nb_merge_kernel": 0,
+    # held-out recommendation ranks (tools/recs_eval_bench.py): features, pair scores, target sort, the fused MFMA scan / count, the exclusion fix
+    "rk_feature_kernel": 0, "rk_pairs_kernel": 0, "rk_sort_kernel": 0, "rk_scan_kernel": 0, "rk_fix_kernel": 0,
 }
 
 

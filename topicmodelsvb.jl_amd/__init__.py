@@ -18,6 +18,8 @@ from .gencorp import gencorp, gencorp_raw, gendoc
 from .heldout import HeldoutResult, heldout_loglik, heldout_loglik_raw, perplexity, split_corpus, split_corpus_raw
 from .coherence import CoherenceResult, coherence, coherence_from_counts, coherence_from_counts_raw, codocfreq_raw
 from .neighbors import NeighborsResult, docsim, neighbors_raw, topic_proportions
+from .recs_eval import (HeldReaders, RecEvalResult, rank_metrics, rank_metrics_raw, rec_eval, rec_quality, rec_ranks_raw, split_readers,
+                        split_readers_raw)
 
 __all__ = ["CorpusError", "DocumentError", "EngineError", "TopicModelError", "build", "exported_symbols", "lib", "LIB_PATH",
            "Corpus", "Document", "PackedCorpus", "check_corp", "check_doc", "dirichlet_rows", "readcorp", "readcorp_packed", "writecorp",
@@ -26,4 +28,5 @@ __all__ = ["CorpusError", "DocumentError", "EngineError", "TopicModelError", "bu
            "gencorp", "gencorp_raw", "gendoc",
            "HeldoutResult", "heldout_loglik", "heldout_loglik_raw", "perplexity", "split_corpus", "split_corpus_raw",
            "CoherenceResult", "coherence", "coherence_from_counts", "coherence_from_counts_raw", "codocfreq_raw",
-           "NeighborsResult", "docsim", "neighbors_raw", "topic_proportions"]
+           "NeighborsResult", "docsim", "neighbors_raw", "topic_proportions",
+           "HeldReaders", "RecEvalResult", "rank_metrics", "rank_metrics_raw", "rec_eval", "rec_quality", "rec_ranks_raw", "split_readers", "split_readers_raw"]

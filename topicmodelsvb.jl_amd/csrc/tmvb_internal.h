@@ -178,6 +178,7 @@ int tmvb_check_ctx_or_device(const char* fn, tmvb_ctx* ctx);
 //                                   (M not a multiple of 64); tests/test_coherence_mutant_gpu.py
 //   TMVB_MUTANT_NB_DROP_TAIL        the scan kernel of the nearest-document search (tmvb_neighbors.hip) skips the last, partial database tile (Md not a multiple of
 //                                   TMVB_NB_TILE_DB); tests/test_neighbors_mutant_gpu.py
+//   TMVB_MUTANT_RK_DROP_TAIL        the scan kernel of the held-out ranks (tmvb_recranks.hip) skips the last, partial database tile; tests/test_recranks_mutant_gpu.py
 #ifdef TMVB_MUTANT_FLDA_H_NO_GUARD
 #define TMVB_FLDA_H_GUARD(cond) true
 #else

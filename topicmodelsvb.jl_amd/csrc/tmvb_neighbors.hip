@@ -27,27 +27,17 @@
 // No atomics on global memory (the append counter is LDS), no scratch: the 64 accumulator entries are walked by a fully unrolled loop.
 #include "tmvb_internal.h"
 #include "tmvb_call.h"
+#include "tmvb_nbtile.h"
 
 #include <algorithm>
 #include <climits>
 #include <cstring>
 #include <limits>
 
-#define NB_MAX_K 1024
-#define NB_WG 256
-#define NB_QT 128                   // queries per workgroup
-#define NB_TD TMVB_NB_TILE_DB       // database rows per tile
-#define NB_KC_ONE 64                // kp up to this: one K-chunk, the query tile stays resident
-#define NB_KC 32                    // else chunks of this many floats
 #define NB_CAND 1024                // survivors buffered per round
-static_assert(NB_TD == 128 && NB_QT == 128, "a workgroup is 2 x 2 waves of 64 x 64");
-
-typedef float nb_f32x16 __attribute__((ext_vector_type(16)));
 
 // the total order: (s, i) comes before (t, j)
 __device__ __forceinline__ bool nb_before(float s, int i, float t, int j) { return s > t || (s == t && i < j); }
-
-__host__ __device__ __forceinline__ int nb_perm(int k) { return (k & ~3) | ((k & 1) << 1) | ((k >> 1) & 1); }
 
 // ------------------------------------------------------------------------------------------------------------------ features
 // x: column-major K x M fp64 (row r = x[K r ..]); f: [M][kp].  One wave per row.
@@ -56,40 +46,10 @@ static __global__ __launch_bounds__(NB_WG) void nb_feature_kernel(int K, int kp,
     const int lane = threadIdx.x & 63;
     const int64_t r = (int64_t)blockIdx.x * (NB_WG / 64) + (threadIdx.x >> 6);
     if (r >= M) return;                                 // wave-uniform
-    const double* xr = x + r * K;
-    double inv = 1.0;
-    if (metric == TMVB_NB_COSINE) {
-        double s = 0.0;
-        for (int k = lane; k < K; k += 64) s = fma(xr[k], xr[k], s);
-        inv = sqrt(wave_sum_d(s));
-    }
-    for (int p = lane; p < kp; p += 64) {
-        const int k = nb_perm(p);
-        double v = 0.0;
-        if (k < K) {
-            v = xr[k];
-            if (metric == TMVB_NB_HELLINGER) v = sqrt(v);
-            else if (metric == TMVB_NB_COSINE) v = v / inv;
-        }
-        f[r * kp + p] = (float)v;
-    }
+    nb_feature_row(K, kp, metric, x + r * K, f + r * kp, lane);
 }
 
 // ------------------------------------------------------------------------------------------------------------------ scan
-// 128 rows [row0, row0 + 128) x floats [k0, k0 + kc) of F[rows][kp] into s[128][S], S = kc + 2; rows at or past `rows` are zero
-__device__ __forceinline__ void nb_stage(float* __restrict__ s, int S, const float* __restrict__ F, int64_t row0, int64_t rows, int kp, int k0, int kc)
-{
-    const int upr = kc >> 2;                            // 16-byte units per row
-    for (int u = threadIdx.x; u < 128 * upr; u += NB_WG) {
-        const int row = u / upr, c = u - row * upr;
-        float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        if (row0 + row < rows) v = *reinterpret_cast<const float4*>(F + (row0 + row) * kp + k0 + 4 * c);
-        float2* d = reinterpret_cast<float2*>(s + row * S + 4 * c);
-        d[0] = make_float2(v.x, v.y);
-        d[1] = make_float2(v.z, v.w);
-    }
-}
-
 // one wave, lane j = slot j of list[n] (sorted, LDS): insert (cs, ci) if it is among the n best; the threshold follows slot n - 1
 __device__ __forceinline__ void nb_insert(float2* list, int n, float cs, int ci, float2* thr, int lane)
 {
@@ -145,33 +105,7 @@ static __global__ __launch_bounds__(NB_WG) void nb_scan_kernel(int kp, int kc_ma
     for (int64_t t = t_begin; t < t_end; t++) {
         const int64_t e0 = t * NB_TD;
         nb_f32x16 acc[2][2];
-#pragma unroll
-        for (int a = 0; a < 2; a++)
-#pragma unroll
-            for (int b = 0; b < 2; b++)
-#pragma unroll
-                for (int r = 0; r < 16; r++) acc[a][b][r] = 0.0f;
-        for (int k0 = 0; k0 < kp; k0 += kc_max) {
-            const int kc = min(kc_max, kp - k0);
-            __syncthreads();                                             // the previous chunk / tile has been read
-            if (!one_chunk) nb_stage(sA, S, Fq, qt0, Mq, kp, k0, kc);
-            nb_stage(sB, S, Fd, e0, Md, kp, k0, kc);
-            __syncthreads();
-            const float* pa = sA + (64 * wq + l31) * S + 2 * half;
-            const float* pb = sB + (64 * wd + l31) * S + 2 * half;
-            for (int kk = 0; kk < kc; kk += 4) {
-                const float2 a0 = *reinterpret_cast<const float2*>(pa + kk), a1 = *reinterpret_cast<const float2*>(pa + 32 * S + kk);
-                const float2 b0 = *reinterpret_cast<const float2*>(pb + kk), b1 = *reinterpret_cast<const float2*>(pb + 32 * S + kk);
-                acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.x, b0.x, acc[0][0], 0, 0, 0);
-                acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.x, b1.x, acc[0][1], 0, 0, 0);
-                acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.x, b0.x, acc[1][0], 0, 0, 0);
-                acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.x, b1.x, acc[1][1], 0, 0, 0);
-                acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.y, b0.y, acc[0][0], 0, 0, 0);
-                acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.y, b1.y, acc[0][1], 0, 0, 0);
-                acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.y, b0.y, acc[1][0], 0, 0, 0);
-                acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.y, b1.y, acc[1][1], 0, 0, 0);
-            }
-        }
+        nb_tile_scores(acc, sA, sB, S, kp, kc_max, one_chunk, Fq, qt0, Mq, Fd, e0, Md, wq, wd, l31, half);
         // ---- epilogue.  C/D layout: column (database row) = lane & 31, row (query) = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
         unsigned long long pend = 0ull;
 #pragma unroll

@@ -32,7 +32,9 @@ TMVB_HD inline tmvb_philox4 tmvb_philox4x32_10_raw(uint32_t c0, uint32_t c1, uin
 
 // The stages of the generative process: one counter sub-space each (counter word 2; the topic index of a per-topic draw rides in its upper bits).
 // TMVB_RNG_SPLIT is the held-out token split (tmvb_heldout.hip): draw index = Philox block of a document's token occurrences.
-enum : uint32_t { TMVB_RNG_POISSON = 0, TMVB_RNG_GAMMA = 1, TMVB_RNG_BOOST = 2, TMVB_RNG_NORMAL = 3, TMVB_RNG_TOKEN = 4, TMVB_RNG_SPLIT = 5 };
+// TMVB_RNG_RSPLIT_ENTRY / _DOCUMENT are the split of the reader lists (tmvb_recranks.hip): draw index = Philox block of a document's reader entries / 0.
+enum : uint32_t { TMVB_RNG_POISSON = 0, TMVB_RNG_GAMMA = 1, TMVB_RNG_BOOST = 2, TMVB_RNG_NORMAL = 3, TMVB_RNG_TOKEN = 4, TMVB_RNG_SPLIT = 5,
+                  TMVB_RNG_RSPLIT_ENTRY = 6, TMVB_RNG_RSPLIT_DOCUMENT = 7 };
 
 // random bits of (seed, global document index, stage [, topic], draw index)
 TMVB_HD inline tmvb_philox4 tmvb_rng(uint64_t seed, uint64_t doc, uint32_t stage, uint32_t topic, uint32_t draw)

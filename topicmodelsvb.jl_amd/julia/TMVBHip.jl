@@ -1067,3 +1067,86 @@ function docsim(model::TopicModel; docs::AbstractUnitRange{<:Integer}=1:0, topn:
 	return (idx=Int.(idx) .+ 1, score=score, distance=distance, count=Int.(count),
 			ms=(prep=info.ms_prep, scan=info.ms_scan, merge=info.ms_merge), splits=Int(info.splits))
 end
+
+# ---- held-out recommendation metrics for CTPF (include/tmvb.h: tmvb_readers_split, tmvb_score_ranks, tmvb_rank_metrics) -------------------
+# Hold out part of the (document, reader) entries, train on the rest, ask where each held-out document lands in its user's ranking.  The rank of
+# a held-out pair is a count -- how many candidates come before it under reverse(sortperm(.)) -- taken in the epilogue of the f32-MFMA score GEMM
+# on the device; the split and the metrics are host code of the library.
+
+"tmvb_rsplit_t (include/tmvb.h), field for field."
+mutable struct TmvbReaderSplit
+	M::Int64; n_obs::Int64; n_held::Int64
+	obs_ptr::Ptr{Int64}; obs_readers::Ptr{Int32}; obs_ratings::Ptr{Int32}
+	held_ptr::Ptr{Int64}; held_readers::Ptr{Int32}; held_ratings::Ptr{Int32}
+	TmvbReaderSplit() = new(0, 0, 0, C_NULL, C_NULL, C_NULL, C_NULL, C_NULL, C_NULL)
+end
+
+"tmvb_recranks_info_t (include/tmvb.h), field for field."
+mutable struct TmvbRecRanksInfo
+	splits::Int32; kp::Int32
+	ms_prep::Float32; ms_pairs::Float32; ms_scan::Float32; ms_fix::Float32
+	TmvbRecRanksInfo() = new(0, 0, 0f0, 0f0, 0f0, 0f0)
+end
+
+const RSPLIT_MODES = Dict(:entry => 0, :document => 1)
+
+"""
+(obs, held): the reader CSR (rdr_ptr 0-based offsets, readers 0-based, ratings) split into an observed and a held-out CSR over the same documents,
+each a named tuple (ptr, readers, ratings).  mode = :entry holds every entry out with probability frac, :document every document with all of its
+readers.  The same seed gives the same split; doc_offset reproduces a slice of a larger call.
+"""
+function split_readers(rdr_ptr::Vector{Int64}, readers::Vector{Int32}, ratings::Vector{Int32}, U::Integer; frac::Real=0.2, seed::Integer=0,
+		doc_offset::Integer=0, mode::Symbol=:entry)
+	haskey(RSPLIT_MODES, mode)			|| throw(ArgumentError("mode must be :entry or :document."))
+	M = length(rdr_ptr) - 1
+	out = TmvbReaderSplit()
+	GC.@preserve out rdr_ptr readers ratings begin
+		rc = ccall((:tmvb_readers_split, LIBTMVB), Cint,
+			(Int64, Int64, Ptr{Int64}, Ptr{Int32}, Ptr{Int32}, Float64, Int64, Int64, Int32, Ptr{Cvoid}),
+			M, U, rdr_ptr, readers, ratings, frac, seed, doc_offset, RSPLIT_MODES[mode], pointer_from_objref(out))
+		tmvb_check(rc)
+		side(p, r, a, n) = (ptr=copy(unsafe_wrap(Array, p, M + 1)), readers=copy(unsafe_wrap(Array, r, n)), ratings=copy(unsafe_wrap(Array, a, n)))
+		obs = side(out.obs_ptr, out.obs_readers, out.obs_ratings, out.n_obs)
+		held = side(out.held_ptr, out.held_readers, out.held_ratings, out.n_held)
+		ccall((:tmvb_rsplit_free, LIBTMVB), Cvoid, (Ptr{Cvoid},), pointer_from_objref(out))
+		return obs, held
+	end
+end
+
+"""
+(rank, n_cand, score, ms, splits): for every target id of every query its 0-based rank among the query's candidates (every database row outside
+the query's exclusions).  xd: K x Md, xq: K x Mq; excl_ptr / excl_idx and tgt_ptr / tgt_idx: CSR lists of 0-based database ids, strictly
+ascending inside a query, the two disjoint.
+"""
+function score_ranks(xd::Matrix{Float64}, xq::Matrix{Float64}, excl_ptr::Vector{Int64}, excl_idx::Vector{Int32}, tgt_ptr::Vector{Int64},
+		tgt_idx::Vector{Int32}; splits::Integer=0, device::Integer=0)
+	K, Md = size(xd); Mq = size(xq, 2)
+	nT = Int(tgt_ptr[end])
+	rank = zeros(Int32, max(nT, 1)); score = zeros(Float32, max(nT, 1)); n_cand = zeros(Int32, Mq)
+	info = TmvbRecRanksInfo()
+	ctx = tmvb_context(device)
+	GC.@preserve info xd xq excl_ptr excl_idx tgt_ptr tgt_idx rank score n_cand begin
+		rc = ccall((:tmvb_score_ranks, LIBTMVB), Cint,
+			(Ptr{Cvoid}, Int32, Int64, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Int64}, Ptr{Int32}, Ptr{Int64}, Ptr{Int32}, Int32, Ptr{Int32}, Ptr{Int32}, Ptr{Float32}, Ptr{Cvoid}),
+			ctx, K, Md, xd, Mq, xq, excl_ptr, excl_idx, tgt_ptr, tgt_idx, splits, rank, n_cand, score, pointer_from_objref(info))
+		tmvb_destroy_context(ctx)
+		tmvb_check(rc)
+	end
+	return (rank=Int.(rank[1:nT]), n_cand=Int.(n_cand), score=score[1:nT],
+			ms=(prep=info.ms_prep, pairs=info.ms_pairs, scan=info.ms_scan, fix=info.ms_fix), splits=Int(info.splits))
+end
+
+"""
+recall / precision / ndcg (length(topn) x Mq), mrr, pct_rank (Mq; NaN for a query without targets), their means over the queries with targets
+(recall@topn, precision@topn, ndcg@topn, mrr, pct_rank, in that order), the number of such queries and the number of targets.
+"""
+function rank_metrics(tgt_ptr::Vector{Int64}, rank::Vector{Int32}, n_cand::Vector{Int32}; topn::Vector{Int32}=Int32[10, 20, 50, 100])
+	Mq = length(tgt_ptr) - 1; nN = length(topn)
+	recall = zeros(Float64, nN, Mq); precision = zeros(Float64, nN, Mq); ndcg = zeros(Float64, nN, Mq)		# column-major (a, q) = C's [q][a]
+	mrr = zeros(Float64, Mq); pct_rank = zeros(Float64, Mq); means = zeros(Float64, 3nN + 2); counts = zeros(Int64, 2)
+	rc = ccall((:tmvb_rank_metrics, LIBTMVB), Cint,
+		(Int64, Ptr{Int64}, Ptr{Int32}, Ptr{Int32}, Int32, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}),
+		Mq, tgt_ptr, rank, n_cand, nN, topn, recall, precision, ndcg, mrr, pct_rank, means, counts)
+	tmvb_check(rc)
+	return (recall=recall, precision=precision, ndcg=ndcg, mrr=mrr, pct_rank=pct_rank, means=means, n_queries=Int(counts[1]), n_targets=Int(counts[2]))
+end
