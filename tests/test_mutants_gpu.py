@@ -1,7 +1,7 @@
 """
 NEGATIVE CONTROLS of the parity suite (round-4 review: "there is no deliberately wrong variant that must fail").
 
-Nine mutant libraries (three of round 5, two of round 6 for the SURVEY.md section 8(f) rows, two for the trained-state tests, one for the train loop's flags, one for the inverted index) -- the shipped objects with ONE translation unit recompiled under a -DTMVB_MUTANT_* flag (csrc/tmvb_internal.h, tools/build_mutants.sh) -- each
+Ten mutant libraries (three of round 5, two of round 6 for the SURVEY.md section 8(f) rows, two for the trained-state tests, one for the train loop's flags, one for the inverted index, one for the sharded runs) -- the shipped objects with ONE translation unit recompiled under a -DTMVB_MUTANT_* flag (csrc/tmvb_internal.h, tools/build_mutants.sh) -- each
 wrong in one operator, in a way a careless port of the reference would be:
   mut_lda_eps    epsilon dropped from LDA's update_phi! / update_gamma!            src/LDA.jl:152, :145
   mut_ctpf_bet   `log bet` where update_xi! needs `log vav`                         src/CTPF.jl:336 -- the reference's own OpenCL path has this bug, src/gpuCTPF.jl:624
@@ -13,6 +13,8 @@ wrong in one operator, in a way a careless port of the reference would be:
   mut_lda_stale_parts  tmvb_lda_estep leaves the previous iteration's ELBO parts marked valid    csrc/tmvb_lda.hip (logz_valid, pw_diff): a flag of the host state machine, not arithmetic
   mut_index_repeat   tmvb_build_inv_index drops a posting whose (id, document) equals the previous posting of that id      csrc/tmvb_core.hip (host code): a repeated id inside a document
                      counts once -- the reference's overwrite, quirk Q1, where the engine accumulates; only an un-condensed corpus (tests/presentations.py, P5) shows it
+  mut_ctm_empty_tail a CTM shard without documents does not clear the scatter matrix in its statistics tail       csrc/tmvb_ctm.hip (ctm_reduce_docs_on): the empty rank hands the
+                     previous iteration's all-reduced scatter matrix back into the next all-reduce; the world-2, near-even sharded CTM tests pass on it
 For each, a NAMED parity test is run in a fresh pytest process with TMVB_LIB_VARIANT=<mutant> and must FAIL with an assertion of that test (not an import
 error, not a crash), while the shipped library passes the same test in the ordinary suite.  A parity suite that stays green on these would have no teeth.
 """
@@ -50,6 +52,10 @@ MUTANTS = {
     # every sorted, condensed corpus of the suite passes on this mutant (no document holds an id twice): the un-condensed presentation must not
     "mut_index_repeat": ("tmvb_core.hip", "-DTMVB_MUTANT_INDEX_SKIP_REPEAT=1",
                          ["tests/test_corpus_presentations_gpu.py::test_teacher_forced_fixed_sweeps[lda_k50-P5]"]),
+    # no rank of the world-2 sharded tests is empty: they pass on this mutant (test_the_empty_shard_mutant_passes_the_existing_sharded_ctm_tests); the second
+    # teacher-forced iteration of ragged6 sums the stale scatter matrix of the first into sigma
+    "mut_ctm_empty_tail": ("tmvb_ctm.hip", "-DTMVB_MUTANT_CTM_EMPTY_SHARD_TAIL=1",
+                           ["tests/test_sharded_oracle_gpu.py::test_sharded_teacher_forced_fixed_sweeps[ctm_k12-ragged6]"]),
 }
 
 
@@ -107,3 +113,17 @@ def test_the_same_tests_pass_on_the_shipped_library():
     test_id = "tests/test_corpus_presentations_gpu.py::test_teacher_forced_fixed_sweeps[lda_k50-P0]"
     r = _run(test_id, "mut_index_repeat")
     assert r.returncode == 0, (test_id, r.stdout[-2000:], r.stderr[-1000:])
+
+
+def test_the_empty_shard_mutant_passes_the_existing_sharded_ctm_tests():
+    """mut_ctm_empty_tail is invisible to the sharded CTM tests that were there before tests/test_sharded_oracle_gpu.py (world 2, near-even cuts, compared with
+    the single-context run), and what the oracle test fails on is the scatter matrix: ctm.sigma_rel, in the SECOND iteration of ragged6 (the first finds the
+    tail as create left it, zero)."""
+    _ensure("mut_ctm_empty_tail")
+    for test_id in ("tests/test_dist_gpu.py::test_sharded_ctm_world2_matches_single_context", "tests/test_comm_gpu.py::test_in_library_sharded_ctm_world2"):
+        r = _run(test_id, "mut_ctm_empty_tail")
+        assert r.returncode == 0, (test_id, r.stdout[-2000:], r.stderr[-1000:])
+    r = _run(MUTANTS["mut_ctm_empty_tail"][2][0], "mut_ctm_empty_tail")
+    fail = [ln for ln in r.stdout.splitlines() if "AssertionError" in ln]
+    print("mut_ctm_empty_tail fails on:", fail[:2])
+    assert r.returncode == 1 and any("ctm.sigma_rel" in ln and "'ragged6', 1)" in ln for ln in fail), r.stdout[-3000:]

@@ -2079,7 +2079,11 @@ static int ctm_reduce_docs_on(tmvb_ctm* h, hipStream_t st)
                            h->n_scatter_waves, h->K, h->NB, h->tail() + 2 * h->K);
         TMVB_HIP(hipGetLastError());
     } else {
+        // a shard without documents adds nothing to the scatter matrix, but its tail still holds what the last all-reduce left there (the GLOBAL
+        // scatter matrix of the previous iteration) and goes into the next one
+#ifndef TMVB_MUTANT_CTM_EMPTY_SHARD_TAIL      // MUTANT (tests/test_mutants_gpu.py, never in a shipped build): the stale tail is handed back to the all-reduce
         TMVB_HIP(hipMemsetAsync(h->tail() + 2 * h->K, 0, (size_t)h->K * h->K * sizeof(float), st));
+#endif
     }
     return TMVB_OK;
 }
