@@ -709,6 +709,56 @@ int tmvb_score_ranks(tmvb_ctx* ctx, int32_t K, int64_t Md, const double* xd, int
 int tmvb_rank_metrics(int64_t Mq, const int64_t* tgt_ptr, const int32_t* rank, const int32_t* n_cand, int32_t nN, const int32_t* Ns, double* recall,
                       double* precision, double* ndcg, double* mrr, double* pct_rank, double* mean, int64_t* counts);
 
+/* ============================== stochastic (minibatch) training for LDA: stepwise EM ==============================
+ * New: the reference's train! moves alpha and beta once per walk over the whole corpus (src/LDA.jl:161-187); the closest precedent for statistics
+ * gathered batch by batch is v0.6/src/gpuLDA.jl:200-225.  Here the globals move once per BATCH (Cappe & Moulines / Liang & Klein's stepwise EM, the
+ * form of online VB that fits a point-estimate beta).
+ * Inputs: a corpus of M documents (CSR as tmvb_corpus_create takes it), K, batch cuts 0 = c_0 < c_1 < ... < c_B = M (batch b = documents
+ * [c_b, c_{b+1}), M_b >= 1 of them), a schedule (tau0 >= 0, 0.5 < kappa <= 1; default 1, 0.7).
+ * State: alpha[K], beta[K*V] (and beta_old), gamma / Elogtheta [K*M] kept across visits as a warm start, the running statistic Sbar[K*V] and its
+ * tail Ebar[K] -- fp32 on the device, scaled to the WHOLE corpus --, and the step counter t (steps taken so far; it continues across calls).
+ * Initial statistic, formed when a set_state (or the first run) finds none given: Sbar_0 = (sum of all counts / K) beta_0, so that normalising it
+ * gives beta_0 back, and Ebar_0 = sum_d Elogtheta_0[:, d].
+ * Step t = 1, 2, ... on batch b:
+ *   1. the E-step of the batch's documents under the current alpha, beta: tmvb_lda_estep's kernels with (viter, vtol) and the per-document exit
+ *      rule of src/LDA.jl:170-180.  It leaves S_b (update_beta!(model, d), :152) and e_b = sum_{d in b} Elogtheta_d (:98).
+ *   2. rho_t = (tau0 + t)^(-kappa) in fp64 on the host; c0 = fp32(1 - rho_t), c1 = fp32(rho_t M / M_b), each rounded once.
+ *   3. Sbar <- c0 Sbar + c1 S_b and Ebar <- c0 Ebar + c1 e_b in fp32; the batch's statistics buffer is zero afterwards.
+ *   4. beta_old <- beta, beta <- Sbar row-normalised (update_beta!, src/LDA.jl:121-125); alpha by update_alpha!(niter, ntol) (:97-118, fp64 Newton
+ *      from the current alpha) with Elogtheta_sum = Ebar and M = the whole corpus's.
+ * With tau0 = 0 the first step has rho = 1, c0 = 0: with B = 1 it is exactly one iteration of train!.
+ * Steps 3 and 4's beta are one fused update of two launches; the row sums are fixed-order partials without floating-point atomics: the same
+ * inputs give the same bits, run([a, b, c, d]) equals run([a, b]) then run([c, d]).  There is no random number in the library: the host decides
+ * the order of the visits. */
+typedef struct tmvb_lda_svi tmvb_lda_svi;
+/* gpuLDA(corp, K) (src/gpuLDA.jl:45-84) over batches.  Corpus checks and error codes are tmvb_corpus_create's (src/Corpus.jl:41-50, :111-122); cuts[B + 1]
+ * not strictly increasing from 0 to M -> TMVB_EINVAL.  Constructor state as tmvb_lda_create. */
+int tmvb_lda_svi_create(tmvb_ctx* ctx, int64_t M, int64_t V, const int64_t* doc_ptr, const int32_t* terms, const int32_t* counts, int32_t K,
+                        const int64_t* cuts, int32_t B, tmvb_lda_svi** out);
+int tmvb_lda_svi_destroy(tmvb_lda_svi* h);
+/* update_buffer! / update_host! (src/modelutils.jl:390-396, :501-516) plus the running statistic and the step counter: alpha[K], beta / beta_old /
+ * sbar[K*V] column-major, gamma / Elogtheta[K*M] in corpus document order, ebar[K], t[1].  NULL = leave / skip; beta without beta_old sets both. */
+int tmvb_lda_svi_set_state(tmvb_lda_svi* h, const double* alpha, const double* beta, const double* beta_old, const double* gamma,
+                           const double* Elogtheta, const double* sbar, const double* ebar, const int64_t* t);
+int tmvb_lda_svi_get_state(tmvb_lda_svi* h, double* alpha, double* beta, double* beta_old, double* gamma, double* Elogtheta, double* sbar,
+                           double* ebar, int64_t* t);
+/* tau0 < 0 or not finite, kappa outside (0.5, 1] -> TMVB_EINVAL */
+int tmvb_lda_svi_set_schedule(tmvb_lda_svi* h, double tau0, double kappa);
+/* n steps of train!'s loop body (src/LDA.jl:170-182) on the batches batches[0 .. n), repeats allowed.  Asynchronous on the context's stream.  A batch id
+ * outside [0, B) -> TMVB_EINVAL before anything is enqueued. */
+int tmvb_lda_svi_run(tmvb_lda_svi* h, const int32_t* batches, int64_t n, int32_t niter, double ntol, int32_t viter, double vtol);
+/* The E-step of every batch under the final alpha, beta (src/LDA.jl:170-180); the globals and the running statistic are not touched.  Afterwards gamma and
+ * Elogtheta of all documents belong to the returned model.  Asynchronous. */
+int tmvb_lda_svi_final_pass(tmvb_lda_svi* h, int32_t viter, double vtol);
+/* rho, c0, c1: of the last step (NaN before the first) */
+typedef struct { int32_t B, K; int64_t M, V, t; double tau0, kappa, rho; float c0, c1; } tmvb_lda_svi_info_t;
+int tmvb_lda_svi_info(tmvb_lda_svi* h, tmvb_lda_svi_info_t* out);
+/* as tmvb_lda_doc_sweeps: out[M], each document's sweeps in the last E-step of ITS batch */
+int tmvb_lda_svi_doc_sweeps(tmvb_lda_svi* h, uint8_t* out);
+/* Timing of the last tmvb_lda_svi_run from HIP events on the context's stream, like tmvb_lda_last_estep_ms (TMVB_ESTEP_TIMING=1 at create): the sums over its
+ * *steps steps of the E-step, the fused update (blend + normalise) and update_alpha!, in ms. */
+int tmvb_lda_svi_last_run_ms(tmvb_lda_svi* h, float* ms_estep, float* ms_update, float* ms_alpha, int64_t* steps);
+
 #ifdef __cplusplus
 }
 #endif

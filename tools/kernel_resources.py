@@ -42,6 +42,8 @@ BENCHED = {
     "nb_feature_kernel": 0, "nb_scan_kernel": 0, "nb_merge_kernel": 0,
     # held-out recommendation ranks (tools/recs_eval_bench.py): features, pair scores, target sort, the fused MFMA scan / count, the exclusion fix
     "rk_feature_kernel": 0, "rk_pairs_kernel": 0, "rk_sort_kernel": 0, "rk_scan_kernel": 0, "rk_fix_kernel": 0,
+    # stochastic LDA training (tools/svi_bench.py): the fused global update -- blend + partial row sums, then normalise
+    "svi_blend_kernel<": 0, "svi_norm_kernel": 0,
 }
 
 

@@ -20,6 +20,7 @@ from .coherence import CoherenceResult, coherence, coherence_from_counts, cohere
 from .neighbors import NeighborsResult, docsim, neighbors_raw, topic_proportions
 from .recs_eval import (HeldReaders, RecEvalResult, rank_metrics, rank_metrics_raw, rec_eval, rec_quality, rec_ranks_raw, split_readers,
                         split_readers_raw)
+from .lda_svi import gpuLDAStochastic, gpu_train_stochastic, svi_cuts, svi_order, svi_rho
 
 __all__ = ["CorpusError", "DocumentError", "EngineError", "TopicModelError", "build", "exported_symbols", "lib", "LIB_PATH",
            "Corpus", "Document", "PackedCorpus", "check_corp", "check_doc", "dirichlet_rows", "readcorp", "readcorp_packed", "writecorp",
@@ -29,4 +30,5 @@ __all__ = ["CorpusError", "DocumentError", "EngineError", "TopicModelError", "bu
            "HeldoutResult", "heldout_loglik", "heldout_loglik_raw", "perplexity", "split_corpus", "split_corpus_raw",
            "CoherenceResult", "coherence", "coherence_from_counts", "coherence_from_counts_raw", "codocfreq_raw",
            "NeighborsResult", "docsim", "neighbors_raw", "topic_proportions",
-           "HeldReaders", "RecEvalResult", "rank_metrics", "rank_metrics_raw", "rec_eval", "rec_quality", "rec_ranks_raw", "split_readers", "split_readers_raw"]
+           "HeldReaders", "RecEvalResult", "rank_metrics", "rank_metrics_raw", "rec_eval", "rec_quality", "rec_ranks_raw", "split_readers", "split_readers_raw",
+           "gpuLDAStochastic", "gpu_train_stochastic", "svi_cuts", "svi_order", "svi_rho"]

@@ -146,6 +146,12 @@ struct tmvb_ctpf_view {
 };
 int tmvb_ctpf_view_of(tmvb_ctpf* h, tmvb_ctpf_view* v);
 int tmvb_corpus_term_index(tmvb_corpus* c);
+// hooks of the stochastic driver (tmvb_lda_svi.hip) into the LDA handle (tmvb_lda.hip): one alpha / beta pair and one set of auxiliary streams for all
+// batch handles, the pair's buffers for the fused update, and the flip of the pair
+struct tmvb_lda_globals_view { float* beta[2]; int cur; int KP; float* stats; };
+int tmvb_lda_share_globals(tmvb_lda* h, tmvb_lda* owner);
+int tmvb_lda_globals_view_of(tmvb_lda* h, tmvb_lda_globals_view* v);
+int tmvb_lda_set_cur(tmvb_lda* h, int cur);
 // n sum-all-reduces issued by one host thread inside one RCCL group (tmvb_comm.hip)
 int tmvb_comm_allreduce_group(tmvb_comm* const* comms, void* const* dev_ptrs, const int64_t* counts, int n, int32_t dtype);
 int tmvb_comm_allreduce_on(tmvb_comm* c, void* dev_ptr, int64_t count, int32_t dtype, hipStream_t on);
@@ -182,6 +188,8 @@ int tmvb_check_ctx_or_device(const char* fn, tmvb_ctx* ctx);
 //   TMVB_MUTANT_CTM_EMPTY_SHARD_TAIL  ctm_reduce_docs_on (tmvb_ctm.hip) does not clear the scatter tail of a shard without documents: the empty rank hands the previous
 //                                   iteration's all-reduced scatter matrix back into the next all-reduce; only a partition with an empty rank, run for two iterations
 //                                   against the oracle, shows it (tests/test_sharded_oracle_gpu.py, ragged6)
+//   TMVB_MUTANT_SVI_KEEP_BATCH_STATS  the fused global update of the stochastic driver (tmvb_lda_svi.hip) does not clear the batch's statistics: the next E-step
+//                                   accumulates on top of them; tests/test_svi_mutant_gpu.py
 #ifdef TMVB_MUTANT_FLDA_H_NO_GUARD
 #define TMVB_FLDA_H_GUARD(cond) true
 #else

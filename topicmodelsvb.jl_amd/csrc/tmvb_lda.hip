@@ -1199,6 +1199,9 @@ struct tmvb_lda {
     hipEvent_t ev_comm = nullptr, ev_tail = nullptr;
     bool ar_live = false;              // set for the E-step inside tmvb_lda_estep_allreduce
     bool tail_early = false;           // ev_tail (on aux[AR]) marks the all-reduced Elogtheta_sum tail: update_alpha! starts from it
+    // stochastic training (tmvb_lda_svi.hip): a batch handle reads the alpha / beta pair and issues on the auxiliary streams of the driver's first
+    // batch handle instead of its own (tmvb_lda_share_globals); it then owns neither
+    bool own_globals = true, own_aux = true;
 };
 
 static bool lda_reg_lpr_supported(int lpr) { return lpr >= 1 && lpr <= 25 && (lpr & 1); }   // every KP = 4 * odd <= 100
@@ -1376,7 +1379,7 @@ extern "C" int tmvb_lda_destroy(tmvb_lda* h)
     if (h->ctx) (void)hipSetDevice(h->ctx->device);
     for (int a = 0; a < tmvb_lda::NAUX; ++a) if (h->aux[a]) (void)hipStreamSynchronize(h->aux[a]);
     if (h->ctx) (void)hipStreamSynchronize(h->ctx->stream);
-    (void)hipFree(h->d_alpha_d); (void)hipFree(h->d_alpha_f); (void)hipFree(h->d_beta[0]); (void)hipFree(h->d_beta[1]);
+    if (h->own_globals) { (void)hipFree(h->d_alpha_d); (void)hipFree(h->d_alpha_f); (void)hipFree(h->d_beta[0]); (void)hipFree(h->d_beta[1]); }
     (void)hipFree(h->d_stats_b); (void)hipFree(h->d_ts_partial_b);
     if (h->own_stats) (void)hipFree(h->d_stats);
     (void)hipFree(h->d_wtok); (void)hipFree(h->d_E); (void)hipFree(h->d_ts_partial);
@@ -1402,7 +1405,8 @@ extern "C" int tmvb_lda_destroy(tmvb_lda* h)
     for (hipEvent_t e : h->ev_piece) if (e) (void)hipEventDestroy(e);
     for (int a = 0; a < tmvb_lda::NAUX; ++a) {
         if (h->ev_join[a]) (void)hipEventDestroy(h->ev_join[a]);
-        tmvb_release_stream(h->aux[a]); h->aux[a] = nullptr;        // pooled streams stay (tmvb_pool_stream)
+        if (h->own_aux) tmvb_release_stream(h->aux[a]);             // pooled streams stay (tmvb_pool_stream)
+        h->aux[a] = nullptr;
     }
     delete h;
     return TMVB_OK;
@@ -2380,4 +2384,43 @@ extern "C" int tmvb_lda_last_estep_ms(tmvb_lda* h, float* ms)
     TMVB_HIP(hipEventSynchronize(h->ev1));
     TMVB_HIP(hipEventElapsedTime(ms, h->ev0, h->ev1));
     return TMVB_OK;
+}
+
+// ---- stochastic training (tmvb_lda_svi.hip): the additive hooks a driver over per-batch handles needs.  None of them is reached from the entry points above.
+// h gives up its own alpha / beta pair and auxiliary streams and uses `owner`'s from here on (same context, K and V): the batch handles of one driver run one
+// after the other, read ONE copy of the globals and fork onto ONE set of streams.  The owner must outlive h.
+int tmvb_lda_share_globals(tmvb_lda* h, tmvb_lda* owner)
+{
+    TMVB_REQUIRE(h && owner && h != owner, TMVB_EINVAL, "tmvb_lda_share_globals: bad handle");
+    TMVB_REQUIRE(h->ctx == owner->ctx && h->K == owner->K && h->V == owner->V, TMVB_ESHAPE, "tmvb_lda_share_globals: the handles differ in context, K or V");
+    TMVB_REQUIRE(h->own_globals && h->own_aux && owner->own_globals && owner->own_aux, TMVB_EINVAL, "tmvb_lda_share_globals: a handle already shares");
+    TMVB_HIP(hipSetDevice(h->ctx->device));
+    { int jrc = lda_join_side(h); if (jrc) return jrc; }
+    for (int a = 0; a < tmvb_lda::NAUX; ++a) TMVB_HIP(hipStreamSynchronize(h->aux[a]));
+    TMVB_HIP(hipStreamSynchronize(h->ctx->stream));
+    (void)hipFree(h->d_alpha_d); (void)hipFree(h->d_alpha_f); (void)hipFree(h->d_beta[0]); (void)hipFree(h->d_beta[1]);
+    h->d_alpha_d = owner->d_alpha_d; h->d_alpha_f = owner->d_alpha_f; h->d_beta[0] = owner->d_beta[0]; h->d_beta[1] = owner->d_beta[1];
+    h->cur = owner->cur;
+    h->own_globals = false;
+    for (int a = 0; a < tmvb_lda::NAUX; ++a) { tmvb_release_stream(h->aux[a]); h->aux[a] = owner->aux[a]; }
+    h->own_aux = false;
+    return TMVB_OK;
+}
+
+int tmvb_lda_globals_view_of(tmvb_lda* h, tmvb_lda_globals_view* v)
+{
+    TMVB_REQUIRE(h && v, TMVB_EINVAL, "tmvb_lda_globals_view_of: NULL argument");
+    v->beta[0] = h->d_beta[0]; v->beta[1] = h->d_beta[1]; v->cur = h->cur; v->KP = h->KP; v->stats = h->d_stats;
+    return TMVB_OK;
+}
+
+// which buffer of the (shared) pair is beta: the driver flips it once per step and tells the handle it runs next; whatever the handle kept about its
+// own last M-step is void.  The context's stream then also waits for the handle's side chain (its update_alpha!).
+int tmvb_lda_set_cur(tmvb_lda* h, int cur)
+{
+    TMVB_REQUIRE(h != nullptr && (cur == 0 || cur == 1), TMVB_EINVAL, "tmvb_lda_set_cur: bad argument");
+    TMVB_HIP(hipSetDevice(h->ctx->device));
+    h->cur = cur;
+    h->mark_valid = false; h->pw_valid = false; h->stats_fresh = false; h->logz_valid = false; h->esum_fresh = false; h->esum_side = false;
+    return lda_join_side(h);
 }
