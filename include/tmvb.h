@@ -759,6 +759,64 @@ int tmvb_lda_svi_doc_sweeps(tmvb_lda_svi* h, uint8_t* out);
  * *steps steps of the E-step, the fused update (blend + normalise) and update_alpha!, in ms. */
 int tmvb_lda_svi_last_run_ms(tmvb_lda_svi* h, float* ms_estep, float* ms_update, float* ms_alpha, int64_t* steps);
 
+/* ============================== stochastic (minibatch) training for CTM: stepwise EM ==============================
+ * New: the reference's train! moves mu, sigma and beta once per walk over the whole corpus (src/CTM.jl:185-217).  Here they move once per BATCH, as
+ * alpha and beta do in the LDA section above.
+ * Inputs: a corpus of M documents (CSR as tmvb_corpus_create takes it), K <= 256, batch cuts 0 = c_0 < c_1 < ... < c_B = M (batch b = documents
+ * [c_b, c_{b+1}), M_b >= 1 of them), a schedule (tau0 >= 0, 0.5 < kappa <= 1; default 1, 0.7).
+ * State: the globals mu[K], sigma / invsigma[K*K], beta[K*V] (and beta_old); per document, kept across visits as a warm start, lambda / vsq [K*M] and
+ * logzeta[M]; the running statistic -- fp32 on the device, scaled to the WHOLE corpus -- Sbar[K*V], lbar[K] (sum lambda), vbar[K] (sum vsq) and
+ * Cbar[K*K], the scatter matrix sum (lambda - m_ref)(lambda - m_ref)^T taken about the vector m_ref[K] (fp64), with m_ref itself; and the step
+ * counter t (steps taken so far; it continues across calls).
+ * Initial statistic, formed when a set_state (or the first run) finds none given: Sbar_0 = (sum of all counts / K) beta_0, so that normalising it
+ * gives beta_0 back; lbar_0 = sum_d lambda_d, vbar_0 = sum_d vsq_d, Cbar_0 = sum_d (lambda_d - mu_0)(lambda_d - mu_0)^T, m_ref = mu_0.  The
+ * constructor state (lambda = 0, vsq = 1, mu = 0) gives lbar = 0, vbar = M, Cbar = 0, hence sigma = I.
+ * Step t = 1, 2, ... on batch b, mu being the current mean:
+ *   1. the E-step of the batch's documents under the current mu, invsigma, beta: tmvb_ctm_estep's kernels with (niter, ntol, viter, vtol) and the
+ *      per-document exit rule of src/CTM.jl:194-205.  It leaves S_b (update_beta!(model, d), :122-125), l_b = sum_{d in b} lambda_d, v_b = sum vsq_d
+ *      and C_b = sum (lambda_d - mu)(lambda_d - mu)^T (the sums of :102-111, the scatter about the CURRENT mu).
+ *   2. rho_t = (tau0 + t)^(-kappa) in fp64 on the host; c0 = fp32(1 - rho_t), c1 = fp32(rho_t M / M_b), each rounded once.
+ *   3. Recentre, then blend.  With a = lbar - M m_ref and d = m_ref - mu (before lbar moves): C' = Cbar + a d^T + d a^T + M d d^T, the exact scatter
+ *      of the same weighted population about mu, in fp64; Cbar <- c0 C' + c1 C_b (fp64, rounded once), Sbar <- c0 Sbar + c1 S_b,
+ *      lbar <- c0 lbar + c1 l_b, vbar <- c0 vbar + c1 v_b (fp32), m_ref <- mu; the batch's statistics buffer is cleared.
+ *   4. beta_old <- beta, beta <- Sbar row-normalised (update_beta!, src/CTM.jl:114-119); sigma <- (diag(vbar) + Cbar) / M and invsigma by the fp64
+ *      inversion of update_sigma! (:108-111) -- about the PRE-step mu, the reference's order update_sigma! then update_mu! (:207-208) --; then
+ *      mu <- lbar / M (update_mu!, :102-104).
+ * With tau0 = 0 the first step has rho = 1, c0 = 0, c1 = M / M_b: with B = 1 it is exactly one iteration of train!.
+ * Steps 3 and 4 are four launches on the context's stream (blend, normalise, tail, sigma / mu) without floating-point atomics and with a fixed
+ * summation order: the same inputs give the same bits, run([a, b, c, d]) equals run([a, b]) then run([c, d]).  There is no random number in the
+ * library: the host decides the order of the visits. */
+typedef struct tmvb_ctm_svi tmvb_ctm_svi;
+/* gpuCTM(corp, K) (src/gpuCTM.jl:6-99) over batches.  Corpus checks and error codes are tmvb_corpus_create's (src/Corpus.jl:41-50, :111-122); K limits are
+ * tmvb_ctm_create's; cuts[B + 1] not strictly increasing from 0 to M -> TMVB_EINVAL.  Constructor state as tmvb_ctm_create (src/CTM.jl:37-48). */
+int tmvb_ctm_svi_create(tmvb_ctx* ctx, int64_t M, int64_t V, const int64_t* doc_ptr, const int32_t* terms, const int32_t* counts, int32_t K,
+                        const int64_t* cuts, int32_t B, tmvb_ctm_svi** out);
+int tmvb_ctm_svi_destroy(tmvb_ctm_svi* h);
+/* update_buffer! / update_host! (src/modelutils.jl:400-435, :519-537) plus the running statistic and the step counter: mu[K], sigma / invsigma[K*K],
+ * beta / beta_old / sbar[K*V] column-major, lambda / vsq[K*M] and logzeta[M] in corpus document order (lambda_old follows lambda), lbar / vbar / mref[K],
+ * cbar[K*K], t[1].  NULL = leave / skip; beta without beta_old sets both; lbar, vbar, cbar and mref are set together or not at all (TMVB_EINVAL). */
+int tmvb_ctm_svi_set_state(tmvb_ctm_svi* h, const double* mu, const double* sigma, const double* invsigma, const double* beta, const double* beta_old,
+                           const double* lambda, const double* vsq, const double* logzeta, const double* sbar, const double* lbar, const double* vbar,
+                           const double* cbar, const double* mref, const int64_t* t);
+int tmvb_ctm_svi_get_state(tmvb_ctm_svi* h, double* mu, double* sigma, double* invsigma, double* beta, double* beta_old, double* lambda, double* vsq,
+                           double* logzeta, double* sbar, double* lbar, double* vbar, double* cbar, double* mref, int64_t* t);
+/* tau0 < 0 or not finite, kappa outside (0.5, 1] -> TMVB_EINVAL (no reference operator: the schedule of the section's head) */
+int tmvb_ctm_svi_set_schedule(tmvb_ctm_svi* h, double tau0, double kappa);
+/* n steps of train!'s loop body (src/CTM.jl:194-208) on the batches batches[0 .. n), repeats allowed.  Asynchronous on the context's stream.  A batch id
+ * outside [0, B) -> TMVB_EINVAL before anything is enqueued. */
+int tmvb_ctm_svi_run(tmvb_ctm_svi* h, const int32_t* batches, int64_t n, int32_t niter, double ntol, int32_t viter, double vtol);
+/* The E-step of every batch under the final mu, sigma, beta (src/CTM.jl:194-205); the globals and the running statistic are not touched.  Afterwards lambda,
+ * vsq and logzeta of all documents belong to the returned model.  Asynchronous. */
+int tmvb_ctm_svi_final_pass(tmvb_ctm_svi* h, int32_t niter, double ntol, int32_t viter, double vtol);
+/* rho, c0, c1: of the last step (NaN before the first); the bookkeeping of train!'s loop counter (src/CTM.jl:193) */
+typedef struct { int32_t B, K; int64_t M, V, t; double tau0, kappa, rho; float c0, c1; } tmvb_ctm_svi_info_t;
+int tmvb_ctm_svi_info(tmvb_ctm_svi* h, tmvb_ctm_svi_info_t* out);
+/* as tmvb_ctm_doc_sweeps (the sweep loop of src/CTM.jl:196-204): out[M], each document's sweeps in the last E-step of ITS batch */
+int tmvb_ctm_svi_doc_sweeps(tmvb_ctm_svi* h, uint8_t* out);
+/* Timing of the last tmvb_ctm_svi_run from HIP events on the context's stream, like tmvb_ctm_last_estep_ms (TMVB_ESTEP_TIMING=1 at create): the sums over its
+ * *steps steps of the E-step (src/CTM.jl:194-205), the fused update (blend + normalise + tail) and update_sigma! + update_mu! (:207-208), in ms. */
+int tmvb_ctm_svi_last_run_ms(tmvb_ctm_svi* h, float* ms_estep, float* ms_update, float* ms_sigma_mu, int64_t* steps);
+
 #ifdef __cplusplus
 }
 #endif

@@ -44,6 +44,8 @@ BENCHED = {
     "rk_feature_kernel": 0, "rk_pairs_kernel": 0, "rk_sort_kernel": 0, "rk_scan_kernel": 0, "rk_fix_kernel": 0,
     # stochastic LDA training (tools/svi_bench.py): the fused global update -- blend + partial row sums, then normalise
     "svi_blend_kernel<": 0, "svi_norm_kernel": 0,
+    # stochastic CTM training (tools/ctm_svi_bench.py): the tail of the fused global update -- recentre in fp64, blend (the K x V part is the two above)
+    "ctm_svi_tail_kernel": 0,
 }
 
 

@@ -21,6 +21,7 @@ from .neighbors import NeighborsResult, docsim, neighbors_raw, topic_proportions
 from .recs_eval import (HeldReaders, RecEvalResult, rank_metrics, rank_metrics_raw, rec_eval, rec_quality, rec_ranks_raw, split_readers,
                         split_readers_raw)
 from .lda_svi import gpuLDAStochastic, gpu_train_stochastic, svi_cuts, svi_order, svi_rho
+from .ctm_svi import gpuCTMStochastic, gpu_train_ctm_stochastic
 
 __all__ = ["CorpusError", "DocumentError", "EngineError", "TopicModelError", "build", "exported_symbols", "lib", "LIB_PATH",
            "Corpus", "Document", "PackedCorpus", "check_corp", "check_doc", "dirichlet_rows", "readcorp", "readcorp_packed", "writecorp",
@@ -31,4 +32,5 @@ __all__ = ["CorpusError", "DocumentError", "EngineError", "TopicModelError", "bu
            "CoherenceResult", "coherence", "coherence_from_counts", "coherence_from_counts_raw", "codocfreq_raw",
            "NeighborsResult", "docsim", "neighbors_raw", "topic_proportions",
            "HeldReaders", "RecEvalResult", "rank_metrics", "rank_metrics_raw", "rec_eval", "rec_quality", "rec_ranks_raw", "split_readers", "split_readers_raw",
-           "gpuLDAStochastic", "gpu_train_stochastic", "svi_cuts", "svi_order", "svi_rho"]
+           "gpuLDAStochastic", "gpu_train_stochastic", "svi_cuts", "svi_order", "svi_rho",
+           "gpuCTMStochastic", "gpu_train_ctm_stochastic"]

@@ -1465,6 +1465,9 @@ struct tmvb_ctm {
     double* d_logz = nullptr; size_t logz_cap = 0; int64_t n_logz = 0; float* d_pdot = nullptr; double* d_pw_partial = nullptr; int pw_blocks = 0;
     bool logz_valid = false, stats_fresh = false, pw_valid = false;
     int elbo_form = 0; bool force_walk = false;
+    // stochastic training (tmvb_ctm_svi.hip): a batch handle reads the globals proper of the driver's first batch handle instead of its own
+    // (tmvb_ctm_share_globals); it then owns none of them
+    bool own_globals = true;
     int64_t stats_len() const { return (int64_t)K * V + 2 * K + (int64_t)K * K; }
     float* tail() const { return d_stats + (size_t)K * V; }
 };
@@ -1479,17 +1482,20 @@ extern "C" int tmvb_ctm_destroy(tmvb_ctm* h)
 {
     if (!h) return TMVB_OK;
     if (h->ctx) (void)hipSetDevice(h->ctx->device);
-    (void)hipFree(h->d_beta[0]); (void)hipFree(h->d_beta[1]); (void)hipFree(h->d_beta_pad);
+    if (h->own_globals) {
+        (void)hipFree(h->d_beta[0]); (void)hipFree(h->d_beta[1]); (void)hipFree(h->d_invsigma_f); (void)hipFree(h->d_mu_f);
+        (void)hipFree(h->d_sigma); (void)hipFree(h->d_invsigma); (void)hipFree(h->d_mu); (void)hipFree(h->d_logdet); (void)hipFree(h->d_status);
+    }
+    (void)hipFree(h->d_beta_pad);
     if (h->own_stats) (void)hipFree(h->d_stats);
     (void)hipFree(h->d_lambda); (void)hipFree(h->d_lambda_old); (void)hipFree(h->d_vsq); (void)hipFree(h->d_logzeta);
     (void)hipFree(h->d_sigma_work); (void)hipFree(h->d_sigma_work_s);
-    (void)hipFree(h->d_wtok); (void)hipFree(h->d_E); (void)hipFree(h->d_ts_partial); (void)hipFree(h->d_invsigma_f);
+    (void)hipFree(h->d_wtok); (void)hipFree(h->d_E); (void)hipFree(h->d_ts_partial);
     (void)hipFree(h->d_q_S); (void)hipFree(h->d_q_sd); (void)hipFree(h->d_q_mu);
     (void)hipFree(h->d_bt_sdiag); (void)hipFree(h->d_bt_muf); (void)hipFree(h->d_cg_iters); (void)hipFree(h->d_doc_newton); (void)hipFree(h->d_doc_order0); (void)hipFree(h->d_doc_order_q); (void)hipFree(h->d_wave_keys);
-    (void)hipFree(h->d_mu_f); (void)hipFree(h->d_sigma); (void)hipFree(h->d_invsigma); (void)hipFree(h->d_mu);
-    (void)hipFree(h->d_logdet); (void)hipFree(h->d_scatter_partial); (void)hipFree(h->d_sweeps); (void)hipFree(h->d_doc_order);
+    (void)hipFree(h->d_scatter_partial); (void)hipFree(h->d_sweeps); (void)hipFree(h->d_doc_order);
     (void)hipFree(h->d_partial); (void)hipFree(h->d_partial_docs); (void)hipFree(h->d_partial_docs2); (void)hipFree(h->d_rowsum); (void)hipFree(h->d_doc_val); (void)hipFree(h->d_elbo);
-    (void)hipFree(h->d_newton); (void)hipFree(h->d_status); (void)hipFree(h->d_logz); (void)hipFree(h->d_pdot); (void)hipFree(h->d_pw_partial);
+    (void)hipFree(h->d_newton); (void)hipFree(h->d_logz); (void)hipFree(h->d_pdot); (void)hipFree(h->d_pw_partial);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
     if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
@@ -2379,6 +2385,57 @@ extern "C" int tmvb_ctm_last_estep_ms(tmvb_ctm* h, float* ms)
     TMVB_HIP(hipEventSynchronize(h->ev1));
     TMVB_HIP(hipEventElapsedTime(ms, h->ev0, h->ev1));
     return TMVB_OK;
+}
+
+// ---- stochastic training (tmvb_ctm_svi.hip): the additive hooks a driver over per-batch handles needs.  None of them is reached from the entry points above.
+// h gives up its own globals proper -- the beta pair, mu, sigma, invsigma (fp64 and the padded fp32 copies), logdet, the inversion's status -- and reads
+// `owner`'s from here on (same context, K and V): the batch handles of one driver run one after the other on ONE copy.  The derived tables (d_q_*, d_bt_*,
+// d_beta_pad) stay per handle: every E-step launch rebuilds them from the globals.  The auxiliary streams are the device's pooled ones for every handle
+// already.  The owner must outlive h.
+int tmvb_ctm_share_globals(tmvb_ctm* h, tmvb_ctm* owner)
+{
+    TMVB_REQUIRE(h && owner && h != owner, TMVB_EINVAL, "tmvb_ctm_share_globals: bad handle");
+    TMVB_REQUIRE(h->ctx == owner->ctx && h->K == owner->K && h->V == owner->V, TMVB_ESHAPE, "tmvb_ctm_share_globals: the handles differ in context, K or V");
+    TMVB_REQUIRE(h->own_globals && owner->own_globals, TMVB_EINVAL, "tmvb_ctm_share_globals: a handle already shares");
+    TMVB_HIP(hipSetDevice(h->ctx->device));
+    { int jrc = ctm_join_spec(h); if (jrc) return jrc; }
+    TMVB_HIP(hipStreamSynchronize(h->ctx->stream));
+    (void)hipFree(h->d_beta[0]); (void)hipFree(h->d_beta[1]); (void)hipFree(h->d_invsigma_f); (void)hipFree(h->d_mu_f);
+    (void)hipFree(h->d_sigma); (void)hipFree(h->d_invsigma); (void)hipFree(h->d_mu); (void)hipFree(h->d_logdet); (void)hipFree(h->d_status);
+    h->d_beta[0] = owner->d_beta[0]; h->d_beta[1] = owner->d_beta[1]; h->d_invsigma_f = owner->d_invsigma_f; h->d_mu_f = owner->d_mu_f;
+    h->d_sigma = owner->d_sigma; h->d_invsigma = owner->d_invsigma; h->d_mu = owner->d_mu; h->d_logdet = owner->d_logdet; h->d_status = owner->d_status;
+    h->cur = owner->cur;
+    h->own_globals = false;
+    h->tail_fresh = false; h->sigma_staged = false;
+    return TMVB_OK;
+}
+
+int tmvb_ctm_globals_view_of(tmvb_ctm* h, tmvb_ctm_globals_view* v)
+{
+    TMVB_REQUIRE(h && v, TMVB_EINVAL, "tmvb_ctm_globals_view_of: NULL argument");
+    v->beta[0] = h->d_beta[0]; v->beta[1] = h->d_beta[1]; v->cur = h->cur; v->KP = h->KP; v->mu = h->d_mu;
+    return TMVB_OK;
+}
+
+// which buffer of the (shared) pair is beta: the driver flips it once per step and tells the handle it runs next; whatever the handle kept about its own
+// last M-step is void
+int tmvb_ctm_set_cur(tmvb_ctm* h, int cur)
+{
+    TMVB_REQUIRE(h != nullptr && (cur == 0 || cur == 1), TMVB_EINVAL, "tmvb_ctm_set_cur: bad argument");
+    h->cur = cur;
+    h->pw_valid = false; h->stats_fresh = false; h->logz_valid = false;
+    return TMVB_OK;
+}
+
+// update_sigma! then update_mu! (src/CTM.jl:207-208) as ONE launch of ctm_sigma_mu_kernel on the statistics tail as it stands -- the driver has just written
+// the blended running tail there -- with M_total.  The tail is no longer the batch's: tail_fresh and a staged sigma (none for a distributed handle) are void.
+int tmvb_ctm_sigma_mu_from_tail(tmvb_ctm* h)
+{
+    TMVB_REQUIRE(h != nullptr, TMVB_EINVAL, "tmvb_ctm_sigma_mu_from_tail: handle is NULL");
+    h->tail_fresh = false; h->sigma_staged = false;
+    TMVB_HIP(hipSetDevice(h->ctx->device));
+    { int jrc = ctm_join_spec(h); if (jrc) return jrc; }
+    return ctm_sigma_mu(h, 1, 1, false, nullptr);
 }
 
 // ====================================================================================================================

@@ -152,6 +152,13 @@ struct tmvb_lda_globals_view { float* beta[2]; int cur; int KP; float* stats; };
 int tmvb_lda_share_globals(tmvb_lda* h, tmvb_lda* owner);
 int tmvb_lda_globals_view_of(tmvb_lda* h, tmvb_lda_globals_view* v);
 int tmvb_lda_set_cur(tmvb_lda* h, int cur);
+// ... and of the CTM driver (tmvb_ctm_svi.hip) into the CTM handle (tmvb_ctm.hip): one copy of the globals proper (beta pair, mu, sigma, invsigma) for all
+// batch handles, the pair's buffers and the fp64 mu for the fused update, the flip of the pair, and update_sigma! + update_mu! on the blended tail
+struct tmvb_ctm_globals_view { float* beta[2]; int cur; int KP; double* mu; };
+int tmvb_ctm_share_globals(tmvb_ctm* h, tmvb_ctm* owner);
+int tmvb_ctm_globals_view_of(tmvb_ctm* h, tmvb_ctm_globals_view* v);
+int tmvb_ctm_set_cur(tmvb_ctm* h, int cur);
+int tmvb_ctm_sigma_mu_from_tail(tmvb_ctm* h);
 // n sum-all-reduces issued by one host thread inside one RCCL group (tmvb_comm.hip)
 int tmvb_comm_allreduce_group(tmvb_comm* const* comms, void* const* dev_ptrs, const int64_t* counts, int n, int32_t dtype);
 int tmvb_comm_allreduce_on(tmvb_comm* c, void* dev_ptr, int64_t count, int32_t dtype, hipStream_t on);
@@ -190,6 +197,8 @@ int tmvb_check_ctx_or_device(const char* fn, tmvb_ctx* ctx);
 //                                   against the oracle, shows it (tests/test_sharded_oracle_gpu.py, ragged6)
 //   TMVB_MUTANT_SVI_KEEP_BATCH_STATS  the fused global update of the stochastic driver (tmvb_lda_svi.hip) does not clear the batch's statistics: the next E-step
 //                                   accumulates on top of them; tests/test_svi_mutant_gpu.py
+//   TMVB_MUTANT_CTM_SVI_NO_RECENTRE   the tail kernel of the stochastic CTM driver (tmvb_ctm_svi.hip) blends the running scatter matrix without moving it from
+//                                   m_ref to the current mu first; shows once mu has moved between visits; tests/test_ctm_svi_mutant_gpu.py
 #ifdef TMVB_MUTANT_FLDA_H_NO_GUARD
 #define TMVB_FLDA_H_GUARD(cond) true
 #else

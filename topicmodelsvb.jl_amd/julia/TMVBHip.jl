@@ -438,6 +438,61 @@ function train!(model::hipCTM; iter::Integer=150, tol::Real=1.0, niter::Integer=
 	nothing
 end
 
+"""
+    train_stochastic!(model::hipCTM; batch=4096, epochs=2, tau0=1.0, kappa=0.7, order=nothing, final_pass=true, niter=1000, ntol=1/K^2, viter=10, vtol=1/K^2)
+
+Minibatch training (stepwise EM; include/tmvb.h, "stochastic (minibatch) training for CTM"): the loop body of train! (src/CTM.jl:194-208) once per batch
+of `batch` documents (equal cuts, a ragged last one), mu, sigma and beta moving after every batch with rho_t = (tau0 + t)^(-kappa).  `order` (0-based batch
+ids, repeats allowed) replaces the default of `epochs` passes in corpus order: the library draws no random number, a shuffled order comes from the host.
+Takes the model's state over like train!, and leaves lambda / vsq / logzeta of every document under the final globals when `final_pass`.
+Returns (Sbar, lbar, vbar, Cbar, mref, t): the running statistic (K x V), its tail about mref, and the step counter.
+"""
+function train_stochastic!(model::hipCTM; batch::Integer=4096, epochs::Integer=2, tau0::Real=1.0, kappa::Real=0.7, order::Union{Nothing, Vector{<:Integer}}=nothing,
+		final_pass::Bool=true, niter::Integer=1000, ntol::Real=1/model.K^2, viter::Integer=10, vtol::Real=1/model.K^2)
+	check_train_args([ntol, vtol], [niter, viter], Inf)
+	batch >= 1						|| throw(ArgumentError("batch parameter must be a positive integer."))
+	epochs >= 0						|| throw(ArgumentError("epochs parameter must be a nonnegative integer."))
+	(isfinite(tau0) & (tau0 >= 0))	|| throw(ArgumentError("tau0 parameter must be nonnegative."))
+	(0.5 < kappa <= 1)				|| throw(ArgumentError("kappa parameter must be in (0.5, 1]."))
+	K, M, V = model.K, model.M, model.V
+	cuts = Int64[collect(0:batch:M-1); M]
+	B = length(cuts) - 1
+	steps = Int32.(order === nothing ? repeat(collect(0:B-1), epochs) : order)
+	doc_ptr = Int64[0; cumsum([length(doc.terms) for doc in model.corp])]
+	terms   = Int32.(reduce(vcat, [doc.terms for doc in model.corp]; init=Int[]) .- 1)
+	counts  = Int32.(reduce(vcat, [doc.counts for doc in model.corp]; init=Int[]))
+	h = Ref{Ptr{Cvoid}}(C_NULL)
+	tmvb_check(ccall((:tmvb_ctm_svi_create, LIBTMVB), Cint,
+		(Ptr{Cvoid}, Int64, Int64, Ptr{Int64}, Ptr{Int32}, Ptr{Int32}, Int32, Ptr{Int64}, Int32, Ref{Ptr{Cvoid}}),
+		model.ctx, M, V, doc_ptr, terms, counts, K, cuts, B, h))
+	sbar = zeros(K, V); lbar = zeros(K); vbar = zeros(K); cbar = zeros(K, K); mref = zeros(K); t = Ref{Int64}(0)
+	try
+		beta, beta_old = Matrix{Float64}(model.beta), Matrix{Float64}(model.beta_old)
+		lam, vsq = hcat(model.lambda...), hcat(model.vsq...)
+		tmvb_check(ccall((:tmvb_ctm_svi_set_state, LIBTMVB), Cint,
+			(Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+			 Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}),
+			h[], model.mu, model.sigma, model.invsigma, beta, beta_old, lam, vsq, model.logzeta, C_NULL, C_NULL, C_NULL, C_NULL, C_NULL, C_NULL))
+		tmvb_check(ccall((:tmvb_ctm_svi_set_schedule, LIBTMVB), Cint, (Ptr{Cvoid}, Float64, Float64), h[], tau0, kappa))
+		tmvb_check(ccall((:tmvb_ctm_svi_run, LIBTMVB), Cint, (Ptr{Cvoid}, Ptr{Int32}, Int64, Int32, Float64, Int32, Float64),
+			h[], steps, length(steps), niter, ntol, viter, vtol))
+		final_pass && tmvb_check(ccall((:tmvb_ctm_svi_final_pass, LIBTMVB), Cint, (Ptr{Cvoid}, Int32, Float64, Int32, Float64), h[], niter, ntol, viter, vtol))
+		mu = zeros(K); sg = zeros(K, K); isg = zeros(K, K); beta = zeros(K, V); beta_old = zeros(K, V)
+		lam = zeros(K, M); vsq = zeros(K, M); lz = zeros(M)
+		tmvb_check(ccall((:tmvb_ctm_svi_get_state, LIBTMVB), Cint,
+			(Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+			 Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ref{Int64}),
+			h[], mu, sg, isg, beta, beta_old, lam, vsq, lz, sbar, lbar, vbar, cbar, mref, t))
+		model.mu, model.sigma, model.invsigma, model.beta, model.beta_old = mu, sg, isg, beta, beta_old
+		model.lambda, model.lambda_old, model.vsq, model.logzeta = cols(lam), cols(lam), cols(vsq), lz
+	finally
+		ccall((:tmvb_ctm_svi_destroy, LIBTMVB), Cint, (Ptr{Cvoid},), h[])
+	end
+	update_buffer!(model)                                                        # the resident handle follows: predict / update_elbo! see the trained state
+	model.topics = hip_topics(model.ctx, model.beta)
+	return sbar, lbar, vbar, cbar, mref, t[]
+end
+
 function train!(models::Vector{hipCTM}; iter::Integer=150, tol::Real=1.0, niter::Integer=1000, ntol::Real=1/models[1].K^2, viter::Integer=10, vtol::Real=1/models[1].K^2, checkelbo::Real=1, printelbo::Bool=true)
 	check_train_args([tol, ntol, vtol], [iter, niter, viter], checkelbo)
 	foreach(update_buffer!, models)
