@@ -709,6 +709,41 @@ int tmvb_score_ranks(tmvb_ctx* ctx, int32_t K, int64_t Md, const double* xd, int
 int tmvb_rank_metrics(int64_t Mq, const int64_t* tgt_ptr, const int32_t* rank, const int32_t* n_cand, int32_t nN, const int32_t* Ns, double* recall,
                       double* precision, double* ndcg, double* mrr, double* pct_rank, double* mean, int64_t* counts);
 
+/* ============================== top-n recommendations for CTPF: exclusions fused into the score scan ==============================
+ * For every query the n best database rows outside the query's exclusion list: for a user the n best documents outside the library, with
+ * the roles swapped the n best users outside a document's readers (the reference's consumers, showurecs(model, users, M = 15) and
+ * showdrecs(model, docs, U = 15), read the first 15 entries of a full ranking).  No Md x Mq array and no sort.
+ *
+ * tmvb_score_topn: K in [1, 1024]; database xd, column-major K x Md fp64, queries xq, K x Mq fp64, both on the HOST; per query a list of
+ * 0-based database ids in CSR form (excl_ptr[Mq+1], excl_idx), strictly ascending within a query; an empty list is allowed.  n in
+ * [1, TMVB_NB_TOPN_MAX].  Outputs: idx[Mq][n], score[Mq][n] (fp32), count[Mq].
+ * Features: the rows as given, each value rounded ONCE to fp32, padded to kp exactly as in tmvb_topic_neighbors (TMVB_NB_DOT).
+ * Score: s(q, e) is the fp32 fmaf chain over k = 0 .. K - 1 in ascending order starting from 0 -- what v_mfma_f32_32x32x2_f32 computes when
+ * the K loop feeds its accumulator.  The score of a pair has the same bits as the pair's score in tmvb_score_ranks and tmvb_topic_neighbors.
+ * Order: the reference's reverse(sortperm(.)), as in tmvb_score_ranks: e comes BEFORE t iff s_e > s_t, or s_e == s_t and e > t -- descending
+ * index on ties, NOT the order of tmvb_topic_neighbors.
+ * Result: for query q the first count[q] = min(n, Md - |excl(q)|) rows of [0, Md) \ excl(q) under that order, listed in that order in
+ * idx[q][.] and score[q][.]; slots beyond count[q] hold idx = -1 and score = -inf.  With X = gimel / dalet + zayin / het of a CTPF state as
+ * the database, Y = he / vav as the queries and the users' libraries as exclusions, row u is the first n entries of urecs[u] of
+ * tmvb_ctpf_recommend (up to that unit's own rounding of the scores).
+ * Purity: the result is a pure function of the inputs -- independent of `splits` (0 = the library's choice, > 0 forces that many database
+ * splits, as in tmvb_topic_neighbors), of tile sizes and of the order in which workgroups finish; two calls give the same bits; queries
+ * [a, b) of a call equal the call on that slice (its excl_ptr rebased to 0).  No atomics on global memory.
+ * Device path: a feature kernel (the layout of tmvb_topic_neighbors); a scan kernel -- the tile loop of tmvb_topic_neighbors (a workgroup
+ * owns 128 queries and one database split) with a sorted n-list and its threshold per query in LDS, empty slots (-inf, -1) being the worst
+ * key under this order: an accumulator entry is tested against its query's threshold first (one LDS read), only a survivor is looked up in
+ * its query's exclusion list (binary search on the device), and only a survivor that is not listed is inserted.  Every (query, row) pair is
+ * met once, so an excluded row costs at most one search --; a merge kernel takes the splits x n partial lists of a query to the final n
+ * under the same order (skipped with one split).
+ * info (or NULL): splits, kp, ms_prep / ms_scan / ms_merge = device time of the stages (HIP events around the kernels only).
+ * Errors, judged before the device is touched: K outside [1, 1024], n outside [1, TMVB_NB_TOPN_MAX], Md <= 0, Mq <= 0, Md >= 2^31,
+ * splits < 0 or > Md, a NULL argument, 2^31 - 1 or more listed ids -> TMVB_EINVAL; excl_ptr not non-decreasing from 0, a non-finite entry,
+ * an id out of range or not strictly ascending -> TMVB_ESHAPE; then ctx == NULL without a visible device -> TMVB_ENODEVICE (there is no
+ * CPU path). */
+typedef struct { int32_t splits, kp; float ms_prep, ms_scan, ms_merge; } tmvb_rectopn_info_t;
+int tmvb_score_topn(tmvb_ctx* ctx, int32_t K, int64_t Md, const double* xd, int64_t Mq, const double* xq, const int64_t* excl_ptr,
+                    const int32_t* excl_idx, int32_t n, int32_t splits, int32_t* idx, float* score, int32_t* count, tmvb_rectopn_info_t* info);
+
 /* ============================== stochastic (minibatch) training for LDA: stepwise EM ==============================
  * New: the reference's train! moves alpha and beta once per walk over the whole corpus (src/LDA.jl:161-187); the closest precedent for statistics
  * gathered batch by batch is v0.6/src/gpuLDA.jl:200-225.  Here the globals move once per BATCH (Cappe & Moulines / Liang & Klein's stepwise EM, the

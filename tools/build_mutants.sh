@@ -1,5 +1,5 @@
 #!/bin/bash
-# The deliberately WRONG libraries of tests/test_mutants_gpu.py, tests/test_heldout_mutant_gpu.py, tests/test_coherence_mutant_gpu.py, tests/test_neighbors_mutant_gpu.py and tests/test_recranks_mutant_gpu.py (negative controls of the parity suite), each = the shipped objects with one
+# The deliberately WRONG libraries of tests/test_mutants_gpu.py, tests/test_heldout_mutant_gpu.py, tests/test_coherence_mutant_gpu.py, tests/test_neighbors_mutant_gpu.py, tests/test_recranks_mutant_gpu.py and tests/test_rectopn_mutant_gpu.py (negative controls of the parity suite), each = the shipped objects with one
 # translation unit recompiled under a -DTMVB_MUTANT_* flag (csrc/tmvb_internal.h lists them):
 #   topicmodelsvb.jl_amd/libtmvb_hip_mut_lda_eps.so     epsilon dropped from LDA's phi / gamma            (src/LDA.jl:152, :145)
 #   topicmodelsvb.jl_amd/libtmvb_hip_mut_ctpf_bet.so    log bet for log vav in CTPF's xi                   (src/CTPF.jl:336 vs src/gpuCTPF.jl:624)
@@ -14,6 +14,7 @@
 #   topicmodelsvb.jl_amd/libtmvb_hip_mut_coherence_tail.so  pair kernel of the co-document counts without the last partial 64-document word (tests/test_coherence_mutant_gpu.py)
 #   topicmodelsvb.jl_amd/libtmvb_hip_mut_neighbors_tail.so  scan kernel of the nearest-document search without the last partial database tile (tests/test_neighbors_mutant_gpu.py)
 #   topicmodelsvb.jl_amd/libtmvb_hip_mut_recranks_tail.so  scan kernel of the held-out ranks without the last partial database tile (tests/test_recranks_mutant_gpu.py)
+#   topicmodelsvb.jl_amd/libtmvb_hip_mut_rectopn_last_excl.so  scan kernel of the top-n recommendations whose search never finds the last id of an exclusion list (tests/test_rectopn_mutant_gpu.py)
 #   topicmodelsvb.jl_amd/libtmvb_hip_mut_ctm_empty_tail.so  a CTM shard without documents keeps the previous iteration's scatter matrix in its statistics tail (tests/test_sharded_oracle_gpu.py, ragged6)
 #   topicmodelsvb.jl_amd/libtmvb_hip_mut_svi_keep_stats.so  fused global update of stochastic LDA training without the clearing of the batch's statistics (tests/test_svi_mutant_gpu.py)
 #   topicmodelsvb.jl_amd/libtmvb_hip_mut_ctm_svi_no_recentre.so  tail kernel of stochastic CTM training that blends the running scatter matrix without recentring it on the current mu (tests/test_ctm_svi_mutant_gpu.py)
@@ -35,6 +36,7 @@ tools/build_variant.sh mut_lda_stale_parts tmvb_lda.hip -DTMVB_MUTANT_LDA_STALE_
 tools/build_variant.sh mut_coherence_tail tmvb_coherence.hip -DTMVB_MUTANT_CODF_DROP_TAIL=1 &
 tools/build_variant.sh mut_neighbors_tail tmvb_neighbors.hip -DTMVB_MUTANT_NB_DROP_TAIL=1 &
 tools/build_variant.sh mut_recranks_tail tmvb_recranks.hip -DTMVB_MUTANT_RK_DROP_TAIL=1 &
+tools/build_variant.sh mut_rectopn_last_excl tmvb_rectopn.hip -DTMVB_MUTANT_TOPN_MISS_LAST_EXCL=1 &
 tools/build_variant.sh mut_ctm_empty_tail tmvb_ctm.hip -DTMVB_MUTANT_CTM_EMPTY_SHARD_TAIL=1 &
 tools/build_variant.sh mut_svi_keep_stats tmvb_lda_svi.hip -DTMVB_MUTANT_SVI_KEEP_BATCH_STATS=1 &
 tools/build_variant.sh mut_ctm_svi_no_recentre tmvb_ctm_svi.hip -DTMVB_MUTANT_CTM_SVI_NO_RECENTRE=1 &

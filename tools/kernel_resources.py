@@ -42,6 +42,8 @@ BENCHED = {
     "nb_feature_kernel": 0, "nb_scan_kernel": 0, "nb_merge_kernel": 0,
     # held-out recommendation ranks (tools/recs_eval_bench.py): features, pair scores, target sort, the fused MFMA scan / count, the exclusion fix
     "rk_feature_kernel": 0, "rk_pairs_kernel": 0, "rk_sort_kernel": 0, "rk_scan_kernel": 0, "rk_fix_kernel": 0,
+    # top-n recommendations (tools/rectopn_bench.py): features, the fused MFMA scan / exclusion search / top-n, the merge of the splits' lists
+    "rt_feature_kernel": 0, "rt_scan_kernel": 0, "rt_merge_kernel": 0,
     # stochastic LDA training (tools/svi_bench.py): the fused global update -- blend + partial row sums, then normalise
     "svi_blend_kernel<": 0, "svi_norm_kernel": 0,
     # stochastic CTM training (tools/ctm_svi_bench.py): the tail of the fused global update -- recentre in fp64, blend (the K x V part is the two above)

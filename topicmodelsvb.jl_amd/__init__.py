@@ -20,6 +20,7 @@ from .coherence import CoherenceResult, coherence, coherence_from_counts, cohere
 from .neighbors import NeighborsResult, docsim, neighbors_raw, topic_proportions
 from .recs_eval import (HeldReaders, RecEvalResult, rank_metrics, rank_metrics_raw, rec_eval, rec_quality, rec_ranks_raw, split_readers,
                         split_readers_raw)
+from .recs_topn import RecTopN, rec_topn_raw, recommend_topn
 from .lda_svi import gpuLDAStochastic, gpu_train_stochastic, svi_cuts, svi_order, svi_rho
 from .ctm_svi import gpuCTMStochastic, gpu_train_ctm_stochastic
 
@@ -32,5 +33,6 @@ __all__ = ["CorpusError", "DocumentError", "EngineError", "TopicModelError", "bu
            "CoherenceResult", "coherence", "coherence_from_counts", "coherence_from_counts_raw", "codocfreq_raw",
            "NeighborsResult", "docsim", "neighbors_raw", "topic_proportions",
            "HeldReaders", "RecEvalResult", "rank_metrics", "rank_metrics_raw", "rec_eval", "rec_quality", "rec_ranks_raw", "split_readers", "split_readers_raw",
+           "RecTopN", "rec_topn_raw", "recommend_topn",
            "gpuLDAStochastic", "gpu_train_stochastic", "svi_cuts", "svi_order", "svi_rho",
            "gpuCTMStochastic", "gpu_train_ctm_stochastic"]

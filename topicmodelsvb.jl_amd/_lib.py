@@ -20,7 +20,7 @@ LIB_PATH = os.path.join(_HERE, "libtmvb_hip.so")
 # experiments only (tools/build_variant.sh): TMVB_LIB_VARIANT=<name> loads libtmvb_hip_<name>.so, the same sources built with extra -D
 # flags, so that a compile-time variant can be timed against the shipped library inside ONE gpurun call (boxes differ by up to 8 %)
 _VARIANT = os.environ.get("TMVB_LIB_VARIANT", "")
-SOURCES = ["tmvb_core.hip", "tmvb_comm.hip", "tmvb_lda.hip", "tmvb_flda.hip", "tmvb_ctm.hip", "tmvb_ctpf.hip", "tmvb_ctpf_recs.hip", "tmvb_topics.hip", "tmvb_gencorp.hip", "tmvb_heldout.hip", "tmvb_coherence.hip", "tmvb_neighbors.hip", "tmvb_recranks.hip", "tmvb_lda_svi.hip", "tmvb_ctm_svi.hip"]
+SOURCES = ["tmvb_core.hip", "tmvb_comm.hip", "tmvb_lda.hip", "tmvb_flda.hip", "tmvb_ctm.hip", "tmvb_ctpf.hip", "tmvb_ctpf_recs.hip", "tmvb_topics.hip", "tmvb_gencorp.hip", "tmvb_heldout.hip", "tmvb_coherence.hip", "tmvb_neighbors.hip", "tmvb_recranks.hip", "tmvb_rectopn.hip", "tmvb_lda_svi.hip", "tmvb_ctm_svi.hip"]
 
 OK, EINVAL, ESHAPE, ECORPUS, ENOMEM, EHIP, ENONFINITE, ENODEVICE, ERCCL = range(9)
 
@@ -45,6 +45,11 @@ class CorpusInfo(C.Structure):
     _fields_ = [(n, C.c_int64) for n in ("M", "V", "U", "nnz", "nR", "sum_counts", "sum_ratings", "max_doc_len",
                                          "max_readers", "n_empty_docs", "n_docs_with_duplicate_terms",
                                          "n_docs_with_duplicate_readers")]
+
+
+class RecTopNInfo(C.Structure):
+    """tmvb_rectopn_info_t"""
+    _fields_ = [("splits", C.c_int32), ("kp", C.c_int32), ("ms_prep", C.c_float), ("ms_scan", C.c_float), ("ms_merge", C.c_float)]
 
 
 def _sources():
@@ -167,6 +172,7 @@ _lib = None
 P_i64 = C.POINTER(C.c_int64)
 P_i32 = C.POINTER(C.c_int32)
 P_dbl = C.POINTER(C.c_double)
+P_f32 = C.POINTER(C.c_float)
 VP = C.c_void_p
 
 
@@ -213,6 +219,9 @@ def lib():
         L.tmvb_last_error.restype = C.c_char_p
         L.tmvb_abi_version.restype = C.c_int
         L.tmvb_device_count.restype = C.c_int
+        L.tmvb_score_topn.restype = C.c_int
+        L.tmvb_score_topn.argtypes = [VP, C.c_int32, C.c_int64, P_dbl, C.c_int64, P_dbl, P_i64, P_i32, C.c_int32, C.c_int32, P_i32, P_f32, P_i32,
+                                      C.POINTER(RecTopNInfo)]
         _lib = L
     return _lib
 

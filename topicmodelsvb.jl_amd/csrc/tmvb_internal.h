@@ -192,6 +192,8 @@ int tmvb_check_ctx_or_device(const char* fn, tmvb_ctx* ctx);
 //   TMVB_MUTANT_NB_DROP_TAIL        the scan kernel of the nearest-document search (tmvb_neighbors.hip) skips the last, partial database tile (Md not a multiple of
 //                                   TMVB_NB_TILE_DB); tests/test_neighbors_mutant_gpu.py
 //   TMVB_MUTANT_RK_DROP_TAIL        the scan kernel of the held-out ranks (tmvb_recranks.hip) skips the last, partial database tile; tests/test_recranks_mutant_gpu.py
+//   TMVB_MUTANT_TOPN_MISS_LAST_EXCL the scan kernel of the top-n recommendations (tmvb_rectopn.hip) never finds the last id of an exclusion list: a binary search
+//                                   off by one at its upper end; tests/test_rectopn_mutant_gpu.py
 //   TMVB_MUTANT_CTM_EMPTY_SHARD_TAIL  ctm_reduce_docs_on (tmvb_ctm.hip) does not clear the scatter tail of a shard without documents: the empty rank hands the previous
 //                                   iteration's all-reduced scatter matrix back into the next all-reduce; only a partition with an empty rank, run for two iterations
 //                                   against the oracle, shows it (tests/test_sharded_oracle_gpu.py, ragged6)

@@ -1,5 +1,5 @@
-// tmvb_nbtile.h -- what tmvb_neighbors.hip and tmvb_recranks.hip share: the fp32 feature layout [M][kp], the LDS staging of a 128-row operand
-// tile and the 2 x 2 accumulator K-chunk loop on v_mfma_f32_32x32x2_f32.  Device code only; each unit keeps its own kernels (and their names).
+// tmvb_nbtile.h -- what tmvb_neighbors.hip, tmvb_recranks.hip and tmvb_rectopn.hip share: the fp32 feature layout [M][kp], the LDS staging of a
+// 128-row operand tile and the 2 x 2 accumulator K-chunk loop on v_mfma_f32_32x32x2_f32.  Device code only; each unit keeps its own kernels (and their names).
 //
 // Layout.  kp = K rounded up to a multiple of 4, pads zero.  Inside every group of four the values sit in the order k = 0, 2, 1, 3 (nb_perm): a
 // lane of the lower half of a wave then reads the k = 4t and 4t + 2 of its row with ONE 8-byte read and a lane of the upper half k = 4t + 1 and

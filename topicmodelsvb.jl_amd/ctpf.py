@@ -200,6 +200,13 @@ class gpuCTPF:
         self.urecs = [ur[u, :uc[u]] + 1 for u in range(U)]
         return ms0.value, ms1.value
 
+    def recommend_topn(self, topn: int = 15, by: str = "user", ids=None, splits: int = 0):
+        """The `topn` best entries of urecs[u] (by="user") or drecs[d] (by="doc") for the 1-based `ids` (default all) from the
+        device-resident state, without the M x U rankings of recommend(): recs_topn.recommend_topn on this handle's context."""
+        from .recs_topn import recommend_topn
+        self.update_host()
+        return recommend_topn(self, topn, by, ids, splits)
+
     def train(self, iter: int = 150, tol: float = 1.0, viter: int = 10, vtol: float | None = None, checkelbo=1,
               printelbo: bool = True, recs: bool = True):
         """train!(model::gpuCTPF; ...) src/gpuCTPF.jl:677-705.  recs=False skips the M x U recommendation tail (:711-731)."""

@@ -1243,6 +1243,35 @@ function score_ranks(xd::Matrix{Float64}, xq::Matrix{Float64}, excl_ptr::Vector{
 			ms=(prep=info.ms_prep, pairs=info.ms_pairs, scan=info.ms_scan, fix=info.ms_fix), splits=Int(info.splits))
 end
 
+"tmvb_rectopn_info_t (include/tmvb.h), field for field."
+mutable struct TmvbRecTopNInfo
+	splits::Int32; kp::Int32
+	ms_prep::Float32; ms_scan::Float32; ms_merge::Float32
+	TmvbRecTopNInfo() = new(0, 0, 0f0, 0f0, 0f0)
+end
+
+"""
+(idx, score, count, ms, splits): for every query the `topn` best database rows outside its exclusion list under reverse(sortperm(.)) -- the
+head of urecs / drecs without the full ranking.  xd: K x Md, xq: K x Mq; excl_ptr / excl_idx: CSR lists of 0-based database ids, strictly
+ascending inside a query.  idx[j, q] is 1-based, 0 past count[q].
+"""
+function score_topn(xd::Matrix{Float64}, xq::Matrix{Float64}, excl_ptr::Vector{Int64}, excl_idx::Vector{Int32}; topn::Integer=15, splits::Integer=0,
+		device::Integer=0)
+	(1 <= topn <= 64)					|| throw(ArgumentError("topn must be an integer in [1, 64]."))
+	K, Md = size(xd); Mq = size(xq, 2)
+	idx = zeros(Int32, topn, Mq); score = zeros(Float32, topn, Mq); count = zeros(Int32, Mq)	# column-major (j, q) = C's [q][j]
+	info = TmvbRecTopNInfo()
+	ctx = tmvb_context(device)
+	GC.@preserve info xd xq excl_ptr excl_idx idx score count begin
+		rc = ccall((:tmvb_score_topn, LIBTMVB), Cint,
+			(Ptr{Cvoid}, Int32, Int64, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Int64}, Ptr{Int32}, Int32, Int32, Ptr{Int32}, Ptr{Float32}, Ptr{Int32}, Ptr{Cvoid}),
+			ctx, K, Md, xd, Mq, xq, excl_ptr, excl_idx, topn, splits, idx, score, count, pointer_from_objref(info))
+		tmvb_destroy_context(ctx)
+		tmvb_check(rc)
+	end
+	return (idx=Int.(idx) .+ 1, score=score, count=Int.(count), ms=(prep=info.ms_prep, scan=info.ms_scan, merge=info.ms_merge), splits=Int(info.splits))
+end
+
 """
 recall / precision / ndcg (length(topn) x Mq), mrr, pct_rank (Mq; NaN for a query without targets), their means over the queries with targets
 (recall@topn, precision@topn, ndcg@topn, mrr, pct_rank, in that order), the number of such queries and the number of targets.
