@@ -19,4 +19,4 @@ def run(viter, n=5, warm=3):
     return np.mean(ts), gm.sweep_hist().tolist()
 for viter in [int(x) for x in os.environ.get("VITERS", "10").split(",")]:
     ms, hist = run(viter)
-    print(f"flags={os.environ.get('TMVB_DEBUG_FLAGS','0')} viter={viter} estep_ms={ms:.3f} sweeps={hist}", flush=True)
+    print(f"viter={viter} estep_ms={ms:.3f} sweeps={hist}", flush=True)

@@ -58,7 +58,7 @@ void rccl_bind()
         a.so = dlopen(path, RTLD_NOW | RTLD_LOCAL);
         if (!a.so) { const char* de = dlerror(); why = de ? de : (std::string(path) + " not found"); }
     };
-    if (const char* e = getenv("TMVB_RCCL_LIB")) {
+    if (const char* e = tmvb_env_str("TMVB_RCCL_LIB")) {
         // an explicit choice is used as given: if it does not load, say so instead of silently binding another copy
         open(e);
         if (!a.so) { a.error = "RCCL is not available: TMVB_RCCL_LIB=" + std::string(e) + ": " + why; return; }

@@ -472,13 +472,6 @@ static inline int tmvb_colsum2(tmvb_ctx* ctx, int K, tmvb_colsum_job j0, tmvb_co
 // gather-side statistics pass over an inverted index (tmvb_termstats.h)
 // true when the statistics pass recomputes the per-token weights (no wtok stores needed in the document kernels)
 static inline bool tmvb_termstats_recomputes(int KP, bool e_padded) { return e_padded && KP / 4 <= 32; }
-// column chunks per lane of the PAD form of the recompute pass (tmvb_termstats.h): default 1 at KP = 52 (the round-4 form), 4 at KP = 100;
-// TMVB_TS_CPL = 1 | 2 | 4 overrides (A/B)
-static inline int tmvb_termstats_cpl(int lpr)
-{
-    static const int env = [] { const char* e = getenv("TMVB_TS_CPL"); const int c = e ? atoi(e) : 0; return (c == 1 || c == 2 || c == 4) ? c : 0; }();
-    return env ? env : (lpr == 25 ? 4 : 1);
-}
 
 // slice >= 0: only the ids of vocabulary slice `slice` of an index built with id cuts (tmvb_inv_index::slice_*)
 static inline int tmvb_launch_termstats(tmvb_ctx* ctx, int nslot, int KP, bool e_padded, const tmvb_inv_index& ix,
@@ -506,8 +499,7 @@ static inline int tmvb_launch_termstats(tmvb_ctx* ctx, int nslot, int KP, bool e
             // PAD form: rows zero-padded to 4 * LANES floats, 32-bit byte offsets into E, 24-bit document ids (tmvb_termstats.h)
             const int lanes = lpr <= 16 ? 16 : 32;
             const bool pad = tp.estride >= 4 * lanes && ix.n_docs < (1 << 24) && (uint64_t)ix.n_docs * (uint64_t)tp.estride * 4u < (1ull << 32) &&
-                             !(getenv("TMVB_STATS_PAD") && atoi(getenv("TMVB_STATS_PAD")) == 0);
-            const int cpl = tmvb_termstats_cpl(lpr);
+                             tmvb_env_on("TMVB_STATS_PAD", true);     // (0: the unpadded form, what >= 2^24 documents get, at test size)
             // TS(...): the instantiation, or -- tp.logz set, translation units that define TMVB_TS_LOGZ (LDA) -- its LOGZ form, which also leaves the
             // chunk's sum of val * log2(normaliser) for update_elbo!
 #ifdef TMVB_TS_LOGZ
@@ -517,12 +509,9 @@ static inline int tmvb_launch_termstats(tmvb_ctx* ctx, int nslot, int KP, bool e
 #define TS(LPRV, LANESV, PADV, CPLV) do { TMVB_REQUIRE(tp.logz == nullptr, TMVB_EINVAL, "statistics pass: no log-normaliser form in this translation unit"); \
                                           hipLaunchKernelGGL((termstats_recompute_kernel<LPRV, LANESV, PADV, CPLV, false>), grid, block, 0, st, tp, lpr); } while (0)
 #endif
-            if (lpr == 13 && pad && cpl == 2) TS(13, 8, true, 2);
-            else if (lpr == 13 && pad && cpl == 4) TS(13, 4, true, 4);
-            else if (lpr == 25 && pad && cpl == 2) TS(25, 16, true, 2);
-            else if (lpr == 25 && pad && cpl == 4) TS(25, 8, true, 4);
-            else if (lpr == 13 && pad) TS(13, 16, true, 1);
-            else if (lpr == 25 && pad) TS(25, 32, true, 1);
+            // (the PAD form at KP = 100 holds four column chunks per lane, 8 lanes per row slot: tmvb_termstats.h)
+            if (lpr == 13 && pad) TS(13, 16, true, 1);
+            else if (lpr == 25 && pad) TS(25, 8, true, 4);
             else if (lpr == 13) TS(13, 16, false, 1);
             else if (lpr == 25) TS(25, 32, false, 1);
             else if (lpr <= 16) TS(0, 16, false, 1);
@@ -562,8 +551,7 @@ static inline int tmvb_launch_termstats2(tmvb_ctx* ctx, int nslot, int KP, const
     const int lanes = lpr <= 16 ? 16 : 32;
     const int64_t nd = std::max(ix0.n_docs, ix1.n_docs);
     const bool pad = tp0.estride >= 4 * lanes && tp1.estride == tp0.estride && nd < (1 << 24) && (uint64_t)nd * (uint64_t)tp0.estride * 4u < (1ull << 32) &&
-                     !(getenv("TMVB_STATS_PAD") && atoi(getenv("TMVB_STATS_PAD")) == 0);
-    const int cpl = tmvb_termstats_cpl(lpr);
+                     tmvb_env_on("TMVB_STATS_PAD", true);
     TMVB_REQUIRE((tp0.logz == nullptr) == (tp1.logz == nullptr), TMVB_EINVAL, "statistics pass pair: log-normaliser sums for both indices or for neither");
 #ifdef TMVB_TS_LOGZ
 #define TS2(LPRV, LANESV, PADV, CPLV) do { if (tp0.logz) hipLaunchKernelGGL((termstats_recompute2_kernel<LPRV, LANESV, PADV, CPLV, true>), grid, block, 0, st, tp0, tp1, lpr); \
@@ -572,9 +560,7 @@ static inline int tmvb_launch_termstats2(tmvb_ctx* ctx, int nslot, int KP, const
 #define TS2(LPRV, LANESV, PADV, CPLV) do { TMVB_REQUIRE(tp0.logz == nullptr, TMVB_EINVAL, "statistics pass pair: no log-normaliser form in this translation unit"); \
                                            hipLaunchKernelGGL((termstats_recompute2_kernel<LPRV, LANESV, PADV, CPLV, false>), grid, block, 0, st, tp0, tp1, lpr); } while (0)
 #endif
-    if (lpr == 13 && pad && cpl == 2) TS2(13, 8, true, 2);
-    else if (lpr == 13 && pad && cpl == 4) TS2(13, 4, true, 4);
-    else if (lpr == 13 && pad) TS2(13, 16, true, 1);
+    if (lpr == 13 && pad) TS2(13, 16, true, 1);
     else if (lpr == 13) TS2(13, 16, false, 1);
     else if (lpr == 25) TS2(25, 32, false, 1);
     else if (lpr <= 16) TS2(0, 16, false, 1);

@@ -48,7 +48,7 @@ extern "C" int tmvb_device_count(void)
 // see tmvb_internal.h
 bool tmvb_streams_pooled()
 {
-    static const bool on = [] { const char* e = getenv("TMVB_STREAM_POOL"); return e && atoi(e) != 0; }();   // opt-in, see tmvb_internal.h
+    static const bool on = tmvb_env_on("TMVB_STREAM_POOL", false);   // opt-in, see tmvb_internal.h
     return on;
 }
 
@@ -64,8 +64,7 @@ unsigned tmvb_event_flags()
         // system-scope fence of a default event buys nothing -- and costs: a 16 100-document LDA shard, whose iteration crosses streams four
         // times, runs 0.172 / 0.173 ms per iteration without it against 0.187 / 0.182 with (run r4ai, alternating); whole corpus and CTPF
         // inside the noise
-        const char* e = getenv("TMVB_EVENT_FLAGS");
-        const int v = e ? atoi(e) : 1;
+        const int v = tmvb_env_int("TMVB_EVENT_FLAGS", 1);
         return (unsigned)hipEventDisableTiming | (v == 1 ? (unsigned)hipEventDisableSystemFence : v == 2 ? (unsigned)hipEventReleaseToDevice : 0u);
     }();
     return f;
@@ -388,7 +387,7 @@ int tmvb_build_inv_index(tmvb_ctx* ctx, int64_t M, int64_t n_ids, const int64_t*
     // gpuLDA / gpuCTM constructor takes on SYN-NSF) split the documents into T contiguous ranges of equal postings, one host thread each: per-range histograms,
     // one prefix over (id, range), then every range scatters its own documents from its own cursors -- the same positions the one-thread loop assigns
     // (TMVB_CREATE_THREADS=0, or fewer than 2^20 postings: one thread).
-    static const int thread_env = [] { const char* e = getenv("TMVB_CREATE_THREADS"); return e ? atoi(e) : -1; }();
+    static const int thread_env = tmvb_env_int("TMVB_CREATE_THREADS", -1);
     int T = 1;
     if (thread_env != 0 && nnz_all >= (1 << 20)) {
         const unsigned hw = std::thread::hardware_concurrency();
@@ -481,12 +480,12 @@ int tmvb_build_inv_index(tmvb_ctx* ctx, int64_t M, int64_t n_ids, const int64_t*
     // postings per chunk (= per wave of the statistics pass): TMVB_CHUNK (256) for a corpus that fills the device with chunks of that size; a SMALL index (CTPF's
     // SYN-CITEU, an 8-GPU LDA shard: ~1.2 M postings = 4 800 chunks of 256 for 1 024 SIMDs that could hold 16 waves each) is cut finer, so that the gather-latency-bound
     // pass has more rows in flight (round 6; TMVB_CHUNK_SIZE overrides)
-    static const int chunk_env = [] { const char* e = getenv("TMVB_CHUNK_SIZE"); return e ? std::max(16, atoi(e)) : 0; }();
+    static const int chunk_env = tmvb_env_str("TMVB_CHUNK_SIZE") ? std::max(16, tmvb_env_int("TMVB_CHUNK_SIZE", 0)) : 0;
     const int64_t n_post = nnz;                          // postings of this index (of this piece)
     const int64_t CHUNK = chunk_env ? chunk_env : (n_post < TMVB_SMALL_INDEX_POSTINGS ? TMVB_CHUNK_SMALL : TMVB_CHUNK);
-    static const int class_env = [] { const char* e = getenv("TMVB_STATS_CLASSES"); return e ? atoi(e) : -1; }();
-    static const int64_t class_docs = [] { const char* e = getenv("TMVB_CLASS_DOCS"); return e ? (int64_t)atoi(e) : (int64_t)TMVB_CLASS_DOCS; }();
-    static const int64_t class_min = [] { const char* e = getenv("TMVB_CLASS_MIN_POSTINGS"); return e ? (int64_t)atoi(e) : (int64_t)TMVB_CLASS_MIN_POSTINGS; }();
+    static const int class_env = tmvb_env_int("TMVB_STATS_CLASSES", -1);
+    static const int64_t class_docs = tmvb_env_int("TMVB_CLASS_DOCS", TMVB_CLASS_DOCS);
+    static const int64_t class_min = tmvb_env_int("TMVB_CLASS_MIN_POSTINGS", TMVB_CLASS_MIN_POSTINGS);
     int NC = 8 * (int)((ndocs + 8 * class_docs - 1) / (8 * class_docs));
     if (class_env >= 0) NC = 8 * ((class_env + 7) / 8);               // classes are emitted in rounds of 8 (one per XCD): round up
     if (ndocs < 4 * class_docs && class_env < 0) NC = 0;               // everything fits a couple of L2s anyway

@@ -58,7 +58,9 @@ struct CtmParams {
     double ntol;
     int viter;
     double vtol;
-    int debug;                // TMVB_DEBUG_FLAGS (profiling experiments only): 1 = skip vsq Newton, 2 = diagonal solve instead of GJ
+    int debug;                // always 0.  Its bits once skipped phases for timing experiments; ctm_estep_kernel, ctm_estep_batch_kernel and ctm_estep_quad_kernel keep
+                              // the (never taken) tests because their register allocation is worse without them: scratch per lane 372 -> 380 B (batch) and
+                              // 88 -> 116 B (quad) at KP = 52, two more VGPRs in every ctm_estep_kernel (tools/kernel_resources.py)
     int store_w;              // KP > 128: the statistics pass reads stored per-token weights instead of recomputing them
     // filtered CTM only (src/fCTM.jl)
     const float* L = nullptr;         // [V][KP] log(beta + eps), pads 0
@@ -629,9 +631,9 @@ static void ctm_generic_cg_shape(int KP, int max_waves, int* waves, int* tile_ro
     auto rows_for = [&](int w) { const int64_t f = (int64_t)(room / (size_t)w) - 4 * KP; return (int)std::max<int64_t>(0, f / (KP + 6)); };
     int w = max_waves;
     while (w > 4 && rows_for(w) < 24) --w;
-    if (const char* e = getenv("TMVB_CTM_CG_WAVES")) w = std::min(max_waves, std::max(1, atoi(e)));
+    if (tmvb_env_str("TMVB_CTM_CG_WAVES")) w = std::min(max_waves, std::max(1, tmvb_env_int("TMVB_CTM_CG_WAVES", 0)));
     int t = std::min(128, rows_for(w)) & ~3;
-    if (const char* e = getenv("TMVB_CTM_CG_TILE")) t = std::min(t, std::max(4, atoi(e) & ~3));
+    if (tmvb_env_str("TMVB_CTM_CG_TILE")) t = std::min(t, std::max(4, tmvb_env_int("TMVB_CTM_CG_TILE", 0) & ~3));
     *waves = w; *tile_rows = std::max(4, t);
 }
 
@@ -1552,8 +1554,8 @@ extern "C" int tmvb_ctm_create(tmvb_ctx* ctx, tmvb_corpus* corp, int32_t K, tmvb
     tmvb_create_guard<tmvb_ctm, tmvb_ctm_destroy> guard{h};      // every early return below destroys h
     h->ctx = ctx; h->corp = corp; h->K = K; h->KP = tmvb_kpad(K);
     h->nslot = (K + 63) / 64; h->NB = (K + 31) / 32;
-    { const char* e = getenv("TMVB_CTM_ELBO_PARTS"); h->parts_env = e ? atoi(e) : 1; }
-    h->generic = !ctm_kp_supported(h->KP) || [] { const char* e = getenv("TMVB_CTM_FORCE_GENERIC"); return e && atoi(e) != 0; }();   // (the env: measurements)
+    h->parts_env = tmvb_env_int("TMVB_CTM_ELBO_PARTS", 1);
+    h->generic = !ctm_kp_supported(h->KP);
     h->M = corp->info.M; h->V = corp->info.V; h->M_total = h->M;
     const size_t KM = (size_t)K * h->M, KPV = (size_t)h->KP * h->V + 4;
     h->docs_per_wave = 256;
@@ -1579,22 +1581,20 @@ extern "C" int tmvb_ctm_create(tmvb_ctx* ctx, tmvb_corpus* corp, int32_t K, tmvb
     }
     {
         // lane-per-document kernel: the default for KP <= 52 (K <= 50); TMVB_CTM_BATCH=0 selects the wave-per-document kernels
-        const char* e = getenv("TMVB_CTM_BATCH");
         // (a lane walks its document's tokens one after the other: documents of thousands of unique terms would serialise their wave
         // on them, so THOSE documents -- not the corpus: round 2 sent every document of a corpus with one such document there -- keep
         // the wave-per-document kernel, which spreads a document's tokens over the lanes; h->n_long below)
         // (its token phase addresses the token arrays and the topic table with unsigned 32-bit byte offsets)
         h->batch = !h->generic && h->KP <= 52 && corp->info.nnz < (1ll << 30) && (int64_t)h->KP * h->V < (1ll << 30) && h->V < (1 << 24) &&
-                   !(e && atoi(e) == 0);
-        if (const char* t = getenv("TMVB_CTM_CG_TOL")) h->cg_tol = std::max(1e-7f, (float)atof(t));
-        if (const char* t = getenv("TMVB_CTM_CG_ABS")) h->cg_abs = std::max(0.0f, (float)atof(t));
+                   tmvb_env_on("TMVB_CTM_BATCH", true);
+        if (const char* t = tmvb_env_str("TMVB_CTM_CG_TOL")) h->cg_tol = std::max(1e-7f, (float)atof(t));
+        if (const char* t = tmvb_env_str("TMVB_CTM_CG_ABS")) h->cg_abs = std::max(0.0f, (float)atof(t));
         if ((rc = dmalloc(&h->d_bt_sdiag, 64)) || (rc = dmalloc(&h->d_bt_muf, 64)) || (rc = dmalloc(&h->d_cg_iters, 16)) ||
             (rc = dmalloc(&h->d_q_S, (size_t)4 * (((size_t)h->KP * h->KP / 4 + 15) / 16 * 16) + 64)) || (rc = dmalloc(&h->d_q_sd, 64)) || (rc = dmalloc(&h->d_q_mu, 64)) ||
             (rc = dmalloc(&h->d_doc_newton, (size_t)std::max<int64_t>(h->M, 1))) || (rc = dmalloc(&h->d_doc_order0, (size_t)std::max<int64_t>(h->M, 1))) || (rc = dmalloc(&h->d_doc_order_q, (size_t)std::max<int64_t>(h->M, 1))) || (rc = dmalloc(&h->d_wave_keys, CTM_WAVESORT_MAX)))
             return rc;
         // regrouping pays when a chunk of the length-sorted order is still homogeneous in length: corpora of >= 4 chunks
-        const char* r = getenv("TMVB_CTM_REORDER");
-        h->reorder = h->batch && h->M >= 4 * CTM_REORDER_CHUNK && !(r && atoi(r) == 0);
+        h->reorder = h->batch && h->M >= 4 * CTM_REORDER_CHUNK && tmvb_env_on("TMVB_CTM_REORDER", true);
     }
     std::vector<int32_t> order((size_t)h->M);
     std::iota(order.begin(), order.end(), 0);
@@ -1609,9 +1609,8 @@ extern "C" int tmvb_ctm_create(tmvb_ctx* ctx, tmvb_corpus* corp, int32_t K, tmvb
         // 7 waves per CU), and the Newton steps -- 97 % of the kernel -- never touch it.  A 32-row window (8 KB) that
         // longer documents stream through every sweep (L2-resident beta rows, LDS-DMA) lets the register file decide
         // the occupancy instead: 7.76 -> 5.97 ms per E-step on 32 000 SYN-NSF documents (64 / 24 / 16 / 8 KB: 7.76 / 6.80 /
-        // 6.03 / 5.94 ms).  TMVB_CTM_MAX_TILE_KB overrides.
-        size_t cap = 8 * 1024;
-        if (const char* e = getenv("TMVB_CTM_MAX_TILE_KB")) cap = std::max<size_t>(4, (size_t)atoi(e)) * 1024;
+        // 6.03 / 5.94 ms).
+        const size_t cap = 8 * 1024;
         tmvb_build_lds_buckets(len, order, h->batch ? h->n_long : h->M, h->KP, -1, 3, h->buckets, cap);   // batch: the long documents only
     }
     if (h->M) TMVB_HIP(hipMemcpyAsync(h->d_doc_order, order.data(), (size_t)h->M * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
@@ -1744,15 +1743,14 @@ template <bool FILT>
 static int ctm_launch_generic(tmvb_ctm* h, CtmParams p, double ntol)
 {
     tmvb_ctx* ctx = h->ctx;
-    const char* ecg = getenv("TMVB_CTM_GENERIC_CG");          // (read per launch: the tests run both forms in one process)
-    const bool use_cg = !(ecg && atoi(ecg) == 0);
+    const bool use_cg = tmvb_env_on("TMVB_CTM_GENERIC_CG", true);   // (read per launch: the tests run both forms in one process)
     h->generic_cg = use_cg;
     if (use_cg) {
         // instantiation by register budget: TMVB_CTM_CG_MAXW = 8 / 12 / 16 overrides the choice (measurements)
         // (measured on SYN-NSF, ms per E-step at iteration 30: K = 53: 16 waves / 128 VGPRs 7.9, 12 / 168 8.1, 8 / 256 9.8;  K = 64: 9.0, 9.1, 11.3;
         //  K = 80: 12 waves 15.4, 8 waves 18.0;  K = 100: 10 waves / 168 VGPRs 20.9, 8 / 256 22.3;  K = 128: 6 waves / 168 VGPRs 39.1, 6 / 256 37.1)
         int maxw = (h->K <= 64 || h->KP <= 108) ? 12 : 8;
-        if (const char* e = getenv("TMVB_CTM_CG_MAXW")) { if (h->K > 64) maxw = (atoi(e) >= 12) ? 12 : 8; }
+        if (tmvb_env_str("TMVB_CTM_CG_MAXW") && h->K > 64) maxw = (tmvb_env_int("TMVB_CTM_CG_MAXW", 0) >= 12) ? 12 : 8;
         const bool ga = h->K > 128;                            // four topic slots per lane, invsigma read from global memory (L2)
         if (ga) maxw = 8;
         int waves, tile_rows;
@@ -1826,7 +1824,7 @@ static int ctm_launch_quad(tmvb_ctm* h, const CtmParams& p, double ntol)
     const size_t lds = (size_t)(5 * h->KP * 64 + 2 * 3 * 4 * 64) * 4 + (size_t)(2 * 4 * 64) * 8 + (5 * 64 + 4) * 4;      // = cq_dim<KP>::lds_bytes
     // two workgroups per CU: two waves per SIMD (TMVB_CTM_QUAD_PER_CU: diagnostics)
     int per_cu = TMVB_CTM_QWAVES;
-    if (const char* e = getenv("TMVB_CTM_QUAD_PER_CU")) per_cu = std::max(1, std::min(4, atoi(e)));
+    if (tmvb_env_str("TMVB_CTM_QUAD_PER_CU")) per_cu = std::max(1, std::min(4, tmvb_env_int("TMVB_CTM_QUAD_PER_CU", 0)));
     const dim3 grid((unsigned)std::min(n_items, per_cu * ctx->num_cu)), block(256);
     tb.next_item = (unsigned*)(h->d_cg_iters + 12); tb.n_items = n_items;
     if (h->reorder && h->keys_valid && !h->reorder_staged) {
@@ -1850,7 +1848,7 @@ static int ctm_launch_quad(tmvb_ctm* h, const CtmParams& p, double ntol)
     // (the dynamic-LDS attribute once per HANDLE, not per process: one host thread may drive several devices, tmvb_ctm_train_group)
 #define CTM_QCASE(KPV) case KPV: { if (!h->quad_attr_set && lds > 48 * 1024) { TMVB_HIP(hipFuncSetAttribute((const void*)ctm_estep_quad_kernel<KPV, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); h->quad_attr_set = true; } \
                                    hipLaunchKernelGGL((ctm_estep_quad_kernel<KPV, false>), grid, block, lds, ctx->stream, ba); } break;
-    static const bool qprof = [] { const char* e = getenv("TMVB_CTM_QPROF"); return e && atoi(e) != 0; }();
+    static const bool qprof = tmvb_env_on("TMVB_CTM_QPROF", false);
     if (qprof && h->KP == 52) {
         TMVB_HIP(hipFuncSetAttribute((const void*)ctm_estep_quad_kernel<52, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         hipLaunchKernelGGL((ctm_estep_quad_kernel<52, true>), grid, block, lds, ctx->stream, ba);
@@ -1879,10 +1877,10 @@ static int ctm_launch_batch(tmvb_ctm* h, const CtmParams& p, double ntol)
     // waves-of-documents from the queue at d_cg_iters[12] (zeroed by ctm_batch_tabs_kernel); the order of the queue is the processing order, longest
     // documents first.  TMVB_CTM_PERSISTENT=0: one workgroup per wave-of-documents, placed by the hardware dispatcher.
     const int n_items = (int)((Mb + 63) / 64);
-    static const bool persistent = [] { const char* e = getenv("TMVB_CTM_PERSISTENT"); return !(e && atoi(e) == 0); }();
+    static const bool persistent = tmvb_env_on("TMVB_CTM_PERSISTENT", true);
     const size_t lds = (size_t)h->KP * 64 * (sizeof(double) + sizeof(float)) + 64 * sizeof(int32_t);   // vsq, CG solution / row staging, row ids
     int per_cu = (int)std::min<size_t>(4, (160 * 1024) / lds);            // one wave per SIMD, and what the CU's LDS holds
-    if (const char* e = getenv("TMVB_CTM_PER_CU")) per_cu = std::max(1, std::min(per_cu, atoi(e)));   // diagnostics: fewer resident waves (contention experiments, profiles/r5_ctm_token_experiments.txt)
+    if (tmvb_env_str("TMVB_CTM_PER_CU")) per_cu = std::max(1, std::min(per_cu, tmvb_env_int("TMVB_CTM_PER_CU", 0)));   // diagnostics: fewer resident waves (contention experiments, profiles/r5_ctm_token_experiments.txt)
     const dim3 grid((unsigned)(persistent ? std::min(n_items, per_cu * ctx->num_cu) : n_items)), block(64);
     tb.next_item = (unsigned*)(h->d_cg_iters + 12); tb.n_items = n_items;
     if (h->reorder && h->keys_valid && !h->reorder_staged) {      // (staged: the last tmvb_ctm_estep already regrouped behind its statistics tail)
@@ -1901,9 +1899,9 @@ static int ctm_launch_batch(tmvb_ctm* h, const CtmParams& p, double ntol)
         ba.p.beta = h->d_beta_pad;
     }
     h->queue_sorted = false;
-    static const bool prof = [] { const char* e = getenv("TMVB_CTM_PROF"); return e && atoi(e) != 0; }();
+    static const bool prof = tmvb_env_on("TMVB_CTM_PROF", false);
     // TMVB_CTM_WAVE_LOG=<file> (with TMVB_CTM_PROF=1): per-item start / end / placement of this launch, written after a synchronisation (diagnostics only)
-    static const char* wave_log = getenv("TMVB_CTM_WAVE_LOG");
+    static const char* wave_log = tmvb_env_str("TMVB_CTM_WAVE_LOG");
     static unsigned long long* d_wl = nullptr; static size_t wl_cap = 0;
     const bool logging = prof && h->KP == 52 && wave_log;
     if (logging) {
@@ -1940,10 +1938,10 @@ extern "C" int tmvb_ctm_estep(tmvb_ctm* h, int32_t niter, double ntol, int32_t v
     p.lambda = h->d_lambda; p.lambda_old = h->d_lambda_old; p.vsq = h->d_vsq; p.logzeta = h->d_logzeta;
     p.wtok = h->d_wtok; p.E = h->d_E; p.estride = (h->KP / 4 <= 64) ? h->KP : h->K; p.sweeps = h->d_sweeps; p.newton_steps = h->d_newton;
     p.niter = niter; p.ntol = ntol; p.viter = viter; p.vtol = vtol;
-    { const char* dbg = getenv("TMVB_DEBUG_FLAGS"); p.debug = dbg ? atoi(dbg) : 0; }
+    p.debug = 0;
     p.store_w = tmvb_termstats_recomputes(h->KP, h->KP / 4 <= 64) ? 0 : 1;
     // decomposed update_elbo!: this iteration will be checked -- the document kernels leave pdot, the statistics pass the log-normaliser sums
-    const bool collect = (h->parts_env == 2 || (h->parts_env != 0 && h->want_parts)) && p.store_w == 0 && viter > 0 && !(p.debug & 1);
+    const bool collect = (h->parts_env == 2 || (h->parts_env != 0 && h->want_parts)) && p.store_w == 0 && viter > 0;
     h->logz_valid = false; h->pw_valid = false; h->stats_fresh = false;
     if (collect) {
         const size_t need = (size_t)std::max<int64_t>(h->corp->term_index.n_chunks, 1);
@@ -1985,7 +1983,7 @@ extern "C" int tmvb_ctm_estep(tmvb_ctm* h, int32_t niter, double ntol, int32_t v
     if (h->batch && h->M > 0) {
         // round 6: four waves per wave-of-documents (tmvb_ctm_quad.h), two workgroups per CU; TMVB_CTM_QUAD=0 (or the profiling build of the
         // one-wave kernel, TMVB_CTM_PROF=1) selects round 3's one-wave kernel
-        static const bool quad = [] { const char* e = getenv("TMVB_CTM_QUAD"); const char* pr = getenv("TMVB_CTM_PROF"); return !(e && atoi(e) == 0) && !(pr && atoi(pr) != 0); }();
+        static const bool quad = tmvb_env_on("TMVB_CTM_QUAD", true) && !tmvb_env_on("TMVB_CTM_PROF", false);
         // (the four-waves kernel wants 78 KB of LDS per workgroup at KP = 52: on a device whose per-workgroup limit is below that the one-wave kernel -- 40 KB -- runs)
         if (h->lds_limit < 0) {
             int v = 0;
@@ -2005,8 +2003,7 @@ extern "C" int tmvb_ctm_estep(tmvb_ctm* h, int32_t niter, double ntol, int32_t v
     // The document reductions of tmvb_ctm_reduce_docs (sum lambda, sum vsq, the scatter matrix with the current mu: 0.15 ms of small
     // kernels) depend only on what the document kernels just wrote: they run here on a side stream under the statistics pass, and
     // tmvb_ctm_reduce_docs finds them done (tail_fresh; any change of lambda / vsq / mu through the API clears the flag).
-    static const bool fold = [] { const char* e = getenv("TMVB_CTM_FOLD_REDUCE"); return !(e && atoi(e) == 0); }();
-    const bool folded = fold && h->M > 0 && h->aux[0] != nullptr;
+    const bool folded = h->M > 0 && h->aux[0] != nullptr;
     if (folded) {
         TMVB_HIP(hipEventRecord(h->ev_fork, ctx->stream));
         TMVB_HIP(hipStreamWaitEvent(h->aux[0], h->ev_fork, 0));
@@ -2015,8 +2012,7 @@ extern "C" int tmvb_ctm_estep(tmvb_ctm* h, int32_t niter, double ntol, int32_t v
         TMVB_HIP(hipEventRecord(h->ev_join[0], h->aux[0]));
         // behind the tail, still under the statistics pass: update_sigma! staged (single process only: a sharded run all-reduces the
         // tail first) and the documents regrouped for the next E-step
-        const char* espec = getenv("TMVB_CTM_SPECULATE");     // (read per call: the tests run both ways in one process)
-        const bool spec = !(espec && atoi(espec) == 0);
+        const bool spec = tmvb_env_on("TMVB_CTM_SPECULATE", true);     // (read per call: the tests run both ways in one process)
         if (spec) {
             if (!h->distributed) { frc = ctm_sigma_mu(h, 1, 0, true, h->aux[0]); if (frc) return frc; h->sigma_staged = true; }
             if (h->batch && h->reorder && h->keys_valid) {
@@ -2029,8 +2025,7 @@ extern "C" int tmvb_ctm_estep(tmvb_ctm* h, int32_t niter, double ntol, int32_t v
                                        h->d_doc_order0 + h->n_long, h->d_doc_newton, h->d_doc_order + h->n_long, Mb);
                     TMVB_HIP(hipGetLastError());
                     h->reorder_staged = true;
-                    const char* ews = getenv("TMVB_CTM_WAVESORT");
-                    const bool wsort = !(ews && atoi(ews) == 0);
+                    const bool wsort = tmvb_env_on("TMVB_CTM_WAVESORT", true);
                     const int64_t nfull = Mb / 64;
                     if (wsort && nfull >= 2 && nfull <= CTM_WAVESORT_MAX) {
                         int P = 2; while (P < nfull) P <<= 1;
@@ -2657,7 +2652,7 @@ extern "C" int tmvb_fctm_create(tmvb_ctx* ctx, tmvb_corpus* corp, int32_t K, tmv
         (rc = dmalloc(&h->d_tau_old, NZ)) || (rc = dmalloc(&h->d_lse, NZ)) || (rc = dmalloc(&h->d_stats, (size_t)h->stats_len())) ||
         (rc = dmalloc(&h->d_aold, std::max<size_t>(NZ, 1))) || (rc = dmalloc(&h->d_eta_scratch, 1)) || (rc = dmalloc(&h->d_ksum, 1)))
         return rc;
-    { const char* e = getenv("TMVB_FCTM_ELBO_PARTS"); h->parts_env = e ? atoi(e) : 1; }
+    h->parts_env = tmvb_env_int("TMVB_FCTM_ELBO_PARTS", 1);
     TMVB_HIP(hipMemsetAsync(h->d_stats, 0, (size_t)h->stats_len() * sizeof(float), ctx->stream));
     TMVB_HIP(hipMemsetAsync(h->d_lse, 0, std::max<size_t>(NZ, 1) * sizeof(float), ctx->stream));
     TMVB_HIP(hipStreamSynchronize(ctx->stream));

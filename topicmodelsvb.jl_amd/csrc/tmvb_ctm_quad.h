@@ -216,7 +216,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TMVB_CTM_QW
     const int K = a.p.K, p_viter = a.p.viter, p_niter = a.p.niter, p_debug = a.p.debug;
     const double p_ntol = a.p.ntol, p_vtol = a.p.vtol;
     const float cg_tol2 = a.tb.cg_tol2, cg_abs2 = a.tb.cg_abs2;
-    const int cg_maxit = (a.p.debug & 8) ? 0 : a.tb.cg_maxit;              // TMVB_DEBUG_FLAGS & 8: no CG trips (timing experiments only)
+    const int cg_maxit = (a.p.debug & 8) ? 0 : a.tb.cg_maxit;              // (a.p.debug is 0: see CtmParams)
     const int64_t M = a.M;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float* lam_l = lds;                                    // [R][64]  (float)lambda, for the token lanes
@@ -256,7 +256,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TMVB_CTM_QW
         const int tj = 16 * w + (lane >> 2), qd = lane & 3;
         const int td = dinfo[tj], tN = dinfo[128 + tj];
         const unsigned toff4 = (unsigned)dinfo[64 + tj] * 4u;
-        const int Nmax16 = (p_debug & 4) ? 0 : wave_max_i(tN);                 // TMVB_DEBUG_FLAGS & 4: no token walk (timing experiments only)
+        const int Nmax16 = (p_debug & 4) ? 0 : wave_max_i(tN);                 // (p_debug is 0)
         {
             // C_d = sum of counts (src/CTM.jl:33): integers, exact in fp32 in any order
             typedef const __attribute__((address_space(1))) int32_t* gint_p;

@@ -439,25 +439,22 @@ static void ctpf_launch_reg(int tiles, dim3 grid, hipStream_t st, const CtpfPara
 // phi / xi, so they are taken once, in the document's first sweep, and kept (the factors move by a few units per sweep; fp32
 // exp has 80 to spare).  W > 1: W waves share a long document (terms 32 NPT w + ..., readers 32 NPR w + ...), partial sums
 // through LDS once per sweep, every wave runs the identical tail.
-// BW = waves per workgroup: W (the W waves of one long document); with W = 1 and BW > 1 the waves of a workgroup would be
-// independent single-wave documents sharing nothing but the LDS array, sliced by wave (tried as one launch for the whole corpus:
-// slower, see tmvb_ctpf_estep).
-template <int LPR, int NPT, int NPR, int W = 1, int BW = W>
+// A workgroup is the W waves of one document (single-wave documents packed several to a workgroup were tried as one launch for the
+// whole corpus: slower, see tmvb_ctpf_estep).
+template <int LPR, int NPT, int NPR, int W = 1>
 __device__ __forceinline__ void ctpf_estep_grid_body(const CtpfParams& p, const int d, const int* __restrict__ topic_of_lane,
                                                     float (*ef_all)[2][4][16], float (*xch)[4][128])
 {
     constexpr int R = 4 * LPR;
     static_assert(LPR <= 16, "ctpf_estep_grid_body: one result slot per lane");
-    static_assert(W == 1 || W == BW, "ctpf_estep_grid_body: a multi-wave document owns its workgroup");
     static_assert(W <= 4, "ctpf_estep_grid_body: the exchange buffer holds four waves");
     const int lane = threadIdx.x & 63;
-    const int bwave = (BW > 1) ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : 0;   // LDS slice
-    const int wave = (W > 1) ? bwave : 0;                                                       // share of the document
+    const int wave = (W > 1) ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : 0;     // share of the document, LDS slice
     const int a = lane >> 2, b = lane & 3;
     const int K = p.K;
     const int64_t off = p.doc_ptr[d], roff = p.rdr_ptr[d];
     const int N = (int)(p.doc_ptr[d + 1] - off), Rd = (int)(p.rdr_ptr[d + 1] - roff);
-    float (*ef)[4][16] = ef_all[bwave];                 // e / f by class: [b][j], one copy per wave
+    float (*ef)[4][16] = ef_all[wave];                 // e / f by class: [b][j], one copy per wave
 
     gv2f A[NPT][LPR], ct[NPT], H[NPR][LPR], rr[NPR];
     {
@@ -501,7 +498,7 @@ __device__ __forceinline__ void ctpf_estep_grid_body(const CtpfParams& p, const 
         eb = on ? sweep_exp(xb - mab) : 0.f;
         f = ea + eb;
         if (mytopic >= 0) { ef[0][mytopic & 3][mytopic >> 2] = e; ef[1][mytopic & 3][mytopic >> 2] = f; }
-        if constexpr (BW > 1) WAVE_PRIVATE_LDS_FENCE(); else WAVE_LDS_FENCE();
+        if constexpr (W > 1) WAVE_PRIVATE_LDS_FENCE(); else WAVE_LDS_FENCE();
         float G[1], Hh[1];
         {   // terms: s_n = sum_i TA[n][i] e_i, w_n = c_n / s_n, G_i = sum_n w_n TA[n][i]
             gv2f w[NPT];
@@ -558,9 +555,8 @@ __device__ __forceinline__ void ctpf_estep_grid_body(const CtpfParams& p, const 
     }
 }
 
-// length classes of the grid-tile kernel (term pairs, reader pairs per lane): documents of <= 32 readers by their terms
-// (<= 64 / 96 / 128 / 192), <= 128 terms with <= 64 readers, and -- eight waves per document -- <= 512 terms with <= 512 readers
-#define CTPF_GRID_CLASSES(X) X(2, 1) X(3, 1) X(4, 1) X(6, 1) X(4, 2)
+// length classes of the grid-tile kernels (term pairs, reader pairs per lane): single-wave (2, 1) (3, 1) (4, 1) (6, 1) = documents of <= 32 readers
+// by their terms (<= 64 / 96 / 128 / 192), and (4, 2) = <= 128 terms with <= 64 readers;
 // multi-wave classes, four waves per document: (2 term pairs, 4 reader pairs) = <= 256 terms, <= 512 readers, and (3, 3) = <= 384, <= 384
 static inline bool ctpf_grid_class(int64_t n, int64_t r, int* npt, int* npr, int* waves)
 {
@@ -576,12 +572,6 @@ static inline bool ctpf_grid_class(int64_t n, int64_t r, int* npt, int* npr, int
     __shared__ float xch[2][4][128];                    /* multi-wave documents: per-wave partial (G | H), by sweep parity */ \
     __shared__ __attribute__((aligned(16))) float ef_all[BWV][2][4][16]
 
-template <int LPR, int NPT, int NPR>
-__global__ __launch_bounds__(64) void ctpf_estep_grid_kernel(CtpfParams p, int64_t first, const int* __restrict__ topic_of_lane)
-{
-    CTPF_GRID_LDS(1);
-    ctpf_estep_grid_body<LPR, NPT, NPR>(p, p.doc_order[first + blockIdx.x], topic_of_lane, ef_all, xch);
-}
 template <int LPR, int NPT, int NPR, int W>
 __global__ __launch_bounds__(64 * W) void ctpf_estep_grid_long_kernel(CtpfParams p, int64_t first, const int* __restrict__ topic_of_lane)
 {
@@ -601,28 +591,9 @@ __global__ __launch_bounds__(256) void ctpf_estep_grid_long2_kernel(CtpfParams p
     if ((int)blockIdx.x < count_a) ctpf_estep_grid_body<LPR, 3, 3, 4>(p, d, topic_of_lane, ef_all, xch);
     else ctpf_estep_grid_body<LPR, 2, 4, 4>(p, d, topic_of_lane, ef_all, xch);
 }
-// single-wave class of a document (wave-uniform)
-template <int LPR, int BW>
-__device__ __forceinline__ void ctpf_estep_grid_any(const CtpfParams& p, const int d, const int* __restrict__ topic_of_lane,
-                                                   float (*ef_all)[2][4][16], float (*xch)[4][128])
-{
-    const int N = __builtin_amdgcn_readfirstlane((int)(p.doc_ptr[d + 1] - p.doc_ptr[d]));
-    const int Rd = __builtin_amdgcn_readfirstlane((int)(p.rdr_ptr[d + 1] - p.rdr_ptr[d]));
-    if (Rd > 32) ctpf_estep_grid_body<LPR, 4, 2, 1, BW>(p, d, topic_of_lane, ef_all, xch);
-    else if (N > 128) ctpf_estep_grid_body<LPR, 6, 1, 1, BW>(p, d, topic_of_lane, ef_all, xch);
-    else if (N > 96) ctpf_estep_grid_body<LPR, 4, 1, 1, BW>(p, d, topic_of_lane, ef_all, xch);
-    else if (N > 64) ctpf_estep_grid_body<LPR, 3, 1, 1, BW>(p, d, topic_of_lane, ef_all, xch);
-    else ctpf_estep_grid_body<LPR, 2, 1, 1, BW>(p, d, topic_of_lane, ef_all, xch);
-}
-// every single-wave class in one launch, the class read per document (wave-uniform): one kernel tail per iteration
-template <int LPR>
-__global__ __launch_bounds__(64) void ctpf_estep_grid_any_kernel(CtpfParams p, int64_t first, const int* __restrict__ topic_of_lane)
-{
-    CTPF_GRID_LDS(1);
-    ctpf_estep_grid_any<LPR, 1>(p, p.doc_order[first + blockIdx.x], topic_of_lane, ef_all, xch);
-}
-// Round 4: that one launch ran EVERY document at ONE wave per SIMD -- the (6, 1) body needs 258 registers, and a kernel's allocation is
-// its widest path's (the ISA said so; the kernel issued a vector instruction 42 % of the time).  Two launches by register need instead:
+// The single-wave classes, the class read per document (wave-uniform).  One launch for all five ran EVERY document at ONE wave per SIMD
+// (round 4) -- the (6, 1) body needs 258 registers, and a kernel's allocation is its widest path's (the ISA said so; the kernel issued a
+// vector instruction 42 % of the time).  Two launches by register need instead:
 //   NARROW  (2, 1) and (3, 1): documents of <= 96 terms and <= 32 readers (most of a CiteULike-shaped corpus), 168 VGPRs = three waves per SIMD,
 //           on the context's stream;
 //   WIDE    (4, 1), (6, 1), (4, 2): the rest of the single-wave classes, on aux[0] beside it (the multi-wave long documents keep aux[1]).
@@ -632,8 +603,8 @@ __global__ __launch_bounds__(64, 3) void ctpf_estep_grid_narrow_kernel(CtpfParam
     CTPF_GRID_LDS(1);
     const int d = p.doc_order[first + blockIdx.x];
     const int N = __builtin_amdgcn_readfirstlane((int)(p.doc_ptr[d + 1] - p.doc_ptr[d]));
-    if (N > 64) ctpf_estep_grid_body<LPR, 3, 1, 1, 1>(p, d, topic_of_lane, ef_all, xch);
-    else ctpf_estep_grid_body<LPR, 2, 1, 1, 1>(p, d, topic_of_lane, ef_all, xch);
+    if (N > 64) ctpf_estep_grid_body<LPR, 3, 1>(p, d, topic_of_lane, ef_all, xch);
+    else ctpf_estep_grid_body<LPR, 2, 1>(p, d, topic_of_lane, ef_all, xch);
 }
 template <int LPR>
 __global__ __launch_bounds__(64) void ctpf_estep_grid_wide_kernel(CtpfParams p, int64_t first, const int* __restrict__ topic_of_lane)
@@ -642,23 +613,18 @@ __global__ __launch_bounds__(64) void ctpf_estep_grid_wide_kernel(CtpfParams p, 
     const int d = p.doc_order[first + blockIdx.x];
     const int N = __builtin_amdgcn_readfirstlane((int)(p.doc_ptr[d + 1] - p.doc_ptr[d]));
     const int Rd = __builtin_amdgcn_readfirstlane((int)(p.rdr_ptr[d + 1] - p.rdr_ptr[d]));
-    if (Rd > 32) ctpf_estep_grid_body<LPR, 4, 2, 1, 1>(p, d, topic_of_lane, ef_all, xch);
-    else if (N > 128) ctpf_estep_grid_body<LPR, 6, 1, 1, 1>(p, d, topic_of_lane, ef_all, xch);
-    else ctpf_estep_grid_body<LPR, 4, 1, 1, 1>(p, d, topic_of_lane, ef_all, xch);
+    if (Rd > 32) ctpf_estep_grid_body<LPR, 4, 2>(p, d, topic_of_lane, ef_all, xch);
+    else if (N > 128) ctpf_estep_grid_body<LPR, 6, 1>(p, d, topic_of_lane, ef_all, xch);
+    else ctpf_estep_grid_body<LPR, 4, 1>(p, d, topic_of_lane, ef_all, xch);
 }
 template <int LPR>
 static void ctpf_launch_grid(const tmvb_bucket& b, dim3 grid, hipStream_t st, const CtpfParams& p, int64_t first, const int* tol)
 {
-
     if (b.waves == 4 && b.grid_np == 96) { hipLaunchKernelGGL((ctpf_estep_grid_long2_kernel<LPR>), grid, dim3(256), 0, st, p, first, tol, (int)b.grid_np2); return; }
     if (b.waves == 4 && b.grid_np == 2) { hipLaunchKernelGGL((ctpf_estep_grid_long_kernel<LPR, 2, 4, 4>), grid, dim3(256), 0, st, p, first, tol); return; }
     if (b.waves == 4) { hipLaunchKernelGGL((ctpf_estep_grid_long_kernel<LPR, 3, 3, 4>), grid, dim3(256), 0, st, p, first, tol); return; }
-    if (b.grid_np == 99) { hipLaunchKernelGGL((ctpf_estep_grid_any_kernel<LPR>), grid, dim3(64), 0, st, p, first, tol); return; }
     if (b.grid_np == 98) { hipLaunchKernelGGL((ctpf_estep_grid_wide_kernel<LPR>), grid, dim3(64), 0, st, p, first, tol); return; }
     if (b.grid_np == 97) { hipLaunchKernelGGL((ctpf_estep_grid_narrow_kernel<LPR>), grid, dim3(64), 0, st, p, first, tol); return; }
-#define CTPF_GRID_LAUNCH(T_, R_) if (b.grid_np == T_ && b.grid_np2 == R_) { hipLaunchKernelGGL((ctpf_estep_grid_kernel<LPR, T_, R_>), grid, dim3(64), 0, st, p, first, tol); return; }
-    CTPF_GRID_CLASSES(CTPF_GRID_LAUNCH)
-#undef CTPF_GRID_LAUNCH
 }
 // shape update + table refresh:  X[id][i] = prior + stats[id][i];  T[id][i] = exp(psi(X));  stats <- 0
 // (update_alef!/update_he! src/CTPF.jl:251-255, :266-270: X <- X_temp, X_temp <- prior)
@@ -1398,7 +1364,7 @@ struct tmvb_ctpf {
     double elbo = 0.0;
     int* d_topic_of_lane = nullptr;     // register-tile kernel: topic owned by each lane after the reduce-scatter
     int* d_grid_topic_of_lane = nullptr;   // grid-tile kernel (tmvb_gridtile.h): the same for its 16-lane reduce-scatter
-    bool grid_path = false;             // KP <= 60: documents of <= 512 terms and <= 512 readers use ctpf_estep_grid_kernel
+    bool grid_path = false;             // KP <= 60: documents of <= 512 terms and <= 512 readers use the grid-tile kernels (ctpf_estep_grid_*_kernel)
     bool reg_path = false;              // KP = 4 * odd <= 60: short documents (<= 128 terms, <= 64 readers) use ctpf_estep_reg_kernel
     std::vector<tmvb_bucket> buckets;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -1507,7 +1473,7 @@ extern "C" int tmvb_ctpf_create(tmvb_ctx* ctx, tmvb_corpus* corp, int32_t K, tmv
     }
     // grid-tile kernel: KP <= 60, both tables addressable by 32-bit byte offsets; TMVB_CTPF_GRID=0 keeps the lane = token tiles
     h->grid_path = h->reg_path && (uint64_t)std::max(h->V, h->U) * (uint64_t)h->KP * 4u < (1ull << 32) &&
-                   !(getenv("TMVB_CTPF_GRID") && atoi(getenv("TMVB_CTPF_GRID")) == 0);
+                   tmvb_env_on("TMVB_CTPF_GRID", true);
     if (h->grid_path) {
         std::vector<int> tol;
         switch (h->KP / 4) {
@@ -1567,8 +1533,8 @@ extern "C" int tmvb_ctpf_create(tmvb_ctx* ctx, tmvb_corpus* corp, int32_t K, tmv
     TMVB_HIP(hipMemsetAsync(h->d_sweeps, 0, std::max<size_t>((size_t)h->M, 1), ctx->stream));
     // (the two timing events are default events -- time stamps and a system-scope release each -- on the stream the whole iteration runs on:
     //  recorded unconditionally they cost every 0.15 ms iteration two barrier packets; round 4, as LDA has it)
-    { const char* t = getenv("TMVB_ESTEP_TIMING"); h->timing = t && atoi(t) != 0; }
-    { const char* e = getenv("TMVB_CTPF_ELBO_PARTS"); h->parts_env = e ? atoi(e) : 1; }
+    h->timing = tmvb_env_on("TMVB_ESTEP_TIMING", false);
+    h->parts_env = tmvb_env_int("TMVB_CTPF_ELBO_PARTS", 1);
     TMVB_HIP(hipEventCreate(&h->ev0));
     TMVB_HIP(hipEventCreate(&h->ev1));
     TMVB_HIP(hipEventCreateWithFlags(&h->ev_fork, tmvb_event_flags()));
@@ -1577,9 +1543,8 @@ extern "C" int tmvb_ctpf_create(tmvb_ctx* ctx, tmvb_corpus* corp, int32_t K, tmv
     for (int a = 0; a < tmvb_ctpf::NAUX; ++a) {
         // aux[1] carries the few multi-wave (long) documents next to the chain's one big launch: at the default priority its 512-thread
         // workgroups find no CU with eight free wave slots until the chain's launch drains and then add their whole run time to the
-        // E-step; on a high-priority queue they are placed first (TMVB_CTPF_LONG_PRIO=0: default priority)
-        static const bool long_prio = [] { const char* e = getenv("TMVB_CTPF_LONG_PRIO"); return !(e && atoi(e) == 0); }();
-        h->aux[a] = tmvb_pool_stream(ctx->device, 1 + a, a == 1 && long_prio);
+        // E-step; on a high-priority queue they are placed first
+        h->aux[a] = tmvb_pool_stream(ctx->device, 1 + a, a == 1);
         TMVB_REQUIRE(h->aux[a] != nullptr, TMVB_EHIP, "hipStreamCreate failed");
         TMVB_HIP(hipEventCreateWithFlags(&h->ev_join[a], tmvb_event_flags()));
     }
@@ -1796,32 +1761,27 @@ extern "C" int tmvb_ctpf_estep(tmvb_ctpf* h, int32_t viter, double vtol)
         const tmvb_bucket& b = h->buckets[bi];
         dim3 grid((unsigned)b.count), block(64);
         if (b.grid_np > 0) {
-            // the multi-wave (long) documents on aux[1] next to the chain, the single-wave classes on the context's stream -- as ONE
-            // mixed-class launch unless TMVB_CTPF_GRID_ANY=0 (one kernel tail per iteration; the price is the widest body's registers).
+            // the multi-wave (long) documents on aux[1] next to the chain, the single-wave classes as two mixed-class launches (below).
             // (Measured and dropped: everything in one launch of four-wave workgroups, long documents first and four single-wave
             //  documents per later workgroup: 0.256 ms per iteration against 0.193 ms.)
-            static const bool gany = [] { const char* e = getenv("TMVB_CTPF_GRID_ANY"); return !(e && atoi(e) == 0); }();
             hipStream_t st = b.waves > 1 ? h->aux[1] : chain_st;
             tmvb_bucket bb = b;
             // the (3, 3) four-wave bucket and the (2, 4) one behind it as one launch (ctpf_estep_grid_long2_kernel); TMVB_CTPF_LONG_MERGE=0: two
-            const char* elm = getenv("TMVB_CTPF_LONG_MERGE");
             if (b.waves == 4 && b.grid_np == 3 && b.grid_np2 == 3 && bi + 1 < nb && h->buckets[bi + 1].waves == 4 && h->buckets[bi + 1].grid_np == 2 &&
-                h->buckets[bi + 1].grid_np2 == 4 && h->buckets[bi + 1].first == b.first + b.count && b.count < (1 << 30) && !(elm && atoi(elm) == 0)) {
+                h->buckets[bi + 1].grid_np2 == 4 && h->buckets[bi + 1].first == b.first + b.count && b.count < (1 << 30) && tmvb_env_on("TMVB_CTPF_LONG_MERGE", true)) {
                 bb.grid_np = 96; bb.grid_np2 = (int)b.count; bb.count = b.count + h->buckets[bi + 1].count;
                 grid = dim3((unsigned)bb.count);
                 ++bi;
             }
-            // (round 4) the single-wave classes as TWO launches by register need (ctpf_estep_grid_narrow_kernel / _wide_kernel) unless
-            // TMVB_CTPF_SPLIT=0 (read per call: the tests run both)
-            const char* es = getenv("TMVB_CTPF_SPLIT");
-            const bool split = !(es && atoi(es) == 0);
-            if (gany && b.waves == 1) {
+            // (round 4) the single-wave classes as TWO launches by register need: every single-wave bucket leaves here as class 97
+            // (ctpf_estep_grid_narrow_kernel, on the chain) or 98 (ctpf_estep_grid_wide_kernel, on aux[0]) with its neighbours of the same kind
+            if (b.waves == 1) {
                 const bool wide = b.grid_np >= 4;
                 int64_t cnt = b.count;
                 while (bi + 1 < nb && h->buckets[bi + 1].grid_np > 0 && h->buckets[bi + 1].waves == 1 &&
-                       h->buckets[bi + 1].first == b.first + cnt && (!split || (h->buckets[bi + 1].grid_np >= 4) == wide)) { cnt += h->buckets[bi + 1].count; ++bi; }
-                if (split) { bb.count = cnt; bb.grid_np = wide ? 98 : 97; grid = dim3((unsigned)cnt); if (wide) { st = h->aux[0]; aux0_used = true; } }
-                else if (cnt > b.count) { bb.count = cnt; bb.grid_np = 99; grid = dim3((unsigned)cnt); }
+                       h->buckets[bi + 1].first == b.first + cnt && (h->buckets[bi + 1].grid_np >= 4) == wide) { cnt += h->buckets[bi + 1].count; ++bi; }
+                bb.count = cnt; bb.grid_np = wide ? 98 : 97; grid = dim3((unsigned)cnt);
+                if (wide) { st = h->aux[0]; aux0_used = true; }
             }
             switch (p.LPR) {
 #define CTPF_GRID_CASE(LPRV) case LPRV: ctpf_launch_grid<LPRV>(bb, grid, st, p, b.first, h->d_grid_topic_of_lane); break;
@@ -1836,9 +1796,8 @@ extern "C" int tmvb_ctpf_estep(tmvb_ctpf* h, int32_t viter, double vtol)
         if (b.reg_tiles > 0) {
             hipStream_t st = chain_st;
             // two adjacent register-tile buckets (T = 2 then T = 1 in processing order): one mixed-tile launch
-            static const bool any_env = [] { const char* e = getenv("TMVB_CTPF_REG_ANY"); return !(e && atoi(e) == 0); }();
             int tiles = b.reg_tiles;
-            if (any_env && bi + 1 < nb && h->buckets[bi + 1].reg_tiles > 0 && h->buckets[bi + 1].first == b.first + b.count) {
+            if (bi + 1 < nb && h->buckets[bi + 1].reg_tiles > 0 && h->buckets[bi + 1].first == b.first + b.count) {
                 grid = dim3((unsigned)(b.count + h->buckets[bi + 1].count));
                 tiles = 99;
                 ++bi;
@@ -1901,9 +1860,8 @@ extern "C" int tmvb_ctpf_estep(tmvb_ctpf* h, int32_t viter, double vtol)
     TermStatsParams tr = tp;
     tr.w = h->d_wrdr; tr.E = h->d_E2; tr.T = h->d_TH; tr.out = h->he_stats(); tr.partial = h->d_ts_partial2;
     if (collect) { tp.logz = h->d_logz; tr.logz = h->d_logz + nct; }
-    static const bool fuse_env = [] { const char* e = getenv("TMVB_CTPF_FUSE_STATS"); return !(e && atoi(e) == 0); }();
     int rc = TMVB_EINVAL;
-    if (fuse_env && h->U > 0 && tmvb_termstats_recomputes(h->KP, h->e_padded))
+    if (h->U > 0 && tmvb_termstats_recomputes(h->KP, h->e_padded))
         rc = tmvb_launch_termstats2(ctx, h->nslot, h->KP, h->corp->term_index, tp, h->corp->reader_index, tr);
     if (rc == TMVB_EINVAL) {
         TMVB_HIP(hipEventRecord(h->ev_fork, ctx->stream));
@@ -1935,11 +1893,7 @@ static int ctpf_reduce_docs_on(tmvb_ctpf* h, hipStream_t st)
                         {h->d_zayin, h->M, h->d_partial2, h->d_sum_z, h->tail() + h->K}, st);
 }
 
-static bool ctpf_mstep_fused(const tmvb_ctpf* h)
-{
-    static const bool env = [] { const char* e = getenv("TMVB_CTPF_FUSED_MSTEP"); return !(e && atoi(e) == 0); }();
-    return env && h->K <= 64;
-}
+static bool ctpf_mstep_fused(const tmvb_ctpf* h) { return h->K <= 64; }      // ctpf_mstep_kernel; wider models take the separate launches
 
 // the document sums a deferred tmvb_ctpf_reduce_docs still owes (anything that hands the statistics tail out needs them now)
 static int ctpf_flush_docs(tmvb_ctpf* h)
@@ -2069,7 +2023,7 @@ extern "C" int tmvb_ctpf_update_elbo_parts(tmvb_ctpf* h, double* doc_part, doubl
     }
     const double* hy = h->hyper;
     double res[2] = {0.0, 0.0};
-    static const bool legacy_elbo = [] { const char* e = getenv("TMVB_CTPF_ELBO_LEGACY"); return e && atoi(e) != 0; }();
+    static const bool legacy_elbo = tmvb_env_on("TMVB_CTPF_ELBO_LEGACY", false);
     // the decomposed form: the last E-step collected its parts and exactly one M-step ran behind it (alef_old / he_old / the old rates are that E-step's)
     const bool parts = (h->M > 0 || h->distributed) && !legacy_elbo && h->logz_valid && h->msteps_after == 1 && !h->force_walk;
     h->elbo_form = parts ? 1 : 0;

@@ -467,7 +467,7 @@ extern "C" int tmvb_flda_create(tmvb_ctx* ctx, tmvb_corpus* corp, int32_t K, tmv
         (rc = dmalloc(&h->d_rowsum, K)) || (rc = dmalloc(&h->d_esum, K)) || (rc = dmalloc(&h->d_doc_val, (size_t)h->M)) ||
         (rc = dmalloc(&h->d_elbo, 1)) || (rc = dmalloc(&h->d_iters, 1)))
         return rc;
-    { const char* e = getenv("TMVB_FLDA_ELBO_PARTS"); h->parts_env = e ? atoi(e) : 1; }
+    h->parts_env = tmvb_env_int("TMVB_FLDA_ELBO_PARTS", 1);
     std::vector<int32_t> order((size_t)h->M);
     std::iota(order.begin(), order.end(), 0);
     const std::vector<int64_t>& len = corp->h_doc_len;

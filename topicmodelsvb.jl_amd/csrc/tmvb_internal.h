@@ -5,11 +5,19 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdarg>
+#include <cstdlib>
 #include <cmath>
 #include <string>
 #include <vector>
 
 #include "tmvb.h"
+
+// ------------------------------------------------------------------------------------ environment switches
+// The only readers of the TMVB_* switches (one row each in INTEGRATION.md, section 4; tests/test_env_switches_host.py holds the two together).
+// Nothing is cached here: a site that reads once per process keeps its own `static const`, a site that reads per model or per call calls again.
+static inline const char* tmvb_env_str(const char* name) { return getenv(name); }                 // NULL: unset
+static inline int tmvb_env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
+static inline bool tmvb_env_on(const char* name, bool dflt) { const char* e = getenv(name); return e ? atoi(e) != 0 : dflt; }
 
 // ------------------------------------------------------------------------------------ errors
 void tmvb_set_error(const char* fmt, ...);

@@ -71,7 +71,6 @@ struct LdaParams {
     uint8_t* sweeps;
     int viter;
     float vtol;
-    int debug;               // TMVB_DEBUG_FLAGS (profiling experiments only): 1 = skip the statistics pass
     int store_w;             // 0 when the statistics pass recomputes w (K <= 64): no per-token stores at all
 };
 
@@ -1226,7 +1225,7 @@ static void lda_build_buckets(tmvb_lda* h, std::vector<int32_t>& order)
     // gathered once per E-step, a streamed one once per sweep
     // Documents between 64 T and 64 T W unique terms keep the register-tile arithmetic with one workgroup of
     // W = TMVB_LONG_WAVES waves each (lda_estep_reg_long_kernel); only what is longer still goes through LDS.
-    const bool long_reg = h->reg_path && getenv("TMVB_LDA_NO_LONG") == nullptr;
+    const bool long_reg = h->reg_path;
     const int64_t long_max = long_reg ? (int64_t)64 * max_tiles * TMVB_LONG_WAVES : reg_max;
     int64_t pos = tmvb_build_lds_buckets(len, order, h->M, h->KP, long_max, 3, h->buckets, TMVB_BIG_TILE_BYTES);
     // grid-tile kernel with 4 / 2 waves per document: up to 768 / 384 unique terms
@@ -1250,7 +1249,7 @@ static void lda_build_buckets(tmvb_lda* h, std::vector<int32_t>& order)
     // small corpora (one statistics pass): ONE launch for all register-tile documents, longest first
     // (KP <= 60 only: with two result slots per lane the widest body costs the short documents a wave per SIMD --
     //  measured at KP = 100, 16 k documents: 2.14 k it/s merged, 2.26 k separate)
-    if (h->reg_path && h->KP <= 60 && pos < h->M && lda_piece_count(h) == 1 && getenv("TMVB_LDA_NO_MERGE") == nullptr) {
+    if (h->reg_path && h->KP <= 60 && pos < h->M && lda_piece_count(h) == 1 && tmvb_env_str("TMVB_LDA_NO_MERGE") == nullptr) {
         tmvb_bucket b{pos, h->M - pos, 0, TMVB_REG_ANY_TILES};
         if (h->grid_path) b.grid_np = TMVB_GRID_ANY_NP;
         h->buckets.push_back(b);
@@ -1262,8 +1261,7 @@ static void lda_build_buckets(tmvb_lda* h, std::vector<int32_t>& order)
         // SYN-NSF K = 50, alternating on one box: 1256 / 1267 it/s with it against 1287 / 1288 without (its ~125 VALU instructions per sweep
         // against 200 are paid for with 29 dependent LDS broadcast reads per sweep and three waves per SIMD instead of four).  TMVB_LDA_TT=1
         // selects it (read per model: tests/test_lda_gpu.py runs it against the oracle).
-        const char* tt_e = getenv("TMVB_LDA_TT");
-        const bool tt = tt_e && atoi(tt_e) != 0 && h->KP <= 60 && h->estride <= 64;
+        const bool tt = tmvb_env_on("TMVB_LDA_TT", false) && h->KP <= 60 && h->estride <= 64;
         auto cls = [&](int64_t n) { return (tt && n <= 64) ? TMVB_GRID_TT_NP : lda_grid_np_class(n, h->grid_np_max); };
         while (pos < h->M) {
             const int np = cls(len[order[pos]]);
@@ -1289,7 +1287,7 @@ static void lda_build_buckets(tmvb_lda* h, std::vector<int32_t>& order)
 static int lda_piece_count(const tmvb_lda* h)
 {
     if (!tmvb_termstats_recomputes(h->KP, h->e_padded) || !h->reg_path) return 1;
-    if (const char* e = getenv("TMVB_LDA_PIECES")) return std::max(1, std::min(16, atoi(e)));
+    if (tmvb_env_str("TMVB_LDA_PIECES")) return std::max(1, std::min(16, tmvb_env_int("TMVB_LDA_PIECES", 1)));
     // measured on SYN-NSF and its shards in the steady state (tools/run_pieces.sh, it/s): 10.9 M tokens 1 / 2 / 3 / 4 / 6 pieces
     // = 717 / 806 / 813 / 803 / ~790; 5.5 M tokens 1354 / 1413 / 1426; 2.7 M tokens 2416 / 2229; 1.4 M tokens 3926 / 3303.
     // Below ~4 M tokens the one-pass plan (critical chain on the context's stream, no cross-stream hops) wins.
@@ -1314,11 +1312,6 @@ static void lda_cut_pieces(tmvb_lda* h, const std::vector<int32_t>& order, int P
         for (int q = 0; q < P; ++q) { cum[q] = 1.0 + 0.5 * (double)(P - 1 - q) / (double)std::max(P - 1, 1); tot += cum[q]; }
         double run = 0.0;
         for (int q = 0; q < P; ++q) { run += cum[q] / tot; cum[q] = run; }
-        if (const char* e = getenv("TMVB_LDA_PIECE_FRACS")) {          // tuning: "0.3,0.58,0.82"
-            std::vector<double> f;
-            for (const char* c = e; *c;) { char* end; f.push_back(strtod(c, &end)); c = (*end == ',') ? end + 1 : end; if (end == c && *c) break; }
-            for (int q = 0; q + 1 < P && q < (int)f.size(); ++q) cum[q] = f[q];
-        }
         cum[P - 1] = 2.0;
     }
     auto piece_of = [&](int64_t run) { const double x = (double)run / (double)nnz; int q = 0; while (q < P - 1 && x >= cum[q]) ++q; return q; };
@@ -1475,7 +1468,7 @@ extern "C" int tmvb_lda_create(tmvb_ctx* ctx, tmvb_corpus* corp, int32_t K, tmvb
     h->grid_np_max = lda_grid_np_max(h->KP / 4);
     h->grid_path = h->reg_path && h->KP <= 100 && tmvb_termstats_recomputes(h->KP, h->e_padded) &&
                    (uint64_t)h->V * (uint64_t)h->KP * 4u < (1ull << 32) &&            // rows are addressed by 32-bit byte offsets
-                   !(getenv("TMVB_LDA_GRID") && atoi(getenv("TMVB_LDA_GRID")) == 0);
+                   tmvb_env_on("TMVB_LDA_GRID", true);
     if (h->grid_path) {
         std::vector<int> tol;
         switch (h->KP / 4) {
@@ -1503,7 +1496,7 @@ extern "C" int tmvb_lda_create(tmvb_ctx* ctx, tmvb_corpus* corp, int32_t K, tmvb
             h->ev_piece.assign(P, nullptr);
             // the pieces' inverted indices are independent host work (a counting sort over the corpus each, ~50 ms at SYN-NSF's size): one thread per piece
             // (tmvb_lda_create took 150-180 ms of a 265 ms gpuLDA(corp, K) call with them in a row, profiles/r6_train_end_to_end.txt; TMVB_CREATE_THREADS=0: in a row)
-            static const bool create_threads = [] { const char* e = getenv("TMVB_CREATE_THREADS"); return !(e && atoi(e) == 0); }();
+            static const bool create_threads = tmvb_env_on("TMVB_CREATE_THREADS", true);
             std::vector<int> prc((size_t)P, TMVB_OK);
             std::vector<std::string> pmsg((size_t)P);
             auto build_piece = [&](int q) {
@@ -1537,7 +1530,7 @@ extern "C" int tmvb_lda_create(tmvb_ctx* ctx, tmvb_corpus* corp, int32_t K, tmvb
     if (h->M) TMVB_HIP(hipMemcpyAsync(h->d_doc_order, order.data(), (size_t)h->M * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
     TMVB_HIP(hipMemsetAsync(h->d_stats, 0, (KV + K) * sizeof(float), ctx->stream));
     TMVB_HIP(hipMemsetAsync(h->d_sweeps, 0, std::max<size_t>((size_t)h->M, 1), ctx->stream));
-    { const char* t = getenv("TMVB_ESTEP_TIMING"); h->timing = t && atoi(t) != 0; }
+    h->timing = tmvb_env_on("TMVB_ESTEP_TIMING", false);
     TMVB_HIP(hipEventCreate(&h->ev0));
     TMVB_HIP(hipEventCreate(&h->ev1));
     TMVB_HIP(hipEventCreateWithFlags(&h->ev_fork, tmvb_event_flags()));
@@ -1547,7 +1540,7 @@ extern "C" int tmvb_lda_create(tmvb_ctx* ctx, tmvb_corpus* corp, int32_t K, tmvb
     TMVB_HIP(hipEventCreateWithFlags(&h->ev_acopy, tmvb_event_flags()));
     TMVB_HIP(hipEventCreateWithFlags(&h->ev_elbo, tmvb_event_flags()));
     TMVB_HIP(hipEventCreateWithFlags(&h->ev_mark, hipEventDisableTiming /* may sit behind a collective: keeps the system-scope fence */));
-    { const char* e = getenv("TMVB_LDA_ELBO_PARTS"); h->parts_env = e ? atoi(e) : 1; }
+    h->parts_env = tmvb_env_int("TMVB_LDA_ELBO_PARTS", 1);
     if ((rc = dmalloc(&h->d_partial_side, (size_t)TMVB_REDUCE_BLOCKS * K)) || (rc = dmalloc(&h->d_pw_partial, 2048)) || (rc = dmalloc(&h->d_lz_partial, 2048)) || (rc = dmalloc(&h->d_alpha_e, (size_t)K))) return rc;
     for (int a = 0; a < tmvb_lda::NAUX; ++a) {
         h->aux[a] = tmvb_pool_stream(ctx->device, 1 + a);
@@ -1630,7 +1623,7 @@ static int lda_estep_impl(tmvb_lda* h, int32_t viter, double vtol);
 // stream of the side chain (TMVB_LDA_SIDE_STREAM: experiment with the stream -> hardware-queue mapping)
 static int lda_side_index()
 {
-    static const int ix = [] { const char* e = getenv("TMVB_LDA_SIDE_STREAM"); const int v = e ? atoi(e) : (int)tmvb_lda::SIDE; return (v >= 0 && v < (int)tmvb_lda::NAUX) ? v : (int)tmvb_lda::SIDE; }();
+    static const int ix = [] { const int v = tmvb_env_int("TMVB_LDA_SIDE_STREAM", (int)tmvb_lda::SIDE); return (v >= 0 && v < (int)tmvb_lda::NAUX) ? v : (int)tmvb_lda::SIDE; }();
     return ix;
 }
 
@@ -1671,7 +1664,6 @@ static int lda_estep_impl(tmvb_lda* h, int32_t viter, double vtol)
     p.alpha = h->d_alpha_f; p.beta = h->d_beta[h->cur]; p.wtok = h->d_wtok; p.tok_inv = h->pieces.empty() ? h->corp->term_index.d_inv : nullptr; p.E = h->d_E; p.estride = h->estride;
     p.gamma = h->d_gamma; p.elog = h->d_elog; p.elog_old = h->d_elog_old; p.sweeps = h->d_sweeps;
     p.viter = viter; p.vtol = (float)vtol;
-    { const char* dbg = getenv("TMVB_DEBUG_FLAGS"); p.debug = dbg ? atoi(dbg) : 0; }
     p.store_w = tmvb_termstats_recomputes(h->KP, h->e_padded) ? 0 : 1;
     if (h->timing) TMVB_HIP(hipEventRecord(h->ev0, ctx->stream));
     // Stream plan: the register-tile buckets run back to back on aux[0] (piece after piece), the LDS-tile
@@ -1690,7 +1682,7 @@ static int lda_estep_impl(tmvb_lda* h, int32_t viter, double vtol)
     // nothing hides -- follows the last document kernel on the context's stream, as do the M-step and the next E-step: no
     // cross-stream hop is left on the critical path of an iteration (there were two, ~20 us each, around the last pass).
     // TMVB_LDA_CHAIN_AUX=1 restores the round-2 plan (chain on aux[0], every pass on the context's stream).
-    static const bool chain_aux = [] { const char* e = getenv("TMVB_LDA_CHAIN_AUX"); return e && atoi(e) != 0; }();
+    static const bool chain_aux = tmvb_env_on("TMVB_LDA_CHAIN_AUX", false);
     hipStream_t chain_st = (h->reg_path && (P == 1 || !chain_aux)) ? ctx->stream : h->aux[0];
     const bool shadow_stats = P > 1 && chain_st == ctx->stream;       // passes 0 .. P-2 on aux[0]
     if (chain_st == ctx->stream) { int jrc = lda_join_side(h); if (jrc) return jrc; }   // update_alpha! of the last iteration
@@ -1718,7 +1710,7 @@ static int lda_estep_impl(tmvb_lda* h, int32_t viter, double vtol)
     // gather-side statistics of the documents whose kernels precede `after` on its stream:
     //   S[:, j] += beta[:, j] .* sum_tokens w E[:, doc] + eps sum w     (update_beta!(model, d))
     auto stats_pass = [&](const tmvb_inv_index& ix, hipStream_t on, const TermStatsParams& tpp) -> int {
-        if ((p.debug & 1) || ix.n_chunks <= 0) return TMVB_OK;
+        if (ix.n_chunks <= 0) return TMVB_OK;
         return tmvb_launch_termstats(ctx, h->nslot, h->KP, h->e_padded, ix, tpp, on);
     };
     // Decomposed update_elbo! (lda_elbo_doc_kernel): an iteration that will be checked has its statistics passes leave sum c log2 s per chunk
@@ -1731,7 +1723,7 @@ static int lda_estep_impl(tmvb_lda* h, int32_t viter, double vtol)
         if (hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, ctx->device) != hipSuccess || v <= 0) { (void)hipGetLastError(); v = 64 * 1024; }
         h->lds_limit = v;
     }
-    const bool collect = (parts_env == 2 || (parts_env != 0 && h->want_parts)) && tmvb_termstats_recomputes(h->KP, h->e_padded) && !(p.debug & 1) &&
+    const bool collect = (parts_env == 2 || (parts_env != 0 && h->want_parts)) && tmvb_termstats_recomputes(h->KP, h->e_padded) &&
                          viter > 0 &&                               // (viter = 0: the document kernels leave E = 0, not the factor update_elbo! rebuilds phi from)
                          elbo_doc_lds <= (size_t)h->lds_limit;
     std::vector<int64_t> logz_off((size_t)P + 1, 0);
@@ -1757,10 +1749,10 @@ static int lda_estep_impl(tmvb_lda* h, int32_t viter, double vtol)
     // pass 637 - 705 us -- 48 us of a 750 us iteration with the chain waiting).  It now writes a buffer of its own (and its own multi-chunk partials) and
     // starts at once; the join with aux[0] moves behind it, and update_beta!'s column-sum pass adds the two buffers on its way.  One context only (a
     // sharded handle all-reduces d_stats); TMVB_LDA_SPLIT_OUT=0: the round-4 order.
-    static const bool split_out_env = [] { const char* e = getenv("TMVB_LDA_SPLIT_OUT"); return !(e && atoi(e) == 0); }();
+    static const bool split_out_env = tmvb_env_on("TMVB_LDA_SPLIT_OUT", true);
     // (round-5 advice) ... and only into the library's OWN statistics buffer: a host that bound its tensor (tmvb_lda_bind_stats, dist.py) may read it
     // directly between estep and update_beta!, and must see the whole of S there, not S minus the last piece
-    bool split_out = split_out_env && shadow_stats && h->own_stats && !h->distributed && h->comm == nullptr && !h->ar_live && !(p.debug & 1);
+    bool split_out = split_out_env && shadow_stats && h->own_stats && !h->distributed && h->comm == nullptr && !h->ar_live;
     if (split_out && !h->d_stats_b) {
         size_t slots = 1;
         for (const tmvb_inv_index& ix : h->pieces) slots = std::max(slots, (size_t)ix.n_slots);
@@ -1795,7 +1787,8 @@ static int lda_estep_impl(tmvb_lda* h, int32_t viter, double vtol)
             if (piece_open == P - 1 && h->ar_live) {     // tmvb_lda_estep_allreduce: slice by slice, an event behind each
                 const tmvb_inv_index& ix = h->pieces.empty() ? h->ar_index : h->pieces.back();
                 for (int k = 0; k < h->ar_slices; ++k) {
-                    if (!(p.debug & 1)) { int rc = tmvb_launch_termstats(ctx, h->nslot, h->KP, h->e_padded, ix, with_logz(tp, piece_open), pass_st, h->ar_order[(size_t)k]); if (rc) return rc; }
+                    int rc = tmvb_launch_termstats(ctx, h->nslot, h->KP, h->e_padded, ix, with_logz(tp, piece_open), pass_st, h->ar_order[(size_t)k]);
+                    if (rc) return rc;
                     TMVB_HIP(hipEventRecord(h->ev_slice[(size_t)k], pass_st));
                 }
                 continue;
@@ -1906,13 +1899,12 @@ static int lda_estep_impl(tmvb_lda* h, int32_t viter, double vtol)
                 TMVB_HIP(hipFuncSetAttribute((const void*)lda_elbo_doc_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
                 h->elbo_doc_lds_set = (int)lds;
             }
-            static const bool own_stream = [] { const char* e = getenv("TMVB_LDA_ELBO_STREAM"); return !(e && atoi(e) == 0); }();   // 0: in a row on the side stream (A/B)
+            static const bool own_stream = tmvb_env_on("TMVB_LDA_ELBO_STREAM", true);   // 0: in a row on the side stream (A/B)
             hipStream_t es = own_stream ? h->aux[tmvb_lda::ELBO] : side;
             // the kernel starts behind the column sums of Elogtheta (ev_acopy re-recorded behind them) rather than with the end of the document kernels: right
             // beside the last statistics pass it slows that pass more than it gains -- time to the plateau 1.262 / 1.247 / 1.239 s against 1.263 / 1.281 / 1.266 s,
-            // alternating in one call (TMVB_LDA_ELBO_EARLY=1 selects the early start)
-            static const bool early = [] { const char* e = getenv("TMVB_LDA_ELBO_EARLY"); return e && atoi(e) != 0; }();
-            if (!early) TMVB_HIP(hipEventRecord(h->ev_acopy, side));
+            // alternating in one call
+            TMVB_HIP(hipEventRecord(h->ev_acopy, side));
             TMVB_HIP(hipStreamWaitEvent(es, h->ev_chain, 0));     // every document kernel, as the side chain above
             TMVB_HIP(hipStreamWaitEvent(es, h->ev_join[1], 0));
             TMVB_HIP(hipStreamWaitEvent(es, h->ev_acopy, 0));
@@ -1926,7 +1918,7 @@ static int lda_estep_impl(tmvb_lda* h, int32_t viter, double vtol)
         h->side_pending = true;
         h->esum_fresh = true; h->esum_side = true;
     }
-    h->stats_fresh = !(p.debug & 1); h->pw_valid = false;
+    h->stats_fresh = true; h->pw_valid = false;
 #ifdef TMVB_MUTANT_LDA_STALE_PARTS
     if (collect) { h->logz_valid = true; h->n_logz = logz_off[(size_t)P]; }     // MUTANT: an E-step that does not collect leaves the old flag and count alone
 #else
@@ -1969,7 +1961,7 @@ static int lda_ar_prepare(tmvb_lda* h)
 // (default ONE slab: on the 16 100-document shard of an 8-GPU run every further slice costs ~20 us of launches and kernel tails -- fused
     // iteration 0.166 / 0.184 / 0.205 / 0.224 ms with 1 / 2 / 3 / 4 slabs at nranks = 1, tools/ar_slices_probe.py -- against a last pass of
     // ~50 us to hide wire under; what pays at that size is the early collective of the tail, below, which every setting has)
-    const int want = [] { const char* e = getenv("TMVB_AR_SLICES"); return e ? atoi(e) : 1; }();      // read per plan (per communicator)
+    const int want = tmvb_env_int("TMVB_AR_SLICES", 1);      // read per plan (per communicator)
     const int64_t V = h->V;
     int S = (int)std::min<int64_t>(std::max(want, 1), std::max<int64_t>(V, 1));
     if (!(tmvb_termstats_recomputes(h->KP, h->e_padded) && h->reg_path)) S = 1;      // the stored-weight passes keep one collective
@@ -2207,9 +2199,9 @@ static int lda_elbo_enqueue(tmvb_lda* h)
         // behind by its statistics passes and by update_beta!
         use_pw = true; n_vals = h->n_elbo_blocks;
         h->elbo_form = 1;
-    } else if (h->M > 0 && h->reg_path && getenv("TMVB_LDA_ELBO_LEGACY") == nullptr) {
+    } else if (h->M > 0 && h->reg_path) {
         const dim3 grid((unsigned)h->M), block(64);
-        use_pw = h->pw_valid && !h->pw_diff && getenv("TMVB_LDA_ELBO_NO_PW") == nullptr;
+        use_pw = h->pw_valid && !h->pw_diff;
         switch (h->KP / 4) {
 #define LDA_ELBO_CASE(LPRV) case LPRV: \
             if (use_pw) hipLaunchKernelGGL((lda_elbo_reg_kernel<LPRV, false>), grid, block, 0, ctx->stream, h->K, h->d_doc_order, h->corp->d_doc_ptr, \

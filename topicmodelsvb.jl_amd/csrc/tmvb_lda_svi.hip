@@ -106,7 +106,7 @@ extern "C" int tmvb_lda_svi_create(tmvb_ctx* ctx, int64_t M, int64_t V, const in
         tmvb_lda_globals_view gv;
         if ((rc = tmvb_lda_globals_view_of(h->hs[0], &gv))) return rc;
         h->d_beta[0] = gv.beta[0]; h->d_beta[1] = gv.beta[1]; h->cur = gv.cur; h->KP = gv.KP;
-        { const char* e = getenv("TMVB_ESTEP_TIMING"); h->timing = e && atoi(e) != 0; }
+        h->timing = tmvb_env_on("TMVB_ESTEP_TIMING", false);
         guard.release();
         *out = h;
     }

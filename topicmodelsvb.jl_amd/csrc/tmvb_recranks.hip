@@ -228,7 +228,7 @@ int rk_run(tmvb_ctx* ctx, int32_t K, int64_t Md, const double* xd, int64_t Mq, c
     splits = (ntiles + tps - 1) / tps;                  // no empty split
     // the LDS slots of a pass: the default, a smaller number for tests (TMVB_RK_TARGET_SLOTS), never more than the fullest tile needs
     int64_t slots = RK_TGT_SLOTS, need = 1;
-    if (const char* ev = getenv("TMVB_RK_TARGET_SLOTS")) { const long v = atol(ev); if (v >= 1 && v <= RK_TGT_SLOTS) slots = v; }
+    { const long v = tmvb_env_int("TMVB_RK_TARGET_SLOTS", 0); if (v >= 1 && v <= RK_TGT_SLOTS) slots = v; }
     for (int64_t t = 0; t < qtiles; t++) need = std::max(need, tgt_ptr[std::min((t + 1) * NB_QT, Mq)] - tgt_ptr[t * NB_QT]);
     slots = std::min(slots, need);
 

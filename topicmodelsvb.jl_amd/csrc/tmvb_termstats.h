@@ -171,15 +171,14 @@ __global__ __launch_bounds__(256) void termstats_chunk4_kernel(TermStatsParams p
 }
 
 // PAD form of the recompute pass with CPL column chunks per lane (see termstats_recompute_body below for the algorithm and the PAD contract:
-// rows of E zero-padded to 4 * LANES * CPL floats, 32-bit byte offsets, keps > 0 or the select on the row).
+// rows of E zero-padded to 4 * LANES * CPL floats, 32-bit byte offsets, keps > 0 or the select on the row).  The reductions below are written
+// for the one launched shape, 8 lanes per row slot (KP = 100: 8 lanes x 4 chunks).
 template <int LPR, int LANES, int CPL, bool LOGZ = false>
 __device__ __forceinline__ void termstats_recompute_cpl_body(const TermStatsParams& p)
 {
+    static_assert(LANES == 8, "termstats_recompute_cpl_body: 8 lanes per row slot");
     constexpr int SLOTS = 64 / LANES;
-#ifndef TMVB_TS_CPL_U
-#define TMVB_TS_CPL_U ((32 / SLOTS) < 2 ? 2 : ((32 / SLOTS) > 4 ? 4 : (32 / SLOTS)))
-#endif
-    constexpr int U = TMVB_TS_CPL_U;                     // row-slot groups in flight per wave: U * SLOTS rows, U * CPL loads per lane
+    constexpr int U = 4;                                 // row-slot groups in flight per wave: U * SLOTS rows, U * CPL loads per lane
     static_assert(64 % (U * SLOTS) == 0, "the 64 staged tokens are whole groups");
     __shared__ int2 dw_l[4][64];
     typedef float v2f __attribute__((ext_vector_type(2)));
@@ -232,8 +231,7 @@ __device__ __forceinline__ void termstats_recompute_cpl_body(const TermStatsPara
                 float part = d2.x + d2.y;
                 part += dpp_f<0xB1>(part);
                 part += dpp_f<0x4E>(part);
-                if (LANES >= 8) part += dpp_f<0x141>(part);
-                if (LANES >= 16) part += dpp_f<0x140>(part);          // every lane of the slot holds s_n - keps
+                part += dpp_f<0x141>(part);                           // every lane of the slot holds s_n - keps
                 float wz = __builtin_bit_cast(float, dw[u].y) * __builtin_amdgcn_rcpf(part + p.keps);
                 wz = (k0 + u * SLOTS + rs < cnt) ? wz : 0.0f;
                 if constexpr (LOGZ) ll += (k0 + u * SLOTS + rs < cnt) ? (double)(__builtin_bit_cast(float, dw[u].y) * __builtin_amdgcn_logf(part + p.keps)) : 0.0;
@@ -253,22 +251,12 @@ __device__ __forceinline__ void termstats_recompute_cpl_body(const TermStatsPara
 #pragma unroll
     for (int q = 0; q < CPL; ++q) { tot[q][0] = alo[q].x; tot[q][1] = alo[q].y; tot[q][2] = ahi[q].x; tot[q][3] = ahi[q].y; }
     float wsum = wl;
-    if (LANES <= 4) {
 #pragma unroll
-        for (int q = 0; q < CPL; ++q)
+    for (int q = 0; q < CPL; ++q)
 #pragma unroll
-            for (int v = 0; v < 4; ++v) tot[q][v] += dpp_f<0x124>(tot[q][v]);     // row_ror:4
-        wsum += dpp_f<0x124>(wsum);
-        if constexpr (LOGZ) ll += __shfl_xor(ll, 4, 64);          // (lanes cc, cc + 4, cc + 8, cc + 12 of a row, as the two rotations)
-    }
-    if (LANES <= 8) {
-#pragma unroll
-        for (int q = 0; q < CPL; ++q)
-#pragma unroll
-            for (int v = 0; v < 4; ++v) tot[q][v] += dpp_f<0x128>(tot[q][v]);     // row_ror:8
-        wsum += dpp_f<0x128>(wsum);
-        if constexpr (LOGZ) ll += __shfl_xor(ll, 8, 64);
-    }
+        for (int v = 0; v < 4; ++v) tot[q][v] += dpp_f<0x128>(tot[q][v]);         // row_ror:8
+    wsum += dpp_f<0x128>(wsum);
+    if constexpr (LOGZ) ll += __shfl_xor(ll, 8, 64);              // (lanes cc, cc + 8 of a row, as the rotation)
 #pragma unroll
     for (int o = 16; o <= 32; o <<= 1) {
 #pragma unroll
@@ -313,17 +301,17 @@ __device__ __forceinline__ void termstats_recompute_cpl_body(const TermStatsPara
 // slot (LPR active), 64 / LANES row slots per wave instruction; the dot product is a 4-step DPP row reduction
 // (+ one v_permlane16_swap step joining the two 16-lane rows of a 32-lane slot).
 // Round 5 (CPL > 1, PAD form only): a lane owns CPL column chunks of its row slot (chunks cc, cc + LANES, ...), so a row slot needs only
-// LANES = ceil(LPR / CPL) rounded to 4 / 8 / 16 lanes and one wave instruction covers 64 / LANES rows; the per-row VALU work (reduction steps,
+// LANES = ceil(LPR / CPL) rounded up to a power of two and one wave instruction covers 64 / LANES rows; the per-row VALU work (reduction steps,
 // reciprocal, weight, bookkeeping) is shared by more rows with fewer DPP steps (K = 100, 8 lanes x 4 chunks: 8 rows per instruction instead of 2,
 // no v_permlane16_swap; 3.1 instead of ~15 VALU instructions per row).  Measured (profiles/r5_lda_experiments.txt (7)): K = 100 +1.6 % (860.0 /
 // 862.9 -> 875.2 / 875.3 VB it/s with CPL = 4, 870.7 / 874.7 with 2); K = 50 -1 % (CPL = 2) and -7 % (CPL = 4: twice the 128-byte lines per row and
 // instruction) -- the pass is bound by what the L2 delivers to the vector L1s (12 - 15 TB/s of gathered rows), not by its instructions, so the
-// default is CPL = 4 at KP = 100 and the round-4 form (CPL = 1) at KP = 52; TMVB_TS_CPL overrides.
+// launcher takes CPL = 4 at KP = 100 and the round-4 form (CPL = 1) everywhere else; the other forms measured are no longer built.
 template <int LPR_T, int LANES, bool PAD = false, int CPL = 1, bool LOGZ = false>
 __device__ __forceinline__ void termstats_recompute_body(const TermStatsParams& p, int LPR_rt)
 {
-    static_assert(LANES == 4 || LANES == 8 || LANES == 16 || LANES == 32, "termstats_recompute_kernel: 4, 8, 16 or 32 lanes per row slot");
-    static_assert(CPL == 1 || (PAD && LPR_T > 0 && LANES <= 16), "several chunks per lane: PAD form with a compile-time row length only");
+    static_assert(CPL > 1 || LANES == 16 || LANES == 32, "termstats_recompute_kernel: 16 or 32 lanes per row slot");
+    static_assert(CPL == 1 || (PAD && LPR_T > 0), "several chunks per lane: PAD form with a compile-time row length only");
     if constexpr (CPL > 1) { termstats_recompute_cpl_body<LPR_T, LANES, CPL, LOGZ>(p); return; }
     constexpr int SLOTS = 64 / LANES;
     __shared__ int2 dw_l[4][64];

@@ -186,13 +186,13 @@ static int tmvb_train_group_loop(const char* who, H* const* hs, int n, int iter,
             // "single RCCL all-reduce ... per outer iteration").  TMVB_FUSED_ALLREDUCE=1 opts into tmvb_lda_estep_allreduce (the Elogtheta_sum tail
             // all-reduced early on a side stream, the statistics in slabs): two streams of collectives on one communicator, which no multi-rank
             // RCCL run has validated yet (round-4 advice) -- opt-in until tests/test_multigpu_rccl.py has passed on a multi-GPU node.
-            static const bool fuse = [] { const char* e = getenv("TMVB_FUSED_ALLREDUCE"); return e && atoi(e) != 0; }();
+            static const bool fuse = tmvb_env_on("TMVB_FUSED_ALLREDUCE", false);
             if (sharded && n == 1 && fuse) { if ((rc = ops.estep_allreduce(hs[0]))) return rc; fused = true; }
         }
         if constexpr (tmvb_has_graph_ok<Ops, H>::value) {
             // an unchecked iteration of one unsharded handle: captured into a hipGraph at its third occurrence in a row (enough of them left to pay for the
             // capture), replayed from then on; a checked iteration in between runs the ordinary way and the replay resumes behind the next two plain ones
-            static const bool graph_env = [] { const char* e = getenv("TMVB_TRAIN_GRAPH"); return e && atoi(e) != 0; }();     // OPT-IN: measured slower (below)
+            static const bool graph_env = tmvb_env_on("TMVB_TRAIN_GRAPH", false);     // OPT-IN: measured slower (below)
             const bool checked = checkelbo > 0 && (k % checkelbo) == 0;
             if (checked) ig.plain_run = 0;
             if (graph_env && !checked && !sharded && n == 1 && !ig.failed && ops.graph_ok(hs[0])) {
