@@ -744,6 +744,49 @@ typedef struct { int32_t splits, kp; float ms_prep, ms_scan, ms_merge; } tmvb_re
 int tmvb_score_topn(tmvb_ctx* ctx, int32_t K, int64_t Md, const double* xd, int64_t Mq, const double* xq, const int64_t* excl_ptr,
                     const int32_t* excl_idx, int32_t n, int32_t splits, int32_t* idx, float* score, int32_t* count, tmvb_rectopn_info_t* info);
 
+/* ============================== CTPF fold-in: user factors of new libraries with every document factor frozen ==============================
+ * New: the reference moves he once per walk over the corpus (update_he!, src/CTPF.jl:266-277) and has no predict for CTPF
+ * (src/modelutils.jl:831-943).  Here he[:, u] of a user who was not in training is iterated to its fixed point under a trained state.
+ * Inputs: K in [1, 512]; gimel, zayin column-major K x M, dalet, het, vav [K], the hyperparameter e > 0; Un libraries in CSR form
+ * (lib_ptr[Un + 1], lib_docs: 0-based document ids in [0, M), strictly ascending within a user, lib_ratings >= 1); viter >= 0, vtol >= 0;
+ * he0 column-major K x Un, or NULL for all ones (the reference's initial he, src/CTPF.jl:86).
+ * Definition.  With psi = digamma and, once per call,
+ *     W[i, d] = (exp(psi(gimel[i, d])) / dalet[i] + exp(psi(zayin[i, d])) / het[i]) / vav[i],
+ * user u with library lib(u) and ratings r_du runs, from h = he0[:, u],
+ *     sweep:  t = psi(h);  p[:, d] = exp(t) .* W[:, d] / sum_j exp(t_j) W[j, d]  for d in lib(u);  h_new = e + sum_{d in lib(u)} r_du p[:, d]
+ * for at most viter sweeps; after each sweep h <- h_new, and the loop leaves when ||h_new - h||_2 < vtol held for that sweep -- the exit
+ * rule and the sweep count of the document loop (src/CTPF.jl:354-361) with he in the place of gimel.  p[:, d] is xi[1:K, .] + xi[K+1:2K, .]
+ * of update_xi! (:334-337) for the pair (d, u): psi(he[i, u]) enters both halves of the 2K-way softmax at index i, so the halves add up in
+ * front of all sweeps.  One sweep from h = he is the column he_temp[:, u] that one walk of the reference leaves (update_he!(model, d), :274-277).
+ * Outputs: he_out column-major K x Un (fp64 copies of the fp32 results), sweeps_out[Un] = sweeps executed.  viter = 0 returns he0 (rounded to
+ * fp32); an empty library gives h = e exactly (rounded once), after two sweeps under the defaults viter = 10, vtol = 1 / K^2.
+ * Rounding: every input value is rounded ONCE to fp32; W, the sweeps and the exit test are fp32.  exp(t) is taken after subtracting max_j t_j (p
+ * does not change); W needs no shift: exp(psi(x)) <= x, and gimel, zayin are bounded by the corpus's total counts and ratings, so the products
+ * stay far inside fp32.  A shape value below 0.012 has exp(psi(x)) below the fp32 normal range and its term of W flushes to 0.
+ * Purity: a user's result depends on that user's library, he0 column and the state alone -- not on the other users of the call, their order
+ * or number; two calls give the same bits.  No atomics, a fixed summation order.  Users are sorted into launch classes by library length; the
+ * results come back in the caller's order.
+ * Device path: a table kernel (W as [M][kp] fp32, kp = K rounded up to a multiple of 4); one wave per user for libraries of at most
+ * TMVB_FOLDIN_REG_CAP entries (TMVB_FOLDIN_REG_CAP_BIGK for K > 256): the library's W rows are gathered once and stay in registers over all
+ * sweeps; a workgroup of four waves per longer library, which gathers the rows again in every sweep and combines the waves' partial sums in
+ * LDS in a fixed order.
+ * info (or NULL): kp, capacity = the register path's capacity at this K, n_reg / n_long = users on each path, ms_prep (the table kernel) and
+ * ms_sweeps (the user kernels), HIP events around the kernels only.
+ * Errors, judged before the device is touched: a NULL argument, K outside [1, 512], M <= 0, Un < 0, viter < 0, vtol < 0 or not finite,
+ * e <= 0 or not finite, 2^31 - 1 or more library entries -> TMVB_EINVAL; lib_ptr not non-decreasing from 0, a document id outside [0, M),
+ * ids not strictly ascending, a rating < 1, a state value (gimel, zayin, dalet, het, vav, he0) that is not positive and finite ->
+ * TMVB_ESHAPE; then ctx == NULL without a visible device -> TMVB_ENODEVICE (there is no CPU path).
+ * tmvb_ctpf_foldin_users_on: the same operator on the device-resident state of a handle (gimel, zayin, the rates and e as tmvb_ctpf_set_state or
+ * training left them, already fp32 / fp64 on the device): no K x M upload, the same bits as the stateless form on the same state. */
+#define TMVB_FOLDIN_REG_CAP 32
+#define TMVB_FOLDIN_REG_CAP_BIGK 16
+typedef struct { int32_t kp, capacity; int64_t n_reg, n_long; float ms_prep, ms_sweeps; } tmvb_foldin_info_t;
+int tmvb_ctpf_foldin_users(tmvb_ctx* ctx, int32_t K, int64_t M, const double* gimel, const double* zayin, const double* dalet, const double* het,
+                           const double* vav, double e, int64_t Un, const int64_t* lib_ptr, const int32_t* lib_docs, const int32_t* lib_ratings,
+                           const double* he0, int32_t viter, double vtol, double* he_out, int32_t* sweeps_out, tmvb_foldin_info_t* info);
+int tmvb_ctpf_foldin_users_on(tmvb_ctpf* h, int64_t Un, const int64_t* lib_ptr, const int32_t* lib_docs, const int32_t* lib_ratings,
+                              const double* he0, int32_t viter, double vtol, double* he_out, int32_t* sweeps_out, tmvb_foldin_info_t* info);
+
 /* ============================== stochastic (minibatch) training for LDA: stepwise EM ==============================
  * New: the reference's train! moves alpha and beta once per walk over the whole corpus (src/LDA.jl:161-187); the closest precedent for statistics
  * gathered batch by batch is v0.6/src/gpuLDA.jl:200-225.  Here the globals move once per BATCH (Cappe & Moulines / Liang & Klein's stepwise EM, the

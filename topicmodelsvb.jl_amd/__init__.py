@@ -21,6 +21,8 @@ from .neighbors import NeighborsResult, docsim, neighbors_raw, topic_proportions
 from .recs_eval import (HeldReaders, RecEvalResult, rank_metrics, rank_metrics_raw, rec_eval, rec_quality, rec_ranks_raw, split_readers,
                         split_readers_raw)
 from .recs_topn import RecTopN, rec_topn_raw, recommend_topn
+from .ctpf_foldin import (FOLDIN_REG_CAPACITY, FOLDIN_REG_CAPACITY_BIGK, FoldinUsers, foldin_libraries, foldin_reg_capacity, foldin_users,
+                          foldin_users_raw, predict_ctpf, recommend_new_docs, recommend_new_users)
 from .lda_svi import gpuLDAStochastic, gpu_train_stochastic, svi_cuts, svi_order, svi_rho
 from .ctm_svi import gpuCTMStochastic, gpu_train_ctm_stochastic
 
@@ -34,5 +36,7 @@ __all__ = ["CorpusError", "DocumentError", "EngineError", "TopicModelError", "bu
            "NeighborsResult", "docsim", "neighbors_raw", "topic_proportions",
            "HeldReaders", "RecEvalResult", "rank_metrics", "rank_metrics_raw", "rec_eval", "rec_quality", "rec_ranks_raw", "split_readers", "split_readers_raw",
            "RecTopN", "rec_topn_raw", "recommend_topn",
+           "FOLDIN_REG_CAPACITY", "FOLDIN_REG_CAPACITY_BIGK", "FoldinUsers", "foldin_libraries", "foldin_reg_capacity", "foldin_users", "foldin_users_raw",
+           "predict_ctpf", "recommend_new_docs", "recommend_new_users",
            "gpuLDAStochastic", "gpu_train_stochastic", "svi_cuts", "svi_order", "svi_rho",
            "gpuCTMStochastic", "gpu_train_ctm_stochastic"]

@@ -2181,7 +2181,7 @@ int tmvb_ctpf_view_of(tmvb_ctpf* h, tmvb_ctpf_view* v)
 {
     TMVB_REQUIRE(h && v, TMVB_EINVAL, "tmvb_ctpf_recommend: handle is NULL");
     v->ctx = h->ctx; v->corp = h->corp; v->K = h->K; v->M = h->M; v->U = h->U;
-    v->gimel = h->d_gimel; v->zayin = h->d_zayin; v->he = h->d_he; v->rates = h->d_rates;
+    v->gimel = h->d_gimel; v->zayin = h->d_zayin; v->he = h->d_he; v->rates = h->d_rates; v->e = h->hyper[4];
     return TMVB_OK;
 }
 

@@ -144,13 +144,14 @@ struct tmvb_corpus {
     std::vector<int32_t> h_terms, h_readers, h_counts, h_ratings;
     tmvb_inv_index term_index, reader_index;
 };
-// read-only view of a CTPF handle's resident state for the recommendation pass (tmvb_ctpf_recs.hip)
+// read-only view of a CTPF handle's resident state for the recommendation pass (tmvb_ctpf_recs.hip) and the fold-in (tmvb_ctpf_foldin.hip)
 struct tmvb_ctpf_view {
     tmvb_ctx* ctx; tmvb_corpus* corp;
     int K; int64_t M, U;
     const float* gimel; const float* zayin;     // [M][K]
     const float* he;                             // [U][K]
     const double* rates;                         // [8][K]: bet, vav, dalet, het, *_old
+    double e;                                    // hyperparameter e (src/CTPF.jl:81)
 };
 int tmvb_ctpf_view_of(tmvb_ctpf* h, tmvb_ctpf_view* v);
 int tmvb_corpus_term_index(tmvb_corpus* c);
@@ -209,6 +210,8 @@ int tmvb_check_ctx_or_device(const char* fn, tmvb_ctx* ctx);
 //                                   accumulates on top of them; tests/test_svi_mutant_gpu.py
 //   TMVB_MUTANT_CTM_SVI_NO_RECENTRE   the tail kernel of the stochastic CTM driver (tmvb_ctm_svi.hip) blends the running scatter matrix without moving it from
 //                                   m_ref to the current mu first; shows once mu has moved between visits; tests/test_ctm_svi_mutant_gpu.py
+//   TMVB_MUTANT_FOLDIN_DROP_ZAYIN     the table kernel of the CTPF fold-in (tmvb_ctpf_foldin.hip) leaves the zayin term out of W: the users are folded in against
+//                                   gimel alone; tests/test_ctpf_foldin_mutant_gpu.py
 #ifdef TMVB_MUTANT_FLDA_H_NO_GUARD
 #define TMVB_FLDA_H_GUARD(cond) true
 #else

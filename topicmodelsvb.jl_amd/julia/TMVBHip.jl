@@ -1272,6 +1272,53 @@ function score_topn(xd::Matrix{Float64}, xq::Matrix{Float64}, excl_ptr::Vector{I
 	return (idx=Int.(idx) .+ 1, score=score, count=Int.(count), ms=(prep=info.ms_prep, scan=info.ms_scan, merge=info.ms_merge), splits=Int(info.splits))
 end
 
+"tmvb_foldin_info_t (include/tmvb.h), field for field."
+mutable struct TmvbFoldinInfo
+	kp::Int32; capacity::Int32
+	n_reg::Int64; n_long::Int64
+	ms_prep::Float32; ms_sweeps::Float32
+	TmvbFoldinInfo() = new(0, 0, 0, 0, 0f0, 0f0)
+end
+
+"""
+(he, sweeps, info): he[:, u] of users who were not in training, iterated with every document factor frozen (include/tmvb.h, "CTPF fold-in").
+gimel, zayin: K x M; lib_ptr / lib_docs / lib_ratings: the libraries in CSR form, document ids 0-based and strictly ascending inside a user;
+he0: K x Un, or nothing for all ones.
+"""
+function ctpf_foldin_users(gimel::Matrix{Float64}, zayin::Matrix{Float64}, dalet::Vector{Float64}, het::Vector{Float64}, vav::Vector{Float64}, e::Float64,
+		lib_ptr::Vector{Int64}, lib_docs::Vector{Int32}, lib_ratings::Vector{Int32}; he0::Union{Matrix{Float64}, Nothing}=nothing, viter::Integer=10,
+		vtol::Real=1/size(gimel, 1)^2, device::Integer=0)
+	K, M = size(gimel); Un = length(lib_ptr) - 1
+	he = zeros(Float64, K, max(Un, 1)); sweeps = zeros(Int32, max(Un, 1))
+	h0 = he0 === nothing ? Ptr{Float64}(C_NULL) : pointer(he0)
+	info = TmvbFoldinInfo()
+	ctx = tmvb_context(device)
+	GC.@preserve info gimel zayin dalet het vav lib_ptr lib_docs lib_ratings he0 he sweeps begin
+		rc = ccall((:tmvb_ctpf_foldin_users, LIBTMVB), Cint,
+			(Ptr{Cvoid}, Int32, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Float64, Int64, Ptr{Int64}, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}, Int32, Float64, Ptr{Float64}, Ptr{Int32}, Ptr{Cvoid}),
+			ctx, K, M, gimel, zayin, dalet, het, vav, e, Un, lib_ptr, lib_docs, lib_ratings, h0, viter, vtol, he, sweeps, pointer_from_objref(info))
+		tmvb_destroy_context(ctx)
+		tmvb_check(rc)
+	end
+	return (he=he[:, 1:Un], sweeps=Int.(sweeps[1:Un]), info=info)
+end
+
+"The same on the device-resident state of a CTPF handle (`handle`: the Ptr{Cvoid} of tmvb_ctpf_create): no K x M upload."
+function ctpf_foldin_users_on(handle::Ptr{Cvoid}, K::Integer, lib_ptr::Vector{Int64}, lib_docs::Vector{Int32}, lib_ratings::Vector{Int32};
+		he0::Union{Matrix{Float64}, Nothing}=nothing, viter::Integer=10, vtol::Real=1/K^2)
+	Un = length(lib_ptr) - 1
+	he = zeros(Float64, K, max(Un, 1)); sweeps = zeros(Int32, max(Un, 1))
+	h0 = he0 === nothing ? Ptr{Float64}(C_NULL) : pointer(he0)
+	info = TmvbFoldinInfo()
+	GC.@preserve info lib_ptr lib_docs lib_ratings he0 he sweeps begin
+		rc = ccall((:tmvb_ctpf_foldin_users_on, LIBTMVB), Cint,
+			(Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}, Int32, Float64, Ptr{Float64}, Ptr{Int32}, Ptr{Cvoid}),
+			handle, Un, lib_ptr, lib_docs, lib_ratings, h0, viter, vtol, he, sweeps, pointer_from_objref(info))
+		tmvb_check(rc)
+	end
+	return (he=he[:, 1:Un], sweeps=Int.(sweeps[1:Un]), info=info)
+end
+
 """
 recall / precision / ndcg (length(topn) x Mq), mrr, pct_rank (Mq; NaN for a query without targets), their means over the queries with targets
 (recall@topn, precision@topn, ndcg@topn, mrr, pct_rank, in that order), the number of such queries and the number of targets.
