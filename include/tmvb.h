@@ -641,6 +641,45 @@ typedef struct { int32_t splits, kp; float ms_prep, ms_scan, ms_merge; } tmvb_ne
 int tmvb_topic_neighbors(tmvb_ctx* ctx, int32_t K, int32_t metric, int64_t Md, const double* xd, int64_t Mq, const double* xq, int64_t q0,
                          int32_t n, int32_t splits, int32_t* idx, float* score, int32_t* count, tmvb_neighbors_info_t* info);
 
+/* ============================== search documents by words: query likelihood with fused top-n ==============================
+ * Which documents are about these words (the reference has no such function): the query likelihood of LDA-based retrieval (Wei & Croft
+ * 2006) = the held-out log-likelihood of tmvb_heldout_loglik with the roles turned round -- one short "held-out document", every training
+ * document's theta.  theta is K x Md and beta K x V, column-major fp64 on the HOST, exactly as in tmvb_heldout_loglik (theta columns are
+ * distributions under the 1e-6 rule, beta is right stochastic).  The queries are a CSR: q_ptr[Q+1], q_terms 0-based in [0, V), q_counts
+ * >= 1; the entries of a query need be neither sorted nor distinct, their order is the summation order; a query has between 1 and
+ * TMVB_SEARCH_TILE_COLS entries.
+ *
+ * Score.  Theta features: the rows rounded ONCE to fp32 and padded to kp, the TMVB_NB_DOT feature of tmvb_topic_neighbors.  beta' =
+ * (beta + laplace_smooth) / (1 + laplace_smooth V) in fp64, rounded once to fp32; only the W = q_ptr[Q] columns the queries name go to
+ * the device.  p(d, j) = the fp32 fmaf chain over k ascending from 0 -- what v_mfma_f32_32x32x2_f32 leaves, and the same bits
+ * tmvb_topic_neighbors (TMVB_NB_DOT) returns for that pair.  score(q, d) = (float) sum_j c_j log((double) p(d, j)): logarithm and sum in
+ * fp64, j over the query's entries in ascending order, ONE accumulator (acc = fma(c_j, log p, acc)), then one rounding to fp32.  p = 0
+ * gives -inf; no epsilon is added.
+ * Order: the total order of tmvb_topic_neighbors (score descending, index ascending).  A -inf document is a candidate like any other (it
+ * comes before an empty slot), so count[q] = min(n, Md).  idx[Q][n] is 0-based, score[Q][n] holds the scores; slots past count[q] hold
+ * idx = -1 and score = -inf.
+ * Purity: the bits of score(q, d) depend on theta_d, on the query's own entries and on beta', and on nothing else -- not on the other
+ * queries, the query's position in a column tile, Md, the row's position, `splits` (as in tmvb_topic_neighbors) or the order in which
+ * workgroups finish; two calls give the same bytes; queries [a, b) of a call equal the call on that slice; a call on database rows
+ * [a, b) returns for those rows the same score bits as the full call.  No atomics on global memory.
+ * Device path: the host packs whole queries, in order, into column tiles of TMVB_SEARCH_TILE_COLS entries (no query straddles a tile);
+ * a feature kernel for theta; a scan kernel -- a workgroup owns one column tile and one database split, takes the 128 x 128 tile of p
+ * through the tile loop of tmvb_topic_neighbors, puts it into LDS, walks every (row, query) pair's column segment with the fp64 log and
+ * inserts the survivors of the threshold test into the query's sorted n-list --; a merge kernel for splits > 1.  Neither the Md x W
+ * probability matrix nor the Md x Q score matrix ever exists.
+ * info (or NULL): splits, kp, col_tiles = column tiles the queries were packed into, ms_prep / ms_scan / ms_merge = device time of the
+ * feature, scan and merge kernels (HIP events around the kernels only).
+ * Errors, judged before the device is touched: K outside [1, 1024], n outside [1, TMVB_NB_TOPN_MAX], Md <= 0, V <= 0, Q <= 0, Md or V
+ * >= 2^31, splits < 0 or > Md, laplace_smooth < 0 or not finite, a NULL argument, 2^31 - 1 or more entries -> TMVB_EINVAL; q_ptr not
+ * non-decreasing from 0, an empty query, a query of more than TMVB_SEARCH_TILE_COLS entries, a term outside [0, V), a count < 1, beta
+ * not right stochastic, a bad theta column (the wording of tmvb_heldout_loglik) -> TMVB_ESHAPE; then ctx == NULL without a visible
+ * device -> TMVB_ENODEVICE (there is no CPU path). */
+#define TMVB_SEARCH_TILE_COLS 128                           /* query entries per column tile; also the most entries one query may have */
+typedef struct { int32_t splits, kp, col_tiles; float ms_prep, ms_scan, ms_merge; } tmvb_search_info_t;
+int tmvb_topic_search(tmvb_ctx* ctx, int32_t K, int64_t V, int64_t Md, const double* theta, const double* beta, double laplace_smooth,
+                      int64_t Q, const int64_t* q_ptr, const int32_t* q_terms, const int32_t* q_counts,
+                      int32_t n, int32_t splits, int32_t* idx, float* score, int32_t* count, tmvb_search_info_t* info);
+
 /* ============================== held-out recommendation metrics for CTPF: reader split, fused ranks, metrics ==============================
  * Hold out part of the (document, reader) entries, train on the rest, ask where each held-out document lands in its user's ranking (the
  * reference stops at showdrecs / showurecs).

@@ -44,6 +44,8 @@ BENCHED = {
     "rk_feature_kernel": 0, "rk_pairs_kernel": 0, "rk_sort_kernel": 0, "rk_scan_kernel": 0, "rk_fix_kernel": 0,
     # top-n recommendations (tools/rectopn_bench.py): features, the fused MFMA scan / exclusion search / top-n, the merge of the splits' lists
     "rt_feature_kernel": 0, "rt_scan_kernel": 0, "rt_merge_kernel": 0,
+    # search by words (tools/search_bench.py): features, the fused MFMA scan / fp64 log over the query segments / top-n, the merge of the splits' lists
+    "sr_feature_kernel": 0, "sr_scan_kernel": 0, "sr_merge_kernel": 0,
     # stochastic LDA training (tools/svi_bench.py): the fused global update -- blend + partial row sums, then normalise
     "svi_blend_kernel<": 0, "svi_norm_kernel": 0,
     # stochastic CTM training (tools/ctm_svi_bench.py): the tail of the fused global update -- recentre in fp64, blend (the K x V part is the two above)

@@ -239,7 +239,9 @@ class PackedCorpus:
         counts = cat([doc.counts for doc in corp.docs])
         readers = cat([doc.readers for doc in corp.docs]) - 1
         ratings = cat([doc.ratings for doc in corp.docs])
-        return cls(doc_ptr, terms, counts, V, rdr_ptr, readers, ratings, U)
+        pc = cls(doc_ptr, terms, counts, V, rdr_ptr, readers, ratings, U)
+        pc.vocab = dict(corp.vocab)                               # key -> name: search resolves a query's words through it
+        return pc
 
     def to_corpus(self) -> Corpus:
         docs = []

@@ -212,6 +212,8 @@ int tmvb_check_ctx_or_device(const char* fn, tmvb_ctx* ctx);
 //                                   m_ref to the current mu first; shows once mu has moved between visits; tests/test_ctm_svi_mutant_gpu.py
 //   TMVB_MUTANT_FOLDIN_DROP_ZAYIN     the table kernel of the CTPF fold-in (tmvb_ctpf_foldin.hip) leaves the zayin term out of W: the users are folded in against
 //                                   gimel alone; tests/test_ctpf_foldin_mutant_gpu.py
+//   TMVB_MUTANT_SEARCH_DROP_LAST_ENTRY  the scan kernel of the word search (tmvb_search.hip) stops the walk over a query's column segment one entry early: a query of one
+//                                   entry scores 0 everywhere, a longer one loses its last word; tests/test_search_mutant_gpu.py
 #ifdef TMVB_MUTANT_FLDA_H_NO_GUARD
 #define TMVB_FLDA_H_GUARD(cond) true
 #else

@@ -1175,6 +1175,75 @@ function docsim(model::TopicModel; docs::AbstractUnitRange{<:Integer}=1:0, topn:
 			ms=(prep=info.ms_prep, scan=info.ms_scan, merge=info.ms_merge), splits=Int(info.splits))
 end
 
+# ---------------------------------------------------------------------------------------------- search documents by words
+# Which documents are about these words: tmvb_topic_search scores every query -- sum_j c_j log(theta_d . beta'_{w_j}), the query likelihood of
+# LDA-based retrieval -- against every document of the model on the device (probabilities on the f32 MFMA, logarithm and sum in fp64) and keeps,
+# per query, the topn best under the total order (score descending, index ascending); neither the probability matrix nor the score matrix exists.
+
+"tmvb_search_info_t (include/tmvb.h), field for field."
+mutable struct TmvbSearchInfo
+	splits::Int32; kp::Int32; col_tiles::Int32
+	ms_prep::Float32; ms_scan::Float32; ms_merge::Float32
+	TmvbSearchInfo() = new(0, 0, 0, 0f0, 0f0, 0f0)
+end
+
+"One query as (term keys, counts): words through the corpus vocabulary, integers as keys, a Dict as key / word => count; repeated terms are merged."
+function search_query(model::TopicModel, q, skip_unknown::Bool)
+	keys_of = Dict(name => key for (key, name) in model.corp.vocab)
+	terms = Int[]; counts = Int[]
+	for (t, c) in (q isa AbstractDict ? collect(q) : [(t, 1) for t in q])
+		key = t isa AbstractString ? get(keys_of, t, 0) : Int(t)
+		if t isa AbstractString && key == 0
+			skip_unknown && continue
+			throw(ArgumentError("word \"$t\" is not in the model's vocabulary."))
+		end
+		(1 <= key <= model.V)			|| throw(ArgumentError("term id $key outside [1, $(model.V)]."))
+		(c >= 1)						|| throw(ArgumentError("the count of a term must be a positive integer."))
+		i = findfirst(==(key), terms)
+		i === nothing ? (push!(terms, key); push!(counts, Int(c))) : (counts[i] += Int(c))
+	end
+	isempty(terms)						&& throw(ArgumentError("a query is empty."))
+	(length(terms) <= 128)				|| throw(ArgumentError("a query has more than 128 distinct terms."))
+	return terms, counts
+end
+
+"""
+(idx, score, count, loglik_per_token) of the `topn` documents under which each query's words are most likely.  `queries` is a vector; each
+query is a vector of vocabulary strings, a vector of term keys, or a Dict term => count.  Theta is topic_proportions(model) unless `theta`
+(K x M, e.g. of predicted documents) is given.  idx[j, q] is 1-based, 0 past count[q].
+"""
+function search(model::TopicModel, queries::AbstractVector; topn::Integer=10, laplace_smooth::Real=0.0, theta=nothing, skip_unknown::Bool=false, device::Integer=0)
+	model isa hipCTPF					&& throw(TopicModelError("search has no method for CTPF models."))
+	(1 <= topn <= 64)					|| throw(ArgumentError("topn must be an integer in [1, 64]."))
+	(laplace_smooth >= 0)				|| throw(ArgumentError("laplace_smooth parameter must be nonnegative."))
+	isempty(queries)					&& throw(ArgumentError("queries is empty."))
+	th = Matrix{Float64}(theta === nothing ? topic_proportions(model) : theta)
+	K, Md = size(th)
+	beta = Matrix{Float64}(model.beta)
+	(size(beta, 1) == K)				|| throw(TopicModelError("theta and model must have the same number of topics."))
+	V = size(beta, 2)
+	q_ptr = Int64[0]; q_terms = Int32[]; q_counts = Int32[]
+	for q in queries
+		terms, counts = search_query(model, q, skip_unknown)
+		append!(q_terms, Int32.(terms .- 1)); append!(q_counts, Int32.(counts)); push!(q_ptr, length(q_terms))
+	end
+	Q = length(queries)
+	idx = zeros(Int32, topn, Q); score = zeros(Float32, topn, Q); count = zeros(Int32, Q)	# column-major (j, q) = C's [q][j]
+	info = TmvbSearchInfo()
+	ctx = tmvb_context(device)
+	GC.@preserve info th beta q_ptr q_terms q_counts idx score count begin
+		rc = ccall((:tmvb_topic_search, LIBTMVB), Cint,
+			(Ptr{Cvoid}, Int32, Int64, Int64, Ptr{Float64}, Ptr{Float64}, Float64, Int64, Ptr{Int64}, Ptr{Int32}, Ptr{Int32}, Int32, Int32, Ptr{Int32}, Ptr{Float32}, Ptr{Int32}, Ptr{Cvoid}),
+			ctx, K, V, Md, th, beta, Float64(laplace_smooth), Q, q_ptr, q_terms, q_counts,
+			topn, 0, idx, score, count, pointer_from_objref(info))
+		tmvb_destroy_context(ctx)
+		tmvb_check(rc)
+	end
+	tokens = [sum(q_counts[q_ptr[q]+1:q_ptr[q+1]]) for q in 1:Q]
+	return (idx=Int.(idx) .+ 1, score=score, count=Int.(count), loglik_per_token=Float64.(score) ./ reshape(Float64.(tokens), 1, Q),
+			info=(splits=Int(info.splits), kp=Int(info.kp), col_tiles=Int(info.col_tiles), ms=(prep=info.ms_prep, scan=info.ms_scan, merge=info.ms_merge)))
+end
+
 # ---- held-out recommendation metrics for CTPF (include/tmvb.h: tmvb_readers_split, tmvb_score_ranks, tmvb_rank_metrics) -------------------
 # Hold out part of the (document, reader) entries, train on the rest, ask where each held-out document lands in its user's ranking.  The rank of
 # a held-out pair is a count -- how many candidates come before it under reverse(sortperm(.)) -- taken in the epilogue of the f32-MFMA score GEMM
