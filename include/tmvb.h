@@ -680,6 +680,44 @@ int tmvb_topic_search(tmvb_ctx* ctx, int32_t K, int64_t V, int64_t Md, const dou
                       int64_t Q, const int64_t* q_ptr, const int32_t* q_terms, const int32_t* q_counts,
                       int32_t n, int32_t splits, int32_t* idx, float* score, int32_t* count, tmvb_search_info_t* info);
 
+/* ============================== word-topic assignments: per-token responsibilities with fused top-t ==============================
+ * Which topic a word belongs to in a document: phi of update_phi! (src/LDA.jl:150-154, src/CTM.jl:175-178, src/CTPF.jl:327-330), the one model
+ * output the reference's update_host! fills (src/modelutils.jl:514-515, :534-535, :559-560) and this engine never keeps.  Stateless and
+ * family-agnostic: for entry n (term w, count c) of document d
+ *     y_k = eps + A[k, d] B[k, w],    r_k = y_k / sum_j y_j,    k = 0 .. K - 1,
+ * with A (K x M) and B (K x V) column-major fp64 on the HOST, both nonnegative: LDA A = exp(Elogtheta), B = beta; CTM A = exp(lambda_d -
+ * max_k lambda_d), B = beta; CTPF A = exp(psi(gimel_d) - log dalet - log bet - column max), B = exp(psi(alef_w) - column max).  eps is the
+ * reference's @positive (EPSILON, src/macros.jl:34-39, src/LDA.jl:152); for CTM and CTPF the eps-form is the softmax wherever sum A B >> eps.
+ * Rounding: A, B and eps are rounded ONCE to fp32; y_k = fma(A, B, eps), the sum in a fixed order (per 16-byte chunk ((y0 + y1) + (y2 + y3)),
+ * a lane's chunks ascending, the lanes of an entry in an xor butterfly) and the IEEE division are fp32.  With eps in [2^-100, 1] every y_k is a
+ * normal positive number.  Products beyond fp32 are the caller's to avoid (shift the columns as above).
+ * Selection.  The CSR is tmvb_corpus_create's (a document without entries is legal).  docs[Ms]: 0-based document ids, repeats and any order
+ * allowed; NULL = all M documents in order (Ms is then M or 0).  The selected documents' entries are numbered 0 .. nsel - 1 in docs order.
+ * Outputs, each may be NULL (top_idx and top_r together), at least one is not:
+ *   top_idx[nsel][t], top_r[nsel][t]   the t best topics of every entry under (r bits descending, topic id ascending); slots past K hold -1 and 0;
+ *   phi[nsel][K]                       the dense fp32 responsibilities, K contiguous per entry (the reference's hcat layout);
+ *   hard[Ms][K]                        int64, sum of c_n over the document's entries whose best topic is k.
+ * max_chunk_entries bounds the entries per launch group and with it the padded device buffer of the dense output ([chunk][KP] fp32); 0 = the
+ * library's choice: with phi as many entries as keep that buffer at 256 MiB, without phi one chunk.  A document is cut where a chunk ends.
+ * Purity: an entry's results depend on its document's A column, its term's B column and eps alone -- not on docs, the chunks, the other outputs
+ * or the order in which workgroups finish; two calls give the same bytes.  No atomics.
+ * info (or NULL): nsel, n_short / n_long = work items (runs of entries of one document inside one chunk) on the 64- and the 256-lane kernel,
+ * chunks, lanes_per_entry (64 / lanes_per_entry entries per trip of a wave), ms_kernel = device time of the kernels (HIP events around them).
+ * Errors, judged before the device is touched, all TMVB_EINVAL: K outside [1, 1024], t outside [1, TMVB_TT_TOP_MAX], eps outside [2^-100, 1]
+ * or NaN, M <= 0, V <= 0, a NULL input, every output NULL, top_idx without top_r, max_chunk_entries < 0, doc_ptr not non-decreasing from 0,
+ * 2^31 - 2 or more entries (of the CSR or selected), a term outside [0, V), a count < 1, an id of docs outside [0, M), a selected document of 2^31 or more tokens, a
+ * value of B or of a selected column of A that is negative, NaN or beyond fp32; then ctx == NULL without a visible device -> TMVB_ENODEVICE (there is no CPU path).
+ *
+ * tmvb_digamma_f64: HOST ONLY, touches no device.  y[i] = psi(x[i]) in fp64 by the engine's host digamma (the recurrence below 7 and the
+ * asymptotic series of the reference's own helper, src/utils.jl:21-53, in fp64; within 1/4 of the positive root 1.46163... a Taylor series
+ * about the root, which keeps the RELATIVE error at 1e-14 where psi passes through 0), so that the CTPF factors above need no SciPy.  x > 0. */
+#define TMVB_TT_TOP_MAX 8
+typedef struct { int64_t nsel, n_short, n_long; int32_t chunks, lanes_per_entry; float ms_kernel; } tmvb_token_topics_info_t;
+int tmvb_token_topics(tmvb_ctx* ctx, int32_t K, int64_t V, int64_t M, const double* A, const double* B, const int64_t* doc_ptr,
+                      const int32_t* terms, const int32_t* counts, const int32_t* docs, int64_t Ms, double eps, int32_t t,
+                      int64_t max_chunk_entries, int32_t* top_idx, float* top_r, float* phi, int64_t* hard, tmvb_token_topics_info_t* info);
+int tmvb_digamma_f64(const double* x, double* y, int64_t n);
+
 /* ============================== held-out recommendation metrics for CTPF: reader split, fused ranks, metrics ==============================
  * Hold out part of the (document, reader) entries, train on the rest, ask where each held-out document lands in its user's ranking (the
  * reference stops at showdrecs / showurecs).

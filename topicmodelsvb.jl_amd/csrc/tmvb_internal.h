@@ -214,6 +214,8 @@ int tmvb_check_ctx_or_device(const char* fn, tmvb_ctx* ctx);
 //                                   gimel alone; tests/test_ctpf_foldin_mutant_gpu.py
 //   TMVB_MUTANT_SEARCH_DROP_LAST_ENTRY  the scan kernel of the word search (tmvb_search.hip) stops the walk over a query's column segment one entry early: a query of one
 //                                   entry scores 0 everywhere, a longer one loses its last word; tests/test_search_mutant_gpu.py
+//   TMVB_MUTANT_TT_TIE_LAST         the cross-lane merge of the top-t selection of the word-topic assignments (tmvb_token_topics.hip) lets the HIGHER topic id win an
+//                                   exact tie of the r bits; only entries whose tied topics sit in different lanes show it; tests/test_token_topics_mutant_gpu.py
 #ifdef TMVB_MUTANT_FLDA_H_NO_GUARD
 #define TMVB_FLDA_H_GUARD(cond) true
 #else

@@ -1244,6 +1244,86 @@ function search(model::TopicModel, queries::AbstractVector; topn::Integer=10, la
 			info=(splits=Int(info.splits), kp=Int(info.kp), col_tiles=Int(info.col_tiles), ms=(prep=info.ms_prep, scan=info.ms_scan, merge=info.ms_merge)))
 end
 
+# ---------------------------------------------------------------------------------------------- word-topic assignments
+# Which topic a word belongs to in a document: phi of update_phi! (src/LDA.jl:150-154, src/CTM.jl:175-178, src/CTPF.jl:327-330), which update_host!
+# fills in the reference (src/modelutils.jl:514-515, :534-535, :559-560) and the engine never keeps.  tmvb_token_topics recomputes it on the device
+# from two nonnegative factors, r_k = (EPSILON + A[k, d] B[k, w]) / sum_j (...), selects the `top` best topics per entry in registers and returns
+# dense phi only for the documents asked for.
+
+"tmvb_token_topics_info_t (include/tmvb.h), field for field."
+mutable struct TmvbTokenTopicsInfo
+	nsel::Int64; n_short::Int64; n_long::Int64
+	chunks::Int32; lanes_per_entry::Int32
+	ms_kernel::Float32
+	TmvbTokenTopicsInfo() = new(0, 0, 0, 0, 0, 0f0)
+end
+
+"psi in fp64 by the library's host digamma (tmvb_digamma_f64; touches no device)."
+function tmvb_digamma(x::Array{Float64})
+	y = similar(x)
+	GC.@preserve x y begin
+		tmvb_check(ccall((:tmvb_digamma_f64, LIBTMVB), Cint, (Ptr{Float64}, Ptr{Float64}, Int64), x, y, length(x)))
+	end
+	return y
+end
+
+"(A, B), K x M and K x V: the factors of update_phi! by family; the column shifts are taken in fp64 and cancel in the normalisation."
+token_factors(model::hipLDA) = (exp.(hcat(model.Elogtheta...)), Matrix{Float64}(model.beta))
+function token_factors(model::hipCTM)
+	lam = hcat(model.lambda...)
+	return exp.(lam .- maximum(lam, dims=1)), Matrix{Float64}(model.beta)
+end
+function token_factors(model::hipCTPF)
+	a = tmvb_digamma(hcat(model.gimel...)) .- log.(model.dalet) .- log.(model.bet)
+	b = tmvb_digamma(Matrix{Float64}(model.alef))
+	return exp.(a .- maximum(a, dims=1)), exp.(b .- maximum(b, dims=1))
+end
+
+function token_topics_call(model::Union{hipLDA, hipCTM, hipCTPF}, docs::Vector{Int}, top::Integer, want_top::Bool, want_phi::Bool, want_hard::Bool, device::Integer)
+	(1 <= top <= 8)						|| throw(ArgumentError("top must be an integer in [1, 8]."))
+	all(d -> 1 <= d <= model.M, docs)	|| throw(CorpusError("document index outside corpus range."))
+	update_host!(model)
+	A, B = token_factors(model)
+	K, M = size(A); V = size(B, 2)
+	doc_ptr, terms, counts = corp_csr(model.corp)
+	zdocs = Int32.(docs .- 1)
+	Ms = length(zdocs)
+	sel_ptr = cumsum(vcat(0, [doc_ptr[d+1] - doc_ptr[d] for d in docs]))
+	nsel = sel_ptr[end]
+	top_idx = fill(Int32(-1), top, max(nsel, 1)); top_r = zeros(Float32, top, max(nsel, 1))		# column-major (j, n) = C's [n][j]
+	phi = zeros(Float32, K, want_phi ? max(nsel, 1) : 1)										# column-major (k, n) = C's [n][k]: the reference's hcat layout
+	hard = zeros(Int64, K, max(Ms, 1))
+	info = TmvbTokenTopicsInfo()
+	ctx = tmvb_context(device)
+	GC.@preserve info A B doc_ptr terms counts zdocs top_idx top_r phi hard begin
+		rc = ccall((:tmvb_token_topics, LIBTMVB), Cint,
+			(Ptr{Cvoid}, Int32, Int64, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Int64, Float64, Int32, Int64, Ptr{Int32}, Ptr{Float32}, Ptr{Float32}, Ptr{Int64}, Ptr{Cvoid}),
+			ctx, K, V, M, A, B, doc_ptr, terms, counts, zdocs, Ms, EPSILON, top, 0,
+			want_top ? pointer(top_idx) : Ptr{Int32}(C_NULL), want_top ? pointer(top_r) : Ptr{Float32}(C_NULL), want_phi ? pointer(phi) : Ptr{Float32}(C_NULL), want_hard ? pointer(hard) : Ptr{Int64}(C_NULL), pointer_from_objref(info))
+		tmvb_destroy_context(ctx)
+		tmvb_check(rc)
+	end
+	return (sel_ptr=sel_ptr, nsel=nsel, top_idx=top_idx[:, 1:nsel], top_r=top_r[:, 1:nsel], phi=phi, hard=hard[:, 1:Ms],
+			info=(nsel=Int(info.nsel), n_short=Int(info.n_short), n_long=Int(info.n_long), chunks=Int(info.chunks), lanes_per_entry=Int(info.lanes_per_entry), ms_kernel=info.ms_kernel))
+end
+
+"""
+(topic, prob, hard, doc_ptr, docs) for the entries of the documents `docs` (1-based, repeats allowed; by default every document): topic[j, n] is the
+j-th best topic (1-based; 0 past K) of the n-th selected entry, prob[j, n] its responsibility, hard[k, s] the tokens of docs[s] whose best topic is k;
+the entries of docs[s] are doc_ptr[s]+1 : doc_ptr[s+1].
+"""
+function token_topics(model::Union{hipLDA, hipCTM, hipCTPF}; docs=1:0, top::Integer=1, device::Integer=0)
+	ds = isempty(docs) ? collect(1:model.M) : collect(Int, docs)
+	r = token_topics_call(model, ds, top, true, false, true, device)
+	return (topic=Int.(r.top_idx) .+ 1, prob=r.top_r, hard=r.hard, doc_ptr=r.sel_ptr, docs=ds, info=r.info)
+end
+
+"phi of document d as the reference keeps it in model.phi (K x N_d, Float32): update_phi! on the device."
+function phi(model::Union{hipLDA, hipCTM, hipCTPF}, d::Integer)
+	r = token_topics_call(model, [Int(d)], 1, false, true, false, 0)
+	return r.phi[:, 1:r.nsel]
+end
+
 # ---- held-out recommendation metrics for CTPF (include/tmvb.h: tmvb_readers_split, tmvb_score_ranks, tmvb_rank_metrics) -------------------
 # Hold out part of the (document, reader) entries, train on the rest, ask where each held-out document lands in its user's ranking.  The rank of
 # a held-out pair is a count -- how many candidates come before it under reverse(sortperm(.)) -- taken in the epilogue of the f32-MFMA score GEMM
