@@ -273,6 +273,9 @@ int tmvb_lda_doc_sweeps(tmvb_lda* h, uint8_t* out);
 int tmvb_lda_elbo_form(tmvb_lda* h, int32_t* form);
 /* Number of kernel launches one tmvb_lda_estep issues (one per document-length bucket). */
 int tmvb_lda_estep_launches(tmvb_lda* h, int32_t* n);
+/* Number of document pieces tmvb_lda_estep runs its statistics passes in, as fixed at tmvb_lda_create (1: one pass over the corpus' own index;
+ * TMVB_LDA_PIECES overrides the size rule). */
+int tmvb_lda_estep_pieces(tmvb_lda* h, int32_t* pieces);
 /* Timing of the last tmvb_lda_estep on the context's stream, from HIP events (ms). */
 int tmvb_lda_last_estep_ms(tmvb_lda* h, float* ms);
 

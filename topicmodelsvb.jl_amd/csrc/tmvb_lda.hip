@@ -1542,8 +1542,14 @@ extern "C" int tmvb_lda_create(tmvb_ctx* ctx, tmvb_corpus* corp, int32_t K, tmvb
     TMVB_HIP(hipEventCreateWithFlags(&h->ev_mark, hipEventDisableTiming /* may sit behind a collective: keeps the system-scope fence */));
     h->parts_env = tmvb_env_int("TMVB_LDA_ELBO_PARTS", 1);
     if ((rc = dmalloc(&h->d_partial_side, (size_t)TMVB_REDUCE_BLOCKS * K)) || (rc = dmalloc(&h->d_pw_partial, 2048)) || (rc = dmalloc(&h->d_lz_partial, 2048)) || (rc = dmalloc(&h->d_alpha_e, (size_t)K))) return rc;
+    // Round 7: in the three-piece plan aux[1] (the long documents, then the side chain: Elogtheta column sums and update_alpha!) is a HIGH-PRIORITY stream.
+    // In a process started with GPU_MAX_HW_QUEUES=4 the kernel trace shows aux[1]'s kernels on the context stream's hardware queue: the long documents' kernels
+    // in front of the chain's first, the side chain in a row with update_beta! (profiles/r7_lda_k50_timeline_before.txt).  As a high-priority stream it is on
+    // a queue of its own (profiles/r7_lda_k50_timeline_after.txt).  With eight queues the two were apart already and nothing changes; K = 100's two-piece plan
+    // measured 0.65 % slower with it and keeps a normal stream (profiles/r7_lda_tail_bench.json).  TMVB_LDA_SIDE_PRIORITY=0: a normal-priority stream everywhere.
+    const bool side_priority = h->pieces.size() >= 3 && tmvb_env_on("TMVB_LDA_SIDE_PRIORITY", true);
     for (int a = 0; a < tmvb_lda::NAUX; ++a) {
-        h->aux[a] = tmvb_pool_stream(ctx->device, 1 + a);
+        h->aux[a] = tmvb_pool_stream(ctx->device, 1 + a, a == 1 && side_priority);
         TMVB_REQUIRE(h->aux[a] != nullptr, TMVB_EHIP, "hipStreamCreate failed");
         TMVB_HIP(hipEventCreateWithFlags(&h->ev_join[a], tmvb_event_flags()));
     }
@@ -2364,6 +2370,14 @@ extern "C" int tmvb_lda_estep_launches(tmvb_lda* h, int32_t* n)
 {
     TMVB_REQUIRE(h && n, TMVB_EINVAL, "tmvb_lda_estep_launches: NULL argument");
     *n = (int32_t)h->buckets.size();
+    return TMVB_OK;
+}
+
+extern "C" int tmvb_lda_estep_pieces(tmvb_lda* h, int32_t* pieces)
+{
+    TMVB_REQUIRE(h && pieces, TMVB_EINVAL, "tmvb_lda_estep_pieces: NULL argument");
+    const int P = std::max<int>((int)h->pieces.size(), 1);
+    *pieces = P;
     return TMVB_OK;
 }
 

@@ -325,6 +325,12 @@ class gpuLDA:
         check(lib().tmvb_lda_estep_launches(self.handle, C.byref(n)))
         return n.value
 
+    def estep_pieces(self) -> int:
+        """Document pieces of the E-step's statistics passes, fixed at construction (1: one pass)."""
+        n = C.c_int32(0)
+        check(lib().tmvb_lda_estep_pieces(self.handle, C.byref(n)))
+        return n.value
+
     def elbo_form(self) -> int:
         """1 if the last update_elbo! took the decomposed form (parts left behind by the iteration itself), 0 for the token walk."""
         f = C.c_int32(0)
