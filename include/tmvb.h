@@ -644,6 +644,53 @@ typedef struct { int32_t splits, kp; float ms_prep, ms_scan, ms_merge; } tmvb_ne
 int tmvb_topic_neighbors(tmvb_ctx* ctx, int32_t K, int32_t metric, int64_t Md, const double* xd, int64_t Mq, const double* xq, int64_t q0,
                          int32_t n, int32_t splits, int32_t* idx, float* score, int32_t* count, tmvb_neighbors_info_t* info);
 
+/* ============================== cluster documents in topic space: k-means with fused assignment ==============================
+ * Lloyd's algorithm on the rows of x (column-major K x M fp64 on the HOST, as xd of tmvb_topic_neighbors; the reference has no such function).
+ * init: K x C centroids in feature space (column c = centroid c), or NULL: k-means++ on the device.  Outputs: label[M] (0-based), centroid[K C]
+ * (the fp32 centroid values widened to fp64, feature space, column c = centroid c), count[C], dist2[M] (each document's squared distance to its
+ * centroid), inertia[max_iter + 1] (J^t for t <= iters, NaN beyond), seeds[C] (the chosen document ids; -1 everywhere when init is given).
+ *
+ * Features: F[M][kp] fp32 as in tmvb_topic_neighbors -- TMVB_KM_EUCLID the row as given, TMVB_KM_HELLINGER sqrt(x), TMVB_KM_COSINE x / ||x||_2 --
+ * each value rounded ONCE, kp = K rounded up to a multiple of 4, pads zero.  n_d = the fp32 fmaf chain of f_dk^2 over k = 0 .. K - 1 ascending
+ * from 0.  Centroids Cf[C][kp] have the same layout, n_c is the same chain over the centroid, b_c = -0.5f n_c.
+ * Assignment: a(d, c) = the f32-MFMA chain of tmvb_topic_neighbors (fp32, k ascending from 0; padding contributes nothing, tiling cannot change
+ * a bit); s(d, c) = a(d, c) + b_c, one fp32 add; label[d] = the c of largest s, the LOWEST c on equal s; dist2[d] = max(0, fmaf(-2,
+ * s(d, label[d]), n_d)).  J = the fp64 sum of the dist2 values in a fixed order: documents in blocks of TMVB_KM_RUN ascending, each block
+ * summed sequentially ascending, the block sums added sequentially ascending.
+ * Update: count[c] is an exact integer.  The members of c in ascending document id are cut into runs of TMVB_KM_RUN; each run of F rows is
+ * summed sequentially ascending in fp64, the run sums are added sequentially ascending.  EUCLID, HELLINGER: centroid = (float)(sum /
+ * (double)count).  COSINE: centroid = (float)(sum / ||sum||_2), the norm in fp64 (spherical k-means).  A cluster without members keeps its
+ * centroid; n_empty counts such clusters in the last assignment.  No floating-point atomics anywhere (integer ones for the histogram and
+ * the changed-label counter).
+ * Loop: c^0 = init rounded once to fp32, or the seeding.  For t = 0, 1, ...: (1) label^t = assign(c^t), which gives J^t; (2) t >= 1 and no label
+ * differs from label^(t-1): stop = 1 (c^t is then the mean of these labels); (3) t == max_iter: stop = 0; (4) tol > 0, t >= 1 and J^(t-1) - J^t
+ * <= tol J^(t-1): stop = 2; (5) else c^(t+1) = update(label^t, c^t).  Returned: label^t, c^t, count^t, dist2^t, iters = t -- every returned
+ * label is the best centroid among the RETURNED centroids.  max_iter = 0 is "assign only".
+ * Seeding (init == NULL), k-means++: u_j = tmvb_u53(x[0], x[1]) of tmvb_rng(seed, j, TMVB_RNG_KMEANS, 0, 0).  Seed 0 = document floor(u_0 M).
+ * Round j >= 1: m[d] = min over the seeds s so far of D2(d, s), in fp64 from the fp32 features: dot = sum_k (double)f_dk (double)f_sk
+ * sequentially ascending (every product is exact), N_d and N_s the same sums of a row with itself, D2 = max(0, (N_d + N_s) - 2 dot).  cum = the
+ * prefix sum of m in the blocked order of J: cum(d) = (block sums before d's block, added sequentially from 0) + (m of d's block up to and
+ * including d, added sequentially); total = all block sums.  The pick is the first d with cum(d) > u_j total; with total == 0, or no such d,
+ * the lowest document id not yet chosen.  c^0 = the picked rows of F.
+ * Purity: the same inputs give the same bytes, independent of launch geometry and of the order in which workgroups finish; an assign-only call
+ * on documents [a, b) equals that slice of the full assign-only call.
+ * info (or NULL): iters, stop, n_empty, kp, moved_last = labels that differ from the previous assignment at the last one (M at t = 0),
+ * ms_prep / ms_seed = device time of the feature and seeding kernels, ms_assign / ms_update = device time of ALL assignment (with J) and ALL
+ * update steps of the call (HIP events around the kernels).
+ * Errors, judged before the device is touched: K outside [1, 1024], C outside [1, min(M, TMVB_KM_CMAX)], M <= 0 or >= 2^31, max_iter outside
+ * [0, 10000], tol negative or not finite, an unknown metric, a NULL required argument (everything but init and info) -> TMVB_EINVAL; a
+ * non-finite entry of x or init, HELLINGER: a negative entry or a column sum off 1 by more than 1e-6 (x only: init is in feature space),
+ * COSINE: a negative entry or an all-zero row -> TMVB_ESHAPE; then ctx == NULL without a visible device -> TMVB_ENODEVICE (no CPU path). */
+#define TMVB_KM_EUCLID    0
+#define TMVB_KM_HELLINGER 1
+#define TMVB_KM_COSINE    2
+#define TMVB_KM_CMAX   1024
+#define TMVB_KM_RUN     256                                 /* members / documents per fixed-order partial sum */
+typedef struct { int32_t iters, stop, n_empty, kp; int64_t moved_last; float ms_prep, ms_seed, ms_assign, ms_update; } tmvb_kmeans_info_t;
+int tmvb_topic_kmeans(tmvb_ctx* ctx, int32_t K, int32_t metric, int64_t M, const double* x, int32_t C, const double* init, int64_t seed,
+                      int32_t max_iter, double tol, int32_t* label, double* centroid, int64_t* count, float* dist2, double* inertia,
+                      int32_t* seeds, tmvb_kmeans_info_t* info);
+
 /* ============================== search documents by words: query likelihood with fused top-n ==============================
  * Which documents are about these words (the reference has no such function): the query likelihood of LDA-based retrieval (Wei & Croft
  * 2006) = the held-out log-likelihood of tmvb_heldout_loglik with the roles turned round -- one short "held-out document", every training

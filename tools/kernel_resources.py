@@ -48,6 +48,9 @@ BENCHED = {
     "sr_feature_kernel": 0, "sr_scan_kernel": 0, "sr_merge_kernel": 0,
     # word-topic assignments (tools/token_topics_bench.py): both workgroup sizes, selection only and selection + dense stores
     "token_topics_kernel<64, false>": 0, "token_topics_kernel<256, false>": 0, "token_topics_kernel<64, true>": 0, "token_topics_kernel<256, true>": 0,
+    # clustering in topic space (tools/cluster_bench.py): features and norms, the fused MFMA assignment, the fixed-order update, the k-means++ rounds
+    "km_feature_kernel": 0, "km_norm_kernel": 0, "km_assign_kernel": 0, "km_run_sum_kernel": 0, "km_finalize_kernel": 0, "km_seed_dist_kernel": 0,
+    "km_seed_pick_kernel": 0,
     # stochastic LDA training (tools/svi_bench.py): the fused global update -- blend + partial row sums, then normalise
     "svi_blend_kernel<": 0, "svi_norm_kernel": 0,
     # stochastic CTM training (tools/ctm_svi_bench.py): the tail of the fused global update -- recentre in fp64, blend (the K x V part is the two above)

@@ -18,6 +18,7 @@ from .gencorp import gencorp, gencorp_raw, gendoc
 from .heldout import HeldoutResult, heldout_loglik, heldout_loglik_raw, perplexity, split_corpus, split_corpus_raw
 from .coherence import CoherenceResult, coherence, coherence_from_counts, coherence_from_counts_raw, codocfreq_raw
 from .neighbors import NeighborsResult, docsim, neighbors_raw, topic_proportions
+from .cluster import ClusterResult, cluster_docs, kmeans_raw
 from .search import SearchInfo, SearchResult, pack_queries, search, search_raw
 from .token_topics import TokenTopics, phi, token_factors, token_topics, token_topics_raw
 from .recs_eval import (HeldReaders, RecEvalResult, rank_metrics, rank_metrics_raw, rec_eval, rec_quality, rec_ranks_raw, split_readers,
@@ -36,6 +37,7 @@ __all__ = ["CorpusError", "DocumentError", "EngineError", "TopicModelError", "bu
            "HeldoutResult", "heldout_loglik", "heldout_loglik_raw", "perplexity", "split_corpus", "split_corpus_raw",
            "CoherenceResult", "coherence", "coherence_from_counts", "coherence_from_counts_raw", "codocfreq_raw",
            "NeighborsResult", "docsim", "neighbors_raw", "topic_proportions",
+           "ClusterResult", "cluster_docs", "kmeans_raw",
            "SearchInfo", "SearchResult", "pack_queries", "search", "search_raw",
            "TokenTopics", "phi", "token_factors", "token_topics", "token_topics_raw",
            "HeldReaders", "RecEvalResult", "rank_metrics", "rank_metrics_raw", "rec_eval", "rec_quality", "rec_ranks_raw", "split_readers", "split_readers_raw",

@@ -216,6 +216,8 @@ int tmvb_check_ctx_or_device(const char* fn, tmvb_ctx* ctx);
 //                                   entry scores 0 everywhere, a longer one loses its last word; tests/test_search_mutant_gpu.py
 //   TMVB_MUTANT_TT_TIE_LAST         the cross-lane merge of the top-t selection of the word-topic assignments (tmvb_token_topics.hip) lets the HIGHER topic id win an
 //                                   exact tie of the r bits; only entries whose tied topics sit in different lanes show it; tests/test_token_topics_mutant_gpu.py
+//   TMVB_MUTANT_KM_NO_BIAS          the epilogue of the k-means assignment kernel (tmvb_kmeans.hip) omits b_c = -n_c / 2: the arg-max is that of the dot product alone,
+//                                   wrong wherever the centroids differ in norm; tests/test_kmeans_mutant_gpu.py
 #ifdef TMVB_MUTANT_FLDA_H_NO_GUARD
 #define TMVB_FLDA_H_GUARD(cond) true
 #else

@@ -1175,6 +1175,56 @@ function docsim(model::TopicModel; docs::AbstractUnitRange{<:Integer}=1:0, topn:
 			ms=(prep=info.ms_prep, scan=info.ms_scan, merge=info.ms_merge), splits=Int(info.splits))
 end
 
+# ---------------------------------------------------------------------------------------------- cluster documents in topic space
+# Which documents belong together: tmvb_topic_kmeans runs Lloyd's k-means on the topic proportions on the device -- fp32 features, the assignment
+# on the f32 MFMA with the arg-max in its epilogue, fixed-order fp64 sums for the centroids and the inertia, k-means++ seeding.
+
+"tmvb_kmeans_info_t (include/tmvb.h), field for field."
+mutable struct TmvbKMeansInfo
+	iters::Int32; stop::Int32; n_empty::Int32; kp::Int32
+	moved_last::Int64
+	ms_prep::Float32; ms_seed::Float32; ms_assign::Float32; ms_update::Float32
+	TmvbKMeansInfo() = new(0, 0, 0, 0, 0, 0f0, 0f0, 0f0, 0f0)
+end
+
+const KM_METRICS = Dict(:euclid => 0, :hellinger => 1, :cosine => 2)
+
+"""
+k-means of the documents of `model` in topic space into `k` clusters (on `theta`, K x M topic proportions, if given: e.g. those of what predict
+returned).  labels[d] is 1-based; centroids is K x k in feature space (sqrt of proportions for :hellinger, unit vectors for :cosine), profiles
+the centroids as topic proportions; init = nothing seeds with k-means++ (`seed`), a K x k matrix starts from those centroids; maxiter = 0
+only assigns.  stop: 0 maxiter, 1 no label moved, 2 tol.  seeds are 1-based document ids, 0 when the centroids were given.
+"""
+function kmeans(model::TopicModel, k::Integer; metric::Symbol=:hellinger, init=nothing, seed::Integer=0, maxiter::Integer=100, tol::Real=0.0,
+				theta=nothing, device::Integer=0)
+	haskey(KM_METRICS, metric)			|| throw(ArgumentError("metric must be :euclid, :hellinger or :cosine."))
+	x = Matrix{Float64}(theta === nothing ? topic_proportions(model) : theta)
+	K, M = size(x)
+	(1 <= k <= min(M, 1024))			|| throw(ArgumentError("k must be an integer in [1, min(M, 1024)]."))
+	(0 <= maxiter <= 10000)				|| throw(ArgumentError("maxiter must be an integer in [0, 10000]."))
+	c0 = init === nothing ? zeros(Float64, 0, 0) : Matrix{Float64}(init)
+	(init === nothing || size(c0) == (K, k))	|| throw(TopicModelError("init must be a K x k matrix of centroids."))
+	label = zeros(Int32, M); centroid = zeros(Float64, K, k); count = zeros(Int64, k); dist2 = zeros(Float32, M)
+	inertia = fill(NaN, maxiter + 1); seeds = zeros(Int32, k)
+	info = TmvbKMeansInfo()
+	ctx = tmvb_context(device)
+	GC.@preserve info x c0 label centroid count dist2 inertia seeds begin
+		rc = ccall((:tmvb_topic_kmeans, LIBTMVB), Cint,
+			(Ptr{Cvoid}, Int32, Int32, Int64, Ptr{Float64}, Int32, Ptr{Float64}, Int64, Int32, Float64, Ptr{Int32}, Ptr{Float64}, Ptr{Int64}, Ptr{Float32},
+			 Ptr{Float64}, Ptr{Int32}, Ptr{Cvoid}),
+			ctx, K, KM_METRICS[metric], M, x, k, init === nothing ? Ptr{Float64}(C_NULL) : pointer(c0), seed, maxiter, tol, label, centroid, count, dist2,
+			inertia, seeds, pointer_from_objref(info))
+		tmvb_destroy_context(ctx)
+		tmvb_check(rc)
+	end
+	c = metric == :hellinger ? centroid .^ 2 : centroid
+	d = Float64.(dist2)
+	distance = metric == :hellinger ? sqrt.(0.5 .* d) : metric == :euclid ? sqrt.(d) : 0.5 .* d
+	return (labels=Int.(label) .+ 1, centroids=centroid, profiles=c ./ sum(c, dims=1), counts=Int.(count), dist2=dist2, distance=distance,
+			inertia=inertia[1:info.iters + 1], iters=Int(info.iters), stop=Int(info.stop), n_empty=Int(info.n_empty), seeds=Int.(seeds) .+ 1,
+			ms=(prep=info.ms_prep, seed=info.ms_seed, assign=info.ms_assign, update=info.ms_update))
+end
+
 # ---------------------------------------------------------------------------------------------- search documents by words
 # Which documents are about these words: tmvb_topic_search scores every query -- sum_j c_j log(theta_d . beta'_{w_j}), the query likelihood of
 # LDA-based retrieval -- against every document of the model on the device (probabilities on the f32 MFMA, logarithm and sum in fp64) and keeps,
