@@ -691,6 +691,76 @@ int tmvb_topic_kmeans(tmvb_ctx* ctx, int32_t K, int32_t metric, int64_t M, const
                       int32_t max_iter, double tol, int32_t* label, double* centroid, int64_t* count, float* dist2, double* inertia,
                       int32_t* seeds, tmvb_kmeans_info_t* info);
 
+/* ============================== map documents in two dimensions: exact t-SNE over the topic kNN graph ==============================
+ * Two calls (the reference has no such function): tmvb_map_affinity turns the neighbour lists of tmvb_topic_neighbors into the symmetric input
+ * similarities P of t-SNE (van der Maaten & Hinton 2008), tmvb_map_layout runs the gradient descent with the EXACT repulsive term: all M^2 pairs,
+ * no Barnes-Hut tree, no FFT grid.  Every sum has one order fixed by the constants below, so equal inputs give equal bytes.
+ *
+ * ---- tmvb_map_affinity.  Inputs on the HOST: idx[M][n] (0-based), d2[M][n] (fp32 squared distances), count[M] -- what tmvb_topic_neighbors
+ * returns, with d2 = max(0, 2 - 2 score) for HELLINGER and COSINE features; only the first count[i] slots of row i are read.  perplexity u.
+ * Per point i with n_i = count[i], everything in fp64: delta_j = (double)d2_ij - min_j (double)d2_ij; for a trial beta, e_j = exp(-beta delta_j),
+ * S = sum_j e_j, T = sum_j delta_j e_j, H(beta) = log S + beta T / S.  S and T are xor-butterfly sums over the 64 lanes of a wave (offsets 32, 16,
+ * ... 1), slot j in lane j, empty lanes 0.  Search, a FIXED schedule of TMVB_MAP_BISECT steps without early exit: beta = 1, lo = 0, hi = inf; each
+ * step evaluates H(beta); H > log u: lo = beta, beta = (hi == inf ? 2 beta : (beta + hi) / 2); else: hi = beta, beta = (lo + beta) / 2.  beta_i =
+ * beta after the last step, p_{j|i} = e_j / S at beta_i.  Rows with n_i <= u (no beta reaches log u): beta_i = 0 and p = 1 / n_i; n_i = 0: an
+ * empty row.  Outputs: beta[M], p_cond[M][n] (0 past count), and the symmetrised matrix as CSR (formed on the host side of the library, a counting
+ * sort by column and a merge): row i holds every j that lists i or is listed by i, ascending, once; val = (float)((a + b) / (2.0 M)) with a =
+ * p_{j|i} (0 if i does not list j), b = p_{i|j} (0 likewise): fp64, rounded once.  The caller allocates row_ptr[M + 1], col[2 M n], val[2 M n];
+ * row_ptr[M] entries are used; Mc == M.  The conditional form, for placing new points on a finished map: row_ptr == col == val == NULL, the M >= 1
+ * rows are new points, their indices lie in [0, Mc) (the mapped points) and nothing is a self match; only beta and p_cond are returned.
+ * Errors, judged before the device is touched: M < 2 or >= 2^31, Mc != M (conditional form: M < 1, Mc outside [1, 2^31)), n outside [1,
+ * TMVB_NB_TOPN_MAX], 2 M n >= 2^31, u < 1 or not finite, a NULL argument (only some of row_ptr, col, val given included) -> TMVB_EINVAL;
+ * count[i] outside [0, n], an index outside [0, Mc), i among its own neighbours (symmetric form), an index twice in one row, a negative
+ * or non-finite distance -> TMVB_ESHAPE; then ctx == NULL without a visible device -> TMVB_ENODEVICE (there is no CPU path).
+ *
+ * ---- tmvb_map_layout.  P as the CSR above (row_ptr[0] = 0, columns strictly ascending in a row, no diagonal, values finite and >= 0; it need not
+ * come from tmvb_map_affinity).  State y, vel, gain: [M][2] fp32.  y0 / vel0 / gain0 are the state on entry (vel0 == NULL: 0; gain0 == NULL: 1;
+ * y0 == NULL, allowed only with iter0 == 0: y_ic = (float)(1e-4 (2 u - 1)) in fp64 with u = tmvb_u53(x[0], x[1]) of tmvb_rng(seed, i,
+ * TMVB_RNG_MAP, c, 0)); y / vel / gain are the state on return.  Iteration t = 0 .. iters - 1 has the global index T = iter0 + t; e =
+ * exaggeration and mu = momentum0 while T < exag_iters, else e = 1 and mu = momentum1.
+ * Repulsion, the O(M^2) kernel.  For point i the j's are cut into runs of TMVB_MAP_RUN consecutive indices.  Inside a run, fp32, sequentially
+ * ascending from z = rx = ry = 0:  dx = y_ix - y_jx; dy = y_iy - y_jy; d = fmaf(dy, dy, fmaf(dx, dx, 1.0f)); q = an fp32 reciprocal of d with
+ * error <= 1 ulp (v_rcp_f32: q is NOT pinned bit for bit); z += q; w = q q; rx = fmaf(w, dx, rx); ry = fmaf(w, dy, ry).  j = i is included
+ * (it adds exactly 1 to z and 0 to r).  The run sums are widened to fp64 and added ascending from 0 inside a segment of TMVB_MAP_SEG runs; the
+ * segment sums are added ascending from 0: zrow[i], rep[i][2].  Runs and segments depend on M alone, never on launch geometry (j_split = how many
+ * workgroups share the segments of one tile of points; 0 = the library's choice), and there are no floating-point atomics.
+ * Blocked sum of a column v[M]: blocks of TMVB_MAP_RUN rows, each added sequentially ascending from 0 in fp64, the block sums added sequentially
+ * ascending from 0.  Z = blocked(zrow) - (double)M.
+ * Attraction, fp64 from the fp32 y: edge number m of row i (m = 0 for its first CSR entry) goes to slot m mod 64; a slot adds its terms
+ * (p dx) / (1 + (dx dx + dy dy)), dx = (double)y_ix - (double)y_jx, sequentially ascending from 0; the 64 slots are added ascending from 0: att[i][2].
+ * Gradient: g_ic = (float)(4.0 * (e * att_ic - rep_ic / Z)), every operation rounded on its own (no fusing).
+ * Update, fp32, every operation rounded on its own: differ = (vel > 0 and g < 0) or (vel < 0 and g > 0); gain = differ ? gain + 0.2f : gain * 0.8f;
+ * gain = max(gain, min_gain); vel = mu * vel - (eta * gain) * g; y' = y + vel.  Recentre: m_c = (float)(blocked(y'_c) / (double)M); y = y' - m_c.
+ * |g|^2 = blocked((double)g_x (double)g_x + (double)g_y (double)g_y); the gradient norm is its square root.
+ * KL of a state y: Z(y) as above; row i: slots as in the attraction with terms p log((p Z) (1 + (dx dx + dy dy))), p > 0 only; KL = blocked(rows).
+ * It is evaluated on the state AFTER iteration t whenever check > 0 and (T + 1) mod check == 0, and on the returned state: kl[k], kl_iter[k] = the
+ * number of iterations behind that state (T + 1), info->n_kl entries, kl_cap >= iters / check + 2 (check == 0: 2).  The values stay on the device
+ * until the call returns.  min_grad_norm > 0: at those checked iterations the host reads the gradient norm of iteration t and stops (stop = 1) when
+ * it is below min_grad_norm; that is the only host read inside the loop.
+ * Splittable: (iter0 = 0, iters = a) followed by (iter0 = a, iters = b) on the returned state gives the bytes of (iter0 = 0, iters = a + b).
+ * Optional outputs (or NULL), the pieces of the LAST gradient evaluation (zeros with iters = 0): rep[M][2], zrow[M], att[M][2] (fp64), grad[M][2]
+ * (fp32).  info (or NULL): iters done, stop (0 iters, 1 min_grad_norm), n_kl, j_split used, Z and grad_norm of the last gradient evaluation,
+ * ms_rep / ms_att / ms_upd = device time of all repulsion (with Z), attraction and update (with recentring) kernels of the iterations.
+ * Error model of the repulsion, per row and first order, in units of 2^-24 relative: dx <= 1, d <= 4, q <= 6, w <= 13, w dx <= 14, and a run of
+ * TMVB_MAP_RUN sequential fp32 adds <= (TMVB_MAP_RUN - 1) of sum |terms|:  |rep - rep64| <= (TMVB_MAP_RUN + 24) 2^-24 sum_j |w dx|,  |zrow - z64| <=
+ * (TMVB_MAP_RUN + 8) 2^-24 sum_j q.
+ * Errors, judged before the device is touched: M < 2 or >= 2^31, iters outside [0, 100000], iter0 < 0, exag_iters < 0, check < 0, j_split < 0,
+ * exaggeration < 1, eta <= 0, momentum outside [0, 1), min_gain <= 0, min_grad_norm < 0, any of them not finite, kl_cap too small, y0 == NULL with
+ * iter0 != 0, a NULL required argument -> TMVB_EINVAL; a CSR that breaks the rules above or a non-finite state -> TMVB_ESHAPE; then ctx == NULL
+ * without a visible device -> TMVB_ENODEVICE (there is no CPU path).  A returned state that is not finite -> TMVB_ENONFINITE. */
+#define TMVB_MAP_BISECT 64
+#define TMVB_MAP_RUN   256                                  /* consecutive j per fp32 partial sum; rows per block of a blocked sum */
+#define TMVB_MAP_SEG    64                                  /* runs per fp64 segment sum */
+#define TMVB_MAP_SLOTS  64                                  /* slots of a row's edge sums */
+typedef struct { int32_t iters, iter0, exag_iters, check, j_split, reserved; int64_t seed; double exaggeration, min_grad_norm;
+                 float momentum0, momentum1, eta, min_gain; } tmvb_map_params_t;
+typedef struct { int32_t iters, stop, n_kl, j_split; double Z, grad_norm; float ms_rep, ms_att, ms_upd, reserved; } tmvb_map_info_t;
+int tmvb_map_affinity(tmvb_ctx* ctx, int64_t M, int64_t Mc, int32_t n, const int32_t* idx, const float* d2, const int32_t* count, double perplexity,
+                      double* beta, double* p_cond, int64_t* row_ptr, int32_t* col, float* val);
+int tmvb_map_layout(tmvb_ctx* ctx, int64_t M, const int64_t* row_ptr, const int32_t* col, const float* val, const tmvb_map_params_t* params,
+                    const float* y0, const float* vel0, const float* gain0, float* y, float* vel, float* gain, int32_t kl_cap, double* kl,
+                    int32_t* kl_iter, double* rep, double* zrow, double* att, float* grad, tmvb_map_info_t* info);
+
 /* ============================== search documents by words: query likelihood with fused top-n ==============================
  * Which documents are about these words (the reference has no such function): the query likelihood of LDA-based retrieval (Wei & Croft
  * 2006) = the held-out log-likelihood of tmvb_heldout_loglik with the roles turned round -- one short "held-out document", every training

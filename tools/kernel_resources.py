@@ -51,6 +51,8 @@ BENCHED = {
     # clustering in topic space (tools/cluster_bench.py): features and norms, the fused MFMA assignment, the fixed-order update, the k-means++ rounds
     "km_feature_kernel": 0, "km_norm_kernel": 0, "km_assign_kernel": 0, "km_run_sum_kernel": 0, "km_finalize_kernel": 0, "km_seed_dist_kernel": 0,
     "km_seed_pick_kernel": 0,
+    # document map (tools/docmap_bench.py): the entropy search, the all-pairs repulsion and its segment sums, the edge sums (forces and KL), the update
+    "map_affinity_kernel": 0, "map_repulse_kernel": 0, "map_finish_kernel": 0, "map_attract_kernel<": 0, "map_update_kernel": 0,
     # stochastic LDA training (tools/svi_bench.py): the fused global update -- blend + partial row sums, then normalise
     "svi_blend_kernel<": 0, "svi_norm_kernel": 0,
     # stochastic CTM training (tools/ctm_svi_bench.py): the tail of the fused global update -- recentre in fp64, blend (the K x V part is the two above)

@@ -19,6 +19,7 @@ from .heldout import HeldoutResult, heldout_loglik, heldout_loglik_raw, perplexi
 from .coherence import CoherenceResult, coherence, coherence_from_counts, coherence_from_counts_raw, codocfreq_raw
 from .neighbors import NeighborsResult, docsim, neighbors_raw, topic_proportions
 from .cluster import ClusterResult, cluster_docs, kmeans_raw
+from .docmap import DocMap, map_affinity_raw, map_docs, map_layout_raw
 from .search import SearchInfo, SearchResult, pack_queries, search, search_raw
 from .token_topics import TokenTopics, phi, token_factors, token_topics, token_topics_raw
 from .recs_eval import (HeldReaders, RecEvalResult, rank_metrics, rank_metrics_raw, rec_eval, rec_quality, rec_ranks_raw, split_readers,
@@ -38,6 +39,7 @@ __all__ = ["CorpusError", "DocumentError", "EngineError", "TopicModelError", "bu
            "CoherenceResult", "coherence", "coherence_from_counts", "coherence_from_counts_raw", "codocfreq_raw",
            "NeighborsResult", "docsim", "neighbors_raw", "topic_proportions",
            "ClusterResult", "cluster_docs", "kmeans_raw",
+           "DocMap", "map_affinity_raw", "map_docs", "map_layout_raw",
            "SearchInfo", "SearchResult", "pack_queries", "search", "search_raw",
            "TokenTopics", "phi", "token_factors", "token_topics", "token_topics_raw",
            "HeldReaders", "RecEvalResult", "rank_metrics", "rank_metrics_raw", "rec_eval", "rec_quality", "rec_ranks_raw", "split_readers", "split_readers_raw",

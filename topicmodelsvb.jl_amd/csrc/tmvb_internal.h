@@ -218,6 +218,8 @@ int tmvb_check_ctx_or_device(const char* fn, tmvb_ctx* ctx);
 //                                   exact tie of the r bits; only entries whose tied topics sit in different lanes show it; tests/test_token_topics_mutant_gpu.py
 //   TMVB_MUTANT_KM_NO_BIAS          the epilogue of the k-means assignment kernel (tmvb_kmeans.hip) omits b_c = -n_c / 2: the arg-max is that of the dot product alone,
 //                                   wrong wherever the centroids differ in norm; tests/test_kmeans_mutant_gpu.py
+//   TMVB_MUTANT_MAP_Z_SELF          the normaliser of the document map (tmvb_docmap.hip) keeps the M self terms: Z = blocked(zrow) without - M, so the gradient's
+//                                   repulsive half is too small; tests/test_docmap_mutant_gpu.py
 #ifdef TMVB_MUTANT_FLDA_H_NO_GUARD
 #define TMVB_FLDA_H_GUARD(cond) true
 #else

@@ -34,9 +34,10 @@ TMVB_HD inline tmvb_philox4 tmvb_philox4x32_10_raw(uint32_t c0, uint32_t c1, uin
 // TMVB_RNG_SPLIT is the held-out token split (tmvb_heldout.hip): draw index = Philox block of a document's token occurrences.
 // TMVB_RNG_RSPLIT_ENTRY / _DOCUMENT are the split of the reader lists (tmvb_recranks.hip): draw index = Philox block of a document's reader entries / 0.
 enum : uint32_t { TMVB_RNG_POISSON = 0, TMVB_RNG_GAMMA = 1, TMVB_RNG_BOOST = 2, TMVB_RNG_NORMAL = 3, TMVB_RNG_TOKEN = 4, TMVB_RNG_SPLIT = 5,
-                  TMVB_RNG_RSPLIT_ENTRY = 6, TMVB_RNG_RSPLIT_DOCUMENT = 7, TMVB_RNG_KMEANS = 8 };
+                  TMVB_RNG_RSPLIT_ENTRY = 6, TMVB_RNG_RSPLIT_DOCUMENT = 7, TMVB_RNG_KMEANS = 8, TMVB_RNG_MAP = 9 };
 
 // TMVB_RNG_KMEANS is the k-means++ seeding (tmvb_kmeans.hip): "document" = the seeding round j, draw index 0.
+// TMVB_RNG_MAP is the random start of the document map (tmvb_docmap.hip): "document" = the point i, "topic" = the coordinate c, draw index 0.
 // random bits of (seed, global document index, stage [, topic], draw index)
 TMVB_HD inline tmvb_philox4 tmvb_rng(uint64_t seed, uint64_t doc, uint32_t stage, uint32_t topic, uint32_t draw)
 {

@@ -1225,6 +1225,82 @@ function kmeans(model::TopicModel, k::Integer; metric::Symbol=:hellinger, init=n
 			ms=(prep=info.ms_prep, seed=info.ms_seed, assign=info.ms_assign, update=info.ms_update))
 end
 
+# ---------------------------------------------------------------------------------------------- map documents in two dimensions
+# Where the documents lie: tmvb_map_affinity turns the neighbour lists of tmvb_topic_neighbors into t-SNE's input similarities (entropy search in
+# fp64 on a fixed schedule, symmetrised CSR), tmvb_map_layout runs the gradient descent with the repulsive term over ALL pairs in a fixed order --
+# no Barnes-Hut tree, no FFT grid --, so equal inputs give equal bytes.
+
+"tmvb_map_params_t (include/tmvb.h), field for field."
+mutable struct TmvbMapParams
+	iters::Int32; iter0::Int32; exag_iters::Int32; check::Int32; j_split::Int32; reserved::Int32
+	seed::Int64
+	exaggeration::Float64; min_grad_norm::Float64
+	momentum0::Float32; momentum1::Float32; eta::Float32; min_gain::Float32
+end
+
+"tmvb_map_info_t (include/tmvb.h), field for field."
+mutable struct TmvbMapInfo
+	iters::Int32; stop::Int32; n_kl::Int32; j_split::Int32
+	Z::Float64; grad_norm::Float64
+	ms_rep::Float32; ms_att::Float32; ms_upd::Float32; reserved::Float32
+	TmvbMapInfo() = new(0, 0, 0, 0, 0.0, 0.0, 0f0, 0f0, 0f0, 0f0)
+end
+
+"""
+A 2-D map of the documents of `model` (or of `theta`, K x M topic proportions): t-SNE on the `n_neighbors` nearest documents of each document under
+`metric` (:hellinger or :cosine), the repulsion computed exactly over all pairs.  n_neighbors defaults to min(64, M - 1), perplexity to
+min(20, n_neighbors / 3).  init = nothing starts from the seeded random state on the device, an M x 2 matrix from that state.  Returns xy (M x 2),
+kl and kl_iters (the KL divergence after that many iterations; every `check` iterations and at the end), beta (the precisions of the entropy
+search) and the device times.
+"""
+function map_docs(model::TopicModel; perplexity=nothing, metric::Symbol=:hellinger, n_neighbors=nothing, iters::Integer=750, init=nothing, seed::Integer=0,
+				theta=nothing, check::Integer=50, eta=nothing, exaggeration::Real=12.0, exag_iters::Integer=250, device::Integer=0)
+	(metric == :hellinger || metric == :cosine)	|| throw(ArgumentError("metric must be :hellinger or :cosine."))
+	x = Matrix{Float64}(theta === nothing ? topic_proportions(model) : theta)
+	K, M = size(x)
+	(M >= 3)							|| throw(TopicModelError("a map needs at least 3 documents."))
+	n = n_neighbors === nothing ? min(64, M - 1) : Int(n_neighbors)
+	(2 <= n <= min(64, M - 1))			|| throw(ArgumentError("n_neighbors must be an integer in [2, min(64, M - 1)]."))
+	u = perplexity === nothing ? min(20.0, n / 3) : Float64(perplexity)
+	(1.0 <= u < n)						|| throw(ArgumentError("perplexity must lie in [1, n_neighbors)."))
+	(0 <= iters <= 100000 && check >= 0)	|| throw(ArgumentError("iters must lie in [0, 100000] and check must not be negative."))
+	y0 = init === nothing ? zeros(Float32, 0, 0) : Matrix{Float32}(permutedims(Matrix{Float32}(init)))		# 2 x M column-major = C's [M][2]
+	(init === nothing || size(y0) == (2, M))	|| throw(TopicModelError("init must be an M x 2 matrix."))
+	idx = zeros(Int32, n, M); score = zeros(Float32, n, M); count = zeros(Int32, M)		# column-major (j, q) = C's [q][j]
+	beta = zeros(Float64, M); pcond = zeros(Float64, n, M)
+	row_ptr = zeros(Int64, M + 1); col = zeros(Int32, 2 * M * n); val = zeros(Float32, 2 * M * n)
+	y = zeros(Float32, 2, M); vel = zeros(Float32, 2, M); gain = zeros(Float32, 2, M)
+	cap = (check > 0 ? div(iters, check) : 0) + 2
+	kl = zeros(Float64, cap); kl_iter = zeros(Int32, cap)
+	params = TmvbMapParams(iters, 0, exag_iters, check, 0, 0, seed, exaggeration, 0.0, 0.5f0, 0.8f0,
+						Float32(eta === nothing ? max(M / exaggeration / 4, 50.0) : eta), 0.01f0)
+	info = TmvbMapInfo()
+	ctx = tmvb_context(device)
+	GC.@preserve x idx score count beta pcond row_ptr col val y0 y vel gain kl kl_iter params info begin
+		rc = ccall((:tmvb_topic_neighbors, LIBTMVB), Cint,
+			(Ptr{Cvoid}, Int32, Int32, Int64, Ptr{Float64}, Int64, Ptr{Float64}, Int64, Int32, Int32, Ptr{Int32}, Ptr{Float32}, Ptr{Int32}, Ptr{Cvoid}),
+			ctx, K, NB_METRICS[metric], M, x, M, Ptr{Float64}(C_NULL), 0, n, 0, idx, score, count, C_NULL)
+		rc == 0 || tmvb_destroy_context(ctx)
+		tmvb_check(rc)
+		d2 = map(s -> isfinite(s) ? max(0f0, 2f0 - 2f0 * s) : 0f0, score)
+		idx .= max.(idx, Int32(0))
+		rc = ccall((:tmvb_map_affinity, LIBTMVB), Cint,
+			(Ptr{Cvoid}, Int64, Int64, Int32, Ptr{Int32}, Ptr{Float32}, Ptr{Int32}, Float64, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Int32}, Ptr{Float32}),
+			ctx, M, M, n, idx, d2, count, u, beta, pcond, row_ptr, col, val)
+		rc == 0 || tmvb_destroy_context(ctx)
+		tmvb_check(rc)
+		rc = ccall((:tmvb_map_layout, LIBTMVB), Cint,
+			(Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Int32}, Ptr{Float32}, Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32},
+			 Int32, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float32}, Ptr{Cvoid}),
+			ctx, M, row_ptr, col, val, pointer_from_objref(params), init === nothing ? Ptr{Float32}(C_NULL) : pointer(y0), Ptr{Float32}(C_NULL), Ptr{Float32}(C_NULL),
+			y, vel, gain, cap, kl, kl_iter, Ptr{Float64}(C_NULL), Ptr{Float64}(C_NULL), Ptr{Float64}(C_NULL), Ptr{Float32}(C_NULL), pointer_from_objref(info))
+		tmvb_destroy_context(ctx)
+		tmvb_check(rc)
+	end
+	return (xy=permutedims(y), kl=kl[1:info.n_kl], kl_iters=Int.(kl_iter[1:info.n_kl]), beta=beta, iters=Int(info.iters), stop=Int(info.stop),
+			ms=(repulsion=info.ms_rep, attraction=info.ms_att, update=info.ms_upd))
+end
+
 # ---------------------------------------------------------------------------------------------- search documents by words
 # Which documents are about these words: tmvb_topic_search scores every query -- sum_j c_j log(theta_d . beta'_{w_j}), the query likelihood of
 # LDA-based retrieval -- against every document of the model on the device (probabilities on the f32 MFMA, logarithm and sum in fp64) and keeps,
