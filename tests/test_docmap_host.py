@@ -252,7 +252,7 @@ def test_errors_that_only_the_abi_can_say(tmvb):
     assert rc == EINVAL and "M = 0" in err
 
     P = tmvb.docmap.MapParams(4, 0, 250, 2, 0, 0, 0, 12.0, 0.0, 0.5, 0.8, 50.0, 0.01)
-    b = [i64.ctypes.data_as(P64), i32.ctypes.data_as(P32), f32.ctypes.data_as(PF), C.cast(C.pointer(P), C.c_void_p), f32.ctypes.data_as(PF), f32.ctypes.data_as(PF),
+    b = [i64.ctypes.data_as(P64), i32.ctypes.data_as(P32), f32.ctypes.data_as(PF), C.pointer(P), f32.ctypes.data_as(PF), f32.ctypes.data_as(PF),
          f32.ctypes.data_as(PF), f64.ctypes.data_as(PD), i32.ctypes.data_as(P32)]
 
     def lay(M, p=b, cap=8):

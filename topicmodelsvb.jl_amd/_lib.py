@@ -14,6 +14,9 @@ import sys
 
 import numpy as np
 
+from . import _abi
+from ._abi import CorpusInfo, FoldinInfo, RecTopNInfo, SearchInfo, TokenTopicsInfo, P_dbl, P_f32, P_i32, P_i64, VP  # noqa: F401 (re-exported)
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
 LIB_PATH = os.path.join(_HERE, "libtmvb_hip.so")
@@ -39,33 +42,6 @@ class DocumentError(Exception):
 
 class EngineError(RuntimeError):
     """HIP runtime / device failure inside libtmvb_hip.so"""
-
-
-class CorpusInfo(C.Structure):
-    _fields_ = [(n, C.c_int64) for n in ("M", "V", "U", "nnz", "nR", "sum_counts", "sum_ratings", "max_doc_len",
-                                         "max_readers", "n_empty_docs", "n_docs_with_duplicate_terms",
-                                         "n_docs_with_duplicate_readers")]
-
-
-class RecTopNInfo(C.Structure):
-    """tmvb_rectopn_info_t"""
-    _fields_ = [("splits", C.c_int32), ("kp", C.c_int32), ("ms_prep", C.c_float), ("ms_scan", C.c_float), ("ms_merge", C.c_float)]
-
-
-class SearchInfo(C.Structure):
-    """tmvb_search_info_t"""
-    _fields_ = [("splits", C.c_int32), ("kp", C.c_int32), ("col_tiles", C.c_int32), ("ms_prep", C.c_float), ("ms_scan", C.c_float), ("ms_merge", C.c_float)]
-
-
-class TokenTopicsInfo(C.Structure):
-    """tmvb_token_topics_info_t"""
-    _fields_ = [("nsel", C.c_int64), ("n_short", C.c_int64), ("n_long", C.c_int64), ("chunks", C.c_int32), ("lanes_per_entry", C.c_int32),
-                ("ms_kernel", C.c_float)]
-
-
-class FoldinInfo(C.Structure):
-    """tmvb_foldin_info_t"""
-    _fields_ = [("kp", C.c_int32), ("capacity", C.c_int32), ("n_reg", C.c_int64), ("n_long", C.c_int64), ("ms_prep", C.c_float), ("ms_sweeps", C.c_float)]
 
 
 def _sources():
@@ -185,13 +161,6 @@ def _kernel_resource_check(kres: str, verbose: bool = False) -> str:
 
 _lib = None
 
-P_i64 = C.POINTER(C.c_int64)
-P_i32 = C.POINTER(C.c_int32)
-P_dbl = C.POINTER(C.c_double)
-P_f32 = C.POINTER(C.c_float)
-VP = C.c_void_p
-
-
 # ---- argument and result plumbing of the entry points that work without a model handle (heldout, gencorp, coherence, neighbors)
 def _handle(ctx):
     """the tmvb_ctx* of a DeviceContext; None: a NULL context"""
@@ -232,33 +201,7 @@ def lib():
             if not os.path.exists(path):
                 raise EngineError(f"TMVB_LIB_VARIANT={_VARIANT}: {path} is missing (tools/build_variant.sh)")
         L = C.CDLL(path)
-        L.tmvb_last_error.restype = C.c_char_p
-        L.tmvb_abi_version.restype = C.c_int
-        L.tmvb_device_count.restype = C.c_int
-        L.tmvb_score_topn.restype = C.c_int
-        L.tmvb_score_topn.argtypes = [VP, C.c_int32, C.c_int64, P_dbl, C.c_int64, P_dbl, P_i64, P_i32, C.c_int32, C.c_int32, P_i32, P_f32, P_i32,
-                                      C.POINTER(RecTopNInfo)]
-        L.tmvb_ctpf_foldin_users.restype = C.c_int
-        L.tmvb_ctpf_foldin_users.argtypes = [VP, C.c_int32, C.c_int64, P_dbl, P_dbl, P_dbl, P_dbl, P_dbl, C.c_double, C.c_int64, P_i64, P_i32, P_i32, P_dbl,
-                                             C.c_int32, C.c_double, P_dbl, P_i32, C.POINTER(FoldinInfo)]
-        L.tmvb_ctpf_foldin_users_on.restype = C.c_int
-        L.tmvb_ctpf_foldin_users_on.argtypes = [VP, C.c_int64, P_i64, P_i32, P_i32, P_dbl, C.c_int32, C.c_double, P_dbl, P_i32, C.POINTER(FoldinInfo)]
-        L.tmvb_topic_search.restype = C.c_int
-        L.tmvb_topic_search.argtypes = [VP, C.c_int32, C.c_int64, C.c_int64, P_dbl, P_dbl, C.c_double, C.c_int64, P_i64, P_i32, P_i32, C.c_int32, C.c_int32,
-                                        P_i32, P_f32, P_i32, C.POINTER(SearchInfo)]
-        L.tmvb_token_topics.restype = C.c_int
-        L.tmvb_token_topics.argtypes = [VP, C.c_int32, C.c_int64, C.c_int64, P_dbl, P_dbl, P_i64, P_i32, P_i32, P_i32, C.c_int64, C.c_double, C.c_int32,
-                                        C.c_int64, P_i32, P_f32, P_f32, P_i64, C.POINTER(TokenTopicsInfo)]
-        L.tmvb_topic_kmeans.restype = C.c_int
-        L.tmvb_topic_kmeans.argtypes = [VP, C.c_int32, C.c_int32, C.c_int64, P_dbl, C.c_int32, P_dbl, C.c_int64, C.c_int32, C.c_double, P_i32, P_dbl, P_i64, P_f32,
-                                        P_dbl, P_i32, VP]
-        L.tmvb_map_affinity.restype = C.c_int
-        L.tmvb_map_affinity.argtypes = [VP, C.c_int64, C.c_int64, C.c_int32, P_i32, P_f32, P_i32, C.c_double, P_dbl, P_dbl, P_i64, P_i32, P_f32]
-        L.tmvb_map_layout.restype = C.c_int
-        L.tmvb_map_layout.argtypes = [VP, C.c_int64, P_i64, P_i32, P_f32, VP, P_f32, P_f32, P_f32, P_f32, P_f32, P_f32, C.c_int32, P_dbl, P_i32, P_dbl, P_dbl,
-                                      P_dbl, P_f32, VP]
-        L.tmvb_digamma_f64.restype = C.c_int
-        L.tmvb_digamma_f64.argtypes = [P_dbl, P_dbl, C.c_int64]
+        _abi.apply(L)                  # the one place prototypes are declared: _abi.py holds a line per function of include/tmvb.h
         _lib = L
     return _lib
 

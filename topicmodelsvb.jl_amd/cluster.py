@@ -13,6 +13,7 @@ import ctypes as ct
 
 import numpy as np
 
+from ._abi import KMeansInfo  # noqa: F401 (re-exported)
 from ._lib import CorpusError, TopicModelError, _handle, check, lib, P_dbl, P_f32, P_i32, P_i64
 from .lda import call_context
 from .neighbors import topic_proportions
@@ -22,12 +23,6 @@ METRICS = {"euclid": EUCLID, "hellinger": HELLINGER, "cosine": COSINE}
 CMAX = 1024                             # TMVB_KM_CMAX
 RUN = 256                               # TMVB_KM_RUN: members / documents per fixed-order partial sum
 STOPS = {0: "max_iter", 1: "converged", 2: "tol"}
-
-
-class KMeansInfo(ct.Structure):
-    """tmvb_kmeans_info_t"""
-    _fields_ = [("iters", ct.c_int32), ("stop", ct.c_int32), ("n_empty", ct.c_int32), ("kp", ct.c_int32), ("moved_last", ct.c_int64),
-                ("ms_prep", ct.c_float), ("ms_seed", ct.c_float), ("ms_assign", ct.c_float), ("ms_update", ct.c_float)]
 
 
 def kmeans_raw(ctx, K, metric, x, C, init=None, seed=0, max_iter=100, tol=0.0):
@@ -52,8 +47,8 @@ def kmeans_raw(ctx, K, metric, x, C, init=None, seed=0, max_iter=100, tol=0.0):
     inertia = np.full(min(it, 10000) + 1, np.nan)
     seeds = np.zeros(nc, dtype=np.int32)
     info = KMeansInfo()
-    rc = L.tmvb_topic_kmeans(_handle(ctx), ct.c_int32(int(K)), ct.c_int32(int(metric)), ct.c_int64(M), x.ctypes.data_as(P_dbl), ct.c_int32(int(C)), i_ptr,
-                             ct.c_int64(int(seed)), ct.c_int32(int(max_iter)), ct.c_double(float(tol)), label.ctypes.data_as(P_i32), centroid.ctypes.data_as(P_dbl),
+    rc = L.tmvb_topic_kmeans(_handle(ctx), int(K), int(metric), M, x.ctypes.data_as(P_dbl), int(C), i_ptr,
+                             int(seed), int(max_iter), float(tol), label.ctypes.data_as(P_i32), centroid.ctypes.data_as(P_dbl),
                              count.ctypes.data_as(P_i64), dist2.ctypes.data_as(P_f32), inertia.ctypes.data_as(P_dbl), seeds.ctypes.data_as(P_i32), ct.byref(info))
     if rc != 0:
         return rc, L.tmvb_last_error().decode("utf-8", "replace")

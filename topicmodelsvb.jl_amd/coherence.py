@@ -17,16 +17,12 @@ import ctypes as C
 
 import numpy as np
 
+from ._abi import CodfInfo  # noqa: F401 (re-exported)
 from ._lib import CorpusError, _csr, _handle, check, lib, P_dbl, P_i32, P_i64
 from .lda import _packed, call_context
 
 CODF_CHUNK_DOCS = 4096              # TMVB_CODF_CHUNK_DOCS (include/tmvb.h): documents per workgroup of the pair pass
 TOPN_MIN, TOPN_MAX = 2, 64
-
-
-class CodfInfo(C.Structure):
-    """tmvb_codf_info_t"""
-    _fields_ = [("n_slots", C.c_int64), ("n_batches", C.c_int32), ("ms_bitset", C.c_float), ("ms_pairs", C.c_float)]
 
 
 class CoherenceResult:
@@ -74,8 +70,8 @@ def codocfreq_raw(ctx, M, V, doc_ptr, terms, counts, top, max_bitset_bytes=0):
     K, N = top.shape
     codf = np.zeros((max(K, 1), max(N, 1), max(N, 1)), dtype=np.int64)
     info = CodfInfo()
-    rc = L.tmvb_corpus_codocfreq(_handle(ctx), C.c_int64(int(M)), C.c_int64(int(V)), doc_ptr.ctypes.data_as(P_i64), terms.ctypes.data_as(P_i32),
-                                 counts.ctypes.data_as(P_i32), C.c_int32(K), C.c_int32(N), top.ctypes.data_as(P_i32), C.c_int64(int(max_bitset_bytes)),
+    rc = L.tmvb_corpus_codocfreq(_handle(ctx), int(M), int(V), doc_ptr.ctypes.data_as(P_i64), terms.ctypes.data_as(P_i32),
+                                 counts.ctypes.data_as(P_i32), K, N, top.ctypes.data_as(P_i32), int(max_bitset_bytes),
                                  codf.ctypes.data_as(P_i64), C.byref(info))
     if rc != 0:
         return rc, L.tmvb_last_error().decode("utf-8", "replace")
@@ -90,7 +86,7 @@ def coherence_from_counts_raw(K, N, M, codf):
     codf = np.ascontiguousarray(codf, dtype=np.int64)
     n = max(int(K), 1)
     umass, npmi, undef = np.zeros(n), np.zeros(n), np.zeros(n, dtype=np.int32)
-    rc = L.tmvb_coherence_from_counts(C.c_int32(int(K)), C.c_int32(int(N)), C.c_int64(int(M)), codf.ctypes.data_as(P_i64), umass.ctypes.data_as(P_dbl),
+    rc = L.tmvb_coherence_from_counts(int(K), int(N), int(M), codf.ctypes.data_as(P_i64), umass.ctypes.data_as(P_dbl),
                                       npmi.ctypes.data_as(P_dbl), undef.ctypes.data_as(P_i32))
     if rc != 0:
         return rc, L.tmvb_last_error().decode("utf-8", "replace")

@@ -16,11 +16,11 @@ import ctypes as C
 
 import numpy as np
 
+from ._abi import HOST_ALLREDUCE_FN as _HOST_FN
 from ._lib import check, lib, VP
 
 UNIQUE_ID_BYTES = 128
 F32, F64 = 0, 1
-_HOST_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32)
 
 
 class Communicator:
@@ -38,7 +38,7 @@ class Communicator:
         if len(unique_id) != UNIQUE_ID_BYTES:
             raise ValueError(f"unique id must be {UNIQUE_ID_BYTES} bytes.")
         h = VP()
-        check(lib().tmvb_comm_create_rccl(ctx.handle, C.c_char_p(unique_id), C.c_int32(nranks), C.c_int32(rank), C.byref(h)))
+        check(lib().tmvb_comm_create_rccl(ctx.handle, C.c_char_p(unique_id), nranks, rank, C.byref(h)))
         return cls(h, ctx)
 
     @classmethod
@@ -46,7 +46,7 @@ class Communicator:
         n = len(ctxs)
         arr = (VP * n)(*[c.handle for c in ctxs])
         out = (VP * n)()
-        check(lib().tmvb_comm_create_rccl_all(arr, C.c_int32(n), out))
+        check(lib().tmvb_comm_create_rccl_all(arr, n, out))
         return [cls(VP(out[i]), ctxs[i]) for i in range(n)]
 
     @classmethod
@@ -64,7 +64,7 @@ class Communicator:
                 return 1
         cb = _HOST_FN(tramp)
         h = VP()
-        check(lib().tmvb_comm_create_host(ctx.handle, C.c_int32(nranks), C.c_int32(rank), cb, None, C.byref(h)))
+        check(lib().tmvb_comm_create_host(ctx.handle, nranks, rank, cb, None, C.byref(h)))
         return cls(h, ctx, keep=cb)
 
     _boot_count = 0
@@ -90,7 +90,7 @@ class Communicator:
         return {"nranks": n.value, "rank": r.value, "backend": "rccl" if b.value == 0 else "host"}
 
     def allreduce(self, dev_ptr: int, count: int, dtype: int = F32):
-        check(lib().tmvb_comm_allreduce(self.handle, VP(dev_ptr), C.c_int64(count), C.c_int32(dtype)))
+        check(lib().tmvb_comm_allreduce(self.handle, VP(dev_ptr), count, dtype))
 
     def close(self):
         if self.handle:
@@ -105,6 +105,4 @@ class Communicator:
 
 
 def rccl_version() -> int:
-    L = lib()
-    L.tmvb_rccl_version.restype = C.c_int
-    return int(L.tmvb_rccl_version())
+    return int(lib().tmvb_rccl_version())

@@ -14,13 +14,15 @@ Host-side mirror of the reference's CTM / gpuCTM interface above the C ABI.
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import math
 
 import numpy as np
 
-from ._lib import TopicModelError, check, lib, P_dbl, P_i64, VP
+from ._lib import CorpusError, TopicModelError, P_i64
+from ._model import DeviceModel, EstepTimer, PackedStats, _op
 from .corpus import dirichlet_rows
-from .lda import DeviceContext, DeviceCorpus, _F, _packed, _pd, _print_delbo, _topic_orders, _validate_train_args
+from .lda import _packed
 
 
 class CTM:
@@ -76,146 +78,45 @@ def check_model_ctm(model, rtol: float = 1.5e-8):
         raise TopicModelError("elbo must be finite.")
 
 
-class gpuCTM:
+class gpuCTM(PackedStats, EstepTimer, DeviceModel):
     """GPU accelerated correlated topic model (src/gpuCTM.jl:6-99) on libtmvb_hip.so."""
 
-    _FIELDS = ("corp", "K", "M", "V", "N", "C", "topics", "mu", "sigma", "invsigma", "beta", "beta_old", "lam", "lam_old",
-               "vsq", "logzeta", "elbo")
-
-    def __init__(self, corp, K: int, seed: int = 7, ctx: DeviceContext | None = None, device_id: int = 0, stream=None,
-                 _from: CTM | None = None):
-        host = _from if _from is not None else CTM(corp, K, seed)
-        for k in self._FIELDS:
-            setattr(self, k, getattr(host, k))
-        self.ctx = ctx or DeviceContext(device_id, stream)
-        self.dcorp = DeviceCorpus(self.ctx, self.corp)
-        self.handle = VP()
-        check(lib().tmvb_ctm_create(self.ctx.handle, self.dcorp.handle, C.c_int32(self.K), C.byref(self.handle)))
-        self.M_total = self.M
-        self.update_buffer()
-
-    def update_buffer(self):
-        K, M, V = self.K, self.M, self.V
-        mu = np.ascontiguousarray(self.mu, dtype=np.float64)
-        elbo = C.c_double(float(self.elbo))
-        lz = np.ascontiguousarray(self.logzeta, dtype=np.float64)
-        check(lib().tmvb_ctm_set_state(self.handle, _pd(mu), _pd(_F(self.sigma, (K, K))), _pd(_F(self.invsigma, (K, K))),
-                                       _pd(_F(self.beta, (K, V))), _pd(_F(self.beta_old, (K, V))), _pd(_F(self.lam, (K, M))),
-                                       _pd(_F(self.lam_old, (K, M))), _pd(_F(self.vsq, (K, M))), _pd(lz), C.byref(elbo)))
-
-    def update_host(self):
-        K, M, V = self.K, self.M, self.V
-        self.mu = np.empty(K)
-        self.sigma = np.empty((K, K), order="F"); self.invsigma = np.empty((K, K), order="F")
-        self.beta = np.empty((K, V), order="F"); self.beta_old = np.empty((K, V), order="F")
-        self.lam = np.empty((K, M), order="F"); self.lam_old = np.empty((K, M), order="F")
-        self.vsq = np.empty((K, M), order="F"); self.logzeta = np.empty(M)
-        elbo = C.c_double(0.0)
-        check(lib().tmvb_ctm_get_state(self.handle, _pd(self.mu), _pd(self.sigma), _pd(self.invsigma), _pd(self.beta),
-                                       _pd(self.beta_old), _pd(self.lam), _pd(self.lam_old), _pd(self.vsq), _pd(self.logzeta),
-                                       C.byref(elbo)))
-        self.elbo = elbo.value
+    _ABI, _HOST, _check = "ctm", CTM, staticmethod(functools.partial(check_model_ctm, rtol=3.5e-4))
+    _STATE = (("mu", "K"), ("sigma", "KK"), ("invsigma", "KK"), ("beta", "KV"), ("beta_old", "KV"), ("lam", "KM"), ("lam_old", "KM"),
+              ("vsq", "KM"), ("logzeta", "M"))
 
     def estep(self, niter: int = 1000, ntol: float | None = None, viter: int = 10, vtol: float | None = None):
-        ntol = 1.0 / self.K ** 2 if ntol is None else ntol
-        vtol = 1.0 / self.K ** 2 if vtol is None else vtol
-        check(lib().tmvb_ctm_estep(self.handle, C.c_int32(niter), C.c_double(ntol), C.c_int32(viter), C.c_double(vtol)))
+        self._call("estep", niter, self._default_tol(ntol), viter, self._default_tol(vtol))
 
-    def reduce_docs(self): check(lib().tmvb_ctm_reduce_docs(self.handle))
-    def update_beta(self): check(lib().tmvb_ctm_update_beta(self.handle))
-    def update_sigma(self): check(lib().tmvb_ctm_update_sigma(self.handle))
-    def update_mu(self): check(lib().tmvb_ctm_update_mu(self.handle))
-
-    def update_elbo(self) -> float:
-        out = C.c_double(0.0)
-        check(lib().tmvb_ctm_update_elbo(self.handle, C.byref(out)))
-        self.elbo = out.value
-        return out.value
-
-    def elbo_form(self) -> int:
-        """1 if the last update_elbo! took the decomposed form (parts left behind by the iteration itself), 0 for the token walk."""
-        f = C.c_int32(0)
-        check(lib().tmvb_ctm_elbo_form(self.handle, C.byref(f)))
-        return f.value
-
-    def stats(self):
-        p, n = VP(), C.c_int64(0)
-        check(lib().tmvb_ctm_stats(self.handle, C.byref(p), C.byref(n)))
-        return p.value, n.value
-
-    def bind_stats(self, dev_ptr: int, n_f32: int):
-        check(lib().tmvb_ctm_bind_stats(self.handle, VP(dev_ptr), C.c_int64(n_f32)))
+    reduce_docs, update_beta, update_sigma, update_mu = _op("reduce_docs"), _op("update_beta"), _op("update_sigma"), _op("update_mu")
 
     def set_distributed(self, M_total: int, distributed: bool = True):
         self.M_total = int(M_total)
-        check(lib().tmvb_ctm_set_distributed(self.handle, C.c_int64(M_total), C.c_int32(1 if distributed else 0)))
+        self._call("set_distributed", M_total, 1 if distributed else 0)
 
     def sweep_hist(self, nbins: int = 11):
         h = np.zeros(nbins, dtype=np.int64)
         ns = C.c_int64(0)
-        check(lib().tmvb_ctm_sweep_hist(self.handle, h.ctypes.data_as(P_i64), C.c_int32(nbins), C.byref(ns)))
+        self._call("sweep_hist", h.ctypes.data_as(P_i64), nbins, C.byref(ns))
         return h, ns.value
 
     def solver_stats(self):
         """Lane-per-document kernel diagnostics of the last E-step (tmvb_ctm_solver_stats)."""
         out = np.zeros(12, dtype=np.int64)
-        check(lib().tmvb_ctm_solver_stats(self.handle, out.ctypes.data_as(P_i64)))
+        self._call("solver_stats", out.ctypes.data_as(P_i64))
         names = ("cg_trips", "newton_trips", "waves", "cyc_token", "cyc_logzeta", "cyc_vsq", "cyc_gradient", "cyc_cg", "cyc_gradmv",
                  "cyc_update", "cyc_spare", "cyc_kernel")
         return dict(zip(names, out.tolist()))
 
-    def doc_sweeps(self):
-        """Sweeps each document ran in the last E-step (uint8 per document, corpus order)."""
-        out = np.zeros(max(self.M, 1), dtype=np.uint8)
-        check(lib().tmvb_ctm_doc_sweeps(self.handle, out.ctypes.data_as(C.POINTER(C.c_uint8))))
-        return out[:self.M]
-
-    def last_estep_ms(self) -> float:
-        ms = C.c_float(0.0)
-        check(lib().tmvb_ctm_last_estep_ms(self.handle, C.byref(ms)))
-        return ms.value
-
-    def synchronize(self):
-        self.ctx.synchronize()
-
     def set_comm(self, comm, M_total: int):
         """Attach a communicator (comm.py): document-sharded train!, every rank calls train() with the same arguments."""
         self.M_total = int(M_total) if comm is not None else self.M
-        self._comm = comm
-        check(lib().tmvb_ctm_set_comm(self.handle, comm.handle if comm is not None else VP(None), C.c_int64(self.M_total)))
+        self._set_comm(comm, self.M_total)
 
     def train(self, iter: int = 150, tol: float = 1.0, niter: int = 1000, ntol: float | None = None, viter: int = 10,
               vtol: float | None = None, checkelbo=1, printelbo: bool = True):
         """train!(model::gpuCTM; ...) src/gpuCTM.jl:487-519."""
-        ntol = 1.0 / self.K ** 2 if ntol is None else ntol
-        vtol = 1.0 / self.K ** 2 if vtol is None else vtol
-        check_model_ctm(self, rtol=3.5e-4)
-        _validate_train_args([tol, ntol, vtol], [iter, niter, viter], checkelbo)
-        self.update_buffer()
-        ce = 0 if checkelbo == math.inf else int(checkelbo)
-        traj = np.full(max(iter, 1), np.nan)
-        done, base = C.c_int32(0), C.c_double(float(self.elbo))
-        check(lib().tmvb_ctm_train(self.handle, C.c_int32(iter), C.c_double(tol), C.c_int32(niter), C.c_double(ntol),
-                                   C.c_int32(viter), C.c_double(vtol), C.c_int32(ce), _pd(traj), C.byref(done), C.byref(base)))
-        traj = traj[:done.value]
-        self.elbo_baseline = base.value
-        if iter > 0:
-            self.update_host()
-        if printelbo and ce:
-            _print_delbo(traj, base.value)
-        self.topics = _topic_orders(self.ctx, self.beta)
-        return traj
-
-    def close(self):
-        if getattr(self, "handle", None):
-            lib().tmvb_ctm_destroy(self.handle)
-            self.handle = VP()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return self._train(iter, tol, (niter, self._default_tol(ntol), viter, self._default_tol(vtol)), checkelbo, printelbo)
 
 
 def gpu_train_ctm(model: CTM, device_id: int = 0, **kwargs):
@@ -240,7 +141,6 @@ def predict_ctm(corp, train_model, iter: int = 10, tol: float | None = None, nit
     ntol = 1.0 / K ** 2 if ntol is None else ntol
     pc = _packed(corp)
     if pc.V != train_model.V:
-        from ._lib import CorpusError
         raise CorpusError("predict corpus and train_model corpus must have identical vocabularies.")
     if tol < 0 or ntol < 0:
         raise ValueError("tolerance parameters must be nonnegative.")
@@ -264,7 +164,6 @@ def topicdist_ctm(model, d):
     if not isinstance(d, (int, np.integer)):
         return [topicdist_ctm(model, int(x)) for x in d]
     if not (1 <= d <= model.M):
-        from ._lib import CorpusError
         raise CorpusError("document index outside corpus range.")
     x = model.lam[:, d - 1] + 0.5 * model.vsq[:, d - 1]
     x = np.exp(x - x.max())

@@ -46,9 +46,9 @@ class gpuCTMStochastic:
         self.ctx = ctx or DeviceContext(device_id)
         self.handle = VP()
         c = self.corp
-        check(lib().tmvb_ctm_svi_create(self.ctx.handle, C.c_int64(c.M), C.c_int64(c.V), c.doc_ptr.ctypes.data_as(P_i64),
-                                        c.terms.ctypes.data_as(P_i32), c.counts.ctypes.data_as(P_i32), C.c_int32(self.K),
-                                        self.cuts.ctypes.data_as(P_i64), C.c_int32(self.B), C.byref(self.handle)))
+        check(lib().tmvb_ctm_svi_create(self.ctx.handle, c.M, c.V, c.doc_ptr.ctypes.data_as(P_i64),
+                                        c.terms.ctypes.data_as(P_i32), c.counts.ctypes.data_as(P_i32), self.K,
+                                        self.cuts.ctypes.data_as(P_i64), self.B, C.byref(self.handle)))
         self.update_buffer()
 
     # ---- marshalling
@@ -97,7 +97,7 @@ class gpuCTMStochastic:
     # ---- operators
     def set_schedule(self, tau0: float = 1.0, kappa: float = 0.7):
         _validate_schedule(tau0, kappa)
-        check(lib().tmvb_ctm_svi_set_schedule(self.handle, C.c_double(tau0), C.c_double(kappa)))
+        check(lib().tmvb_ctm_svi_set_schedule(self.handle, tau0, kappa))
 
     def _tols(self, ntol, vtol):
         return (1.0 / self.K ** 2 if ntol is None else ntol), (1.0 / self.K ** 2 if vtol is None else vtol)
@@ -110,13 +110,12 @@ class gpuCTMStochastic:
         if b.size and (b.min() < 0 or b.max() >= self.B):
             raise ValueError(f"batch ids must lie in [0, {self.B}).")
         b = b.astype(np.int32)
-        check(lib().tmvb_ctm_svi_run(self.handle, b.ctypes.data_as(P_i32), C.c_int64(b.size), C.c_int32(niter), C.c_double(ntol), C.c_int32(viter),
-                                     C.c_double(vtol)))
+        check(lib().tmvb_ctm_svi_run(self.handle, b.ctypes.data_as(P_i32), b.size, niter, ntol, viter, vtol))
 
     def final_pass(self, niter: int = 1000, ntol: float | None = None, viter: int = 10, vtol: float | None = None):
         ntol, vtol = self._tols(ntol, vtol)
         _validate_svi_args([ntol, vtol], [niter, viter], 1, 0, 0.0, 1.0)
-        check(lib().tmvb_ctm_svi_final_pass(self.handle, C.c_int32(niter), C.c_double(ntol), C.c_int32(viter), C.c_double(vtol)))
+        check(lib().tmvb_ctm_svi_final_pass(self.handle, niter, ntol, viter, vtol))
 
     def info(self) -> dict:
         out = SviInfo()

@@ -18,9 +18,10 @@ import math
 
 import numpy as np
 
-from ._lib import TopicModelError, check, lib, P_i64, VP
+from ._lib import CorpusError, TopicModelError, P_i32, P_i64
+from ._model import DeviceModel, EstepTimer, PackedStats, _F, _op, _pd
 from .corpus import dirichlet_rows
-from .lda import DeviceContext, DeviceCorpus, _F, _packed, _pd, _print_delbo, _topic_orders, _validate_train_args
+from .lda import _packed
 
 
 class CTPF:
@@ -71,38 +72,30 @@ def check_model_ctpf(model):
         raise TopicModelError("elbo must be finite.")
 
 
-class gpuCTPF:
+class gpuCTPF(PackedStats, EstepTimer, DeviceModel):
     """GPU accelerated collaborative topic Poisson factorization model (src/gpuCTPF.jl:6-153) on libtmvb_hip.so."""
 
-    _FIELDS = ("corp", "K", "M", "V", "U", "N", "C", "R", "topics", "a", "b", "c", "d", "e", "f", "g", "h", "alef", "alef_old",
-               "he", "he_old", "bet", "bet_old", "vav", "vav_old", "dalet", "dalet_old", "het", "het_old", "gimel", "gimel_old",
-               "zayin", "zayin_old", "elbo", "libs", "scores", "drecs", "urecs")
-
-    def __init__(self, corp, K: int, seed: int = 7, ctx: DeviceContext | None = None, device_id: int = 0, stream=None,
-                 _from: CTPF | None = None):
-        host = _from if _from is not None else CTPF(corp, K, seed)
-        for k in self._FIELDS:
-            setattr(self, k, getattr(host, k))
-        self.ctx = ctx or DeviceContext(device_id, stream)
-        self.dcorp = DeviceCorpus(self.ctx, self.corp)
-        self.handle = VP()
-        check(lib().tmvb_ctpf_create(self.ctx.handle, self.dcorp.handle, C.c_int32(self.K), C.byref(self.handle)))
-        self.update_buffer()
+    _ABI, _HOST, _check = "ctpf", CTPF, staticmethod(check_model_ctpf)
+    _RATES = ("bet", "vav", "dalet", "het")
+    _ARRAYS = ("alef", "he") + _RATES + ("gimel", "zayin")
+    _ATTRS = (("corp", "K", "M", "V", "U", "N", "C", "R", "topics", "a", "b", "c", "d", "e", "f", "g", "h", "libs", "scores", "drecs", "urecs")
+              + _ARRAYS + tuple(n + "_old" for n in _ARRAYS))
 
     hyper = CTPF.hyper
 
+    # tmvb_ctpf_set_state takes the hyper-parameters and the current fields, _set_state_old the *_old ones, and _get_state packs the eight
+    # rate vectors into one array: the copies are written out here, not driven by _STATE
     def update_buffer(self):
         K, M, V, U = self.K, self.M, self.V, self.U
-        hy = self.hyper()
-        elbo = C.c_double(float(self.elbo))
-        vec = lambda x: np.ascontiguousarray(x, dtype=np.float64)
-        check(lib().tmvb_ctpf_set_state(self.handle, _pd(hy), _pd(_F(self.alef, (K, V))), _pd(_F(self.he, (K, U))),
-                                        _pd(vec(self.bet)), _pd(vec(self.vav)), _pd(vec(self.dalet)), _pd(vec(self.het)),
-                                        _pd(_F(self.gimel, (K, M))), _pd(_F(self.zayin, (K, M))), C.byref(elbo)))
+
+        def arrays(old):                 # the eight fields as tmvb_ctpf_set_state (old = "") and _set_state_old (old = "_old") take them
+            f = lambda n: getattr(self, n + old)
+            return [_F(f("alef"), (K, V)), _F(f("he"), (K, U)), *[np.ascontiguousarray(f(n), dtype=np.float64) for n in self._RATES],
+                    _F(f("gimel"), (K, M)), _F(f("zayin"), (K, M))]
+        hy, cur, old = self.hyper(), arrays(""), arrays("_old")
+        self._call("set_state", _pd(hy), *map(_pd, cur), C.byref(C.c_double(float(self.elbo))))
         # the *_old fields feed update_elbo! (src/CTPF.jl:239-240) and are part of update_buffer! (src/modelutils.jl:474-493)
-        check(lib().tmvb_ctpf_set_state_old(self.handle, _pd(_F(self.alef_old, (K, V))), _pd(_F(self.he_old, (K, U))),
-                                            _pd(vec(self.bet_old)), _pd(vec(self.vav_old)), _pd(vec(self.dalet_old)),
-                                            _pd(vec(self.het_old)), _pd(_F(self.gimel_old, (K, M))), _pd(_F(self.zayin_old, (K, M)))))
+        self._call("set_state_old", *map(_pd, old))
 
     def update_host(self):
         K, M, V, U = self.K, self.M, self.V, self.U
@@ -112,72 +105,34 @@ class gpuCTPF:
         self.gimel = np.empty((K, M), order="F"); self.gimel_old = np.empty((K, M), order="F")
         self.zayin = np.empty((K, M), order="F"); self.zayin_old = np.empty((K, M), order="F")
         elbo = C.c_double(0.0)
-        check(lib().tmvb_ctpf_get_state(self.handle, _pd(self.alef), _pd(self.alef_old), _pd(self.he), _pd(self.he_old),
-                                        _pd(rates), _pd(self.gimel), _pd(self.gimel_old), _pd(self.zayin), _pd(self.zayin_old),
-                                        C.byref(elbo)))
-        for q, n in enumerate(("bet", "vav", "dalet", "het", "bet_old", "vav_old", "dalet_old", "het_old")):
+        self._call("get_state", _pd(self.alef), _pd(self.alef_old), _pd(self.he), _pd(self.he_old), _pd(rates), _pd(self.gimel),
+                   _pd(self.gimel_old), _pd(self.zayin), _pd(self.zayin_old), C.byref(elbo))
+        for q, n in enumerate(self._RATES + tuple(n + "_old" for n in self._RATES)):
             setattr(self, n, rates[q * K:(q + 1) * K].copy())
         self.elbo = elbo.value
 
     def estep(self, viter: int = 10, vtol: float | None = None):
-        vtol = 1.0 / self.K ** 2 if vtol is None else vtol
-        check(lib().tmvb_ctpf_estep(self.handle, C.c_int32(viter), C.c_double(vtol)))
+        self._call("estep", viter, self._default_tol(vtol))
 
-    def reduce_docs(self): check(lib().tmvb_ctpf_reduce_docs(self.handle))
-    def mstep(self): check(lib().tmvb_ctpf_mstep(self.handle))
-
-    def elbo_form(self) -> int:
-        """1 if the last update_elbo! took the decomposed form (parts left behind by the iteration itself), 0 for the table form."""
-        f = C.c_int32(0)
-        check(lib().tmvb_ctpf_elbo_form(self.handle, C.byref(f)))
-        return f.value
-
-    def update_elbo(self) -> float:
-        out = C.c_double(0.0)
-        check(lib().tmvb_ctpf_update_elbo(self.handle, C.byref(out)))
-        self.elbo = out.value
-        return out.value
+    reduce_docs, mstep = _op("reduce_docs"), _op("mstep")
 
     def update_elbo_parts(self):
         """(per-document part summed over this context's documents, global (beta, eta) part) for document-sharded hosts."""
         a, b = C.c_double(0.0), C.c_double(0.0)
-        check(lib().tmvb_ctpf_update_elbo_parts(self.handle, C.byref(a), C.byref(b)))
+        self._call("update_elbo_parts", C.byref(a), C.byref(b))
         return a.value, b.value
 
-    def stats(self):
-        p, n = VP(), C.c_int64(0)
-        check(lib().tmvb_ctpf_stats(self.handle, C.byref(p), C.byref(n)))
-        return p.value, n.value
-
-    def bind_stats(self, dev_ptr: int, n_f32: int):
-        check(lib().tmvb_ctpf_bind_stats(self.handle, VP(dev_ptr), C.c_int64(n_f32)))
-
     def set_distributed(self, distributed: bool = True):
-        check(lib().tmvb_ctpf_set_distributed(self.handle, C.c_int32(1 if distributed else 0)))
+        self._call("set_distributed", 1 if distributed else 0)
 
     def set_comm(self, comm):
         """Attach a communicator (comm.py): document-sharded train!, every rank calls train() with the same arguments."""
-        self._comm = comm
-        check(lib().tmvb_ctpf_set_comm(self.handle, comm.handle if comm is not None else VP(None)))
+        self._set_comm(comm)
 
     def sweep_hist(self, nbins: int = 11):
         h = np.zeros(nbins, dtype=np.int64)
-        check(lib().tmvb_ctpf_sweep_hist(self.handle, h.ctypes.data_as(P_i64), C.c_int32(nbins)))
+        self._call("sweep_hist", h.ctypes.data_as(P_i64), nbins)
         return h
-
-    def doc_sweeps(self):
-        """Sweeps each document ran in the last E-step (uint8 per document, corpus order)."""
-        out = np.zeros(max(self.M, 1), dtype=np.uint8)
-        check(lib().tmvb_ctpf_doc_sweeps(self.handle, out.ctypes.data_as(C.POINTER(C.c_uint8))))
-        return out[:self.M]
-
-    def last_estep_ms(self) -> float:
-        ms = C.c_float(0.0)
-        check(lib().tmvb_ctpf_last_estep_ms(self.handle, C.byref(ms)))
-        return ms.value
-
-    def synchronize(self):
-        self.ctx.synchronize()
 
     def recommend(self, scores: bool = True):
         """scores (M x U fp64), drecs[d], urecs[u] from the device-resident state (src/CTPF.jl:379-399).  Ids are 1-based.
@@ -191,9 +146,8 @@ class gpuCTPF:
         dr = np.empty((M, U), dtype=np.int32); dc = np.empty(M, dtype=np.int32)
         ur = np.empty((U, M), dtype=np.int32); uc = np.empty(U, dtype=np.int32)
         ms0, ms1 = C.c_float(0.0), C.c_float(0.0)
-        p32 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
-        check(lib().tmvb_ctpf_recommend(self.handle, _pd(sc) if scores else None, p32(dr), p32(dc), p32(ur), p32(uc),
-                                        C.byref(ms0), C.byref(ms1)))
+        p32 = lambda a: a.ctypes.data_as(P_i32)
+        self._call("recommend", _pd(sc) if scores else None, p32(dr), p32(dc), p32(ur), p32(uc), C.byref(ms0), C.byref(ms1))
         if scores:
             self.scores = sc
         self.drecs = [dr[d, :dc[d]] + 1 for d in range(M)]
@@ -207,39 +161,16 @@ class gpuCTPF:
         self.update_host()
         return recommend_topn(self, topn, by, ids, splits)
 
+    def _topic_weights(self):
+        return self.alef / self.bet[:, None]                                                      # src/gpuCTPF.jl:707-708
+
     def train(self, iter: int = 150, tol: float = 1.0, viter: int = 10, vtol: float | None = None, checkelbo=1,
               printelbo: bool = True, recs: bool = True):
         """train!(model::gpuCTPF; ...) src/gpuCTPF.jl:677-705.  recs=False skips the M x U recommendation tail (:711-731)."""
-        vtol = 1.0 / self.K ** 2 if vtol is None else vtol
-        check_model_ctpf(self)
-        _validate_train_args([tol, vtol], [iter, viter], checkelbo)
-        self.update_buffer()
-        ce = 0 if checkelbo == math.inf else int(checkelbo)
-        traj = np.full(max(iter, 1), np.nan)
-        done, base = C.c_int32(0), C.c_double(float(self.elbo))
-        check(lib().tmvb_ctpf_train(self.handle, C.c_int32(iter), C.c_double(tol), C.c_int32(viter), C.c_double(vtol),
-                                    C.c_int32(ce), _pd(traj), C.byref(done), C.byref(base)))
-        self.elbo_baseline = base.value
-        if iter > 0:
-            self.update_host()
-        if printelbo and ce:
-            _print_delbo(traj[:done.value], base.value)
-        Ebeta = self.alef / self.bet[:, None]                                                     # :707-708
-        self.topics = _topic_orders(self.ctx, Ebeta)   # reverse(sortperm(.))
+        traj = self._train(iter, tol, (viter, self._default_tol(vtol)), checkelbo, printelbo)
         if recs:
             self.recommend()                                                                      # :711-731
-        return traj[:done.value]
-
-    def close(self):
-        if getattr(self, "handle", None):
-            lib().tmvb_ctpf_destroy(self.handle)
-            self.handle = VP()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return traj
 
 
 def gpu_train_ctpf(model: CTPF, device_id: int = 0, **kwargs):
@@ -260,7 +191,6 @@ def topicdist_ctpf(model, d):
     if not isinstance(d, (int, np.integer)):
         return [topicdist_ctpf(model, int(x)) for x in d]
     if not (1 <= d <= model.M):
-        from ._lib import CorpusError
         raise CorpusError("document index outside corpus range.")
     g = model.gimel[:, d - 1]
     return g / g.sum()

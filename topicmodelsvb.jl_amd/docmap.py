@@ -15,6 +15,7 @@ import ctypes as ct
 
 import numpy as np
 
+from ._abi import MapInfo, MapParams  # noqa: F401 (re-exported)
 from ._lib import TopicModelError, _handle, lib, P_dbl, P_f32, P_i32, P_i64
 from ._lib import check as _check
 from .lda import call_context
@@ -25,19 +26,6 @@ BISECT, RUN, SEG, SLOTS = 64, 256, 64, 64       # TMVB_MAP_BISECT, TMVB_MAP_RUN,
 RNG_MAP = 9                                     # TMVB_RNG_MAP (csrc/tmvb_philox.h)
 STOPS = {0: "iters", 1: "min_grad_norm"}
 DEFAULTS = dict(exaggeration=12.0, exag_iters=250, momentum0=0.5, momentum1=0.8, min_gain=0.01)
-
-
-class MapParams(ct.Structure):
-    """tmvb_map_params_t"""
-    _fields_ = [("iters", ct.c_int32), ("iter0", ct.c_int32), ("exag_iters", ct.c_int32), ("check", ct.c_int32), ("j_split", ct.c_int32), ("reserved", ct.c_int32),
-                ("seed", ct.c_int64), ("exaggeration", ct.c_double), ("min_grad_norm", ct.c_double), ("momentum0", ct.c_float), ("momentum1", ct.c_float),
-                ("eta", ct.c_float), ("min_gain", ct.c_float)]
-
-
-class MapInfo(ct.Structure):
-    """tmvb_map_info_t"""
-    _fields_ = [("iters", ct.c_int32), ("stop", ct.c_int32), ("n_kl", ct.c_int32), ("j_split", ct.c_int32), ("Z", ct.c_double), ("grad_norm", ct.c_double),
-                ("ms_rep", ct.c_float), ("ms_att", ct.c_float), ("ms_upd", ct.c_float), ("reserved", ct.c_float)]
 
 
 def default_eta(M, exaggeration=12.0):
@@ -59,8 +47,8 @@ def map_affinity_raw(ctx, idx, d2, count, perplexity, Mc=None, symmetric=True):
     cap = 2 * max(M, 1) * max(n, 1) if symmetric else 1
     row_ptr, col, val = np.zeros(max(M, 1) + 1, dtype=np.int64), np.zeros(cap, dtype=np.int32), np.zeros(cap, dtype=np.float32)
     null = lambda t: ct.cast(None, t)
-    rc = L.tmvb_map_affinity(_handle(ctx), ct.c_int64(M), ct.c_int64(M if Mc is None else int(Mc)), ct.c_int32(n), idx.ctypes.data_as(P_i32), d2.ctypes.data_as(P_f32),
-                             count.ctypes.data_as(P_i32), ct.c_double(float(perplexity)), beta.ctypes.data_as(P_dbl), p.ctypes.data_as(P_dbl),
+    rc = L.tmvb_map_affinity(_handle(ctx), M, M if Mc is None else int(Mc), n, idx.ctypes.data_as(P_i32), d2.ctypes.data_as(P_f32),
+                             count.ctypes.data_as(P_i32), float(perplexity), beta.ctypes.data_as(P_dbl), p.ctypes.data_as(P_dbl),
                              row_ptr.ctypes.data_as(P_i64) if symmetric else null(P_i64), col.ctypes.data_as(P_i32) if symmetric else null(P_i32),
                              val.ctypes.data_as(P_f32) if symmetric else null(P_f32))
     if rc != 0:
@@ -107,8 +95,8 @@ def map_layout_raw(ctx, M, row_ptr, col, val, iters, iter0=0, y=None, vel=None, 
     rep, zrow, att, grad = np.zeros((rows, 2)), np.zeros(rows), np.zeros((rows, 2)), np.zeros((rows, 2), dtype=np.float32)
     opt = (lambda a, t: a.ctypes.data_as(t)) if pieces else (lambda a, t: ct.cast(None, t))
     info = MapInfo()
-    rc = L.tmvb_map_layout(_handle(ctx), ct.c_int64(M), row_ptr.ctypes.data_as(P_i64), col.ctypes.data_as(P_i32), val.ctypes.data_as(P_f32), ct.byref(P), y0p, v0p, g0p,
-                           yo.ctypes.data_as(P_f32), vo.ctypes.data_as(P_f32), go.ctypes.data_as(P_f32), ct.c_int32(cap), kl.ctypes.data_as(P_dbl),
+    rc = L.tmvb_map_layout(_handle(ctx), M, row_ptr.ctypes.data_as(P_i64), col.ctypes.data_as(P_i32), val.ctypes.data_as(P_f32), ct.byref(P), y0p, v0p, g0p,
+                           yo.ctypes.data_as(P_f32), vo.ctypes.data_as(P_f32), go.ctypes.data_as(P_f32), cap, kl.ctypes.data_as(P_dbl),
                            kl_iter.ctypes.data_as(P_i32), opt(rep, P_dbl), opt(zrow, P_dbl), opt(att, P_dbl), opt(grad, P_f32), ct.byref(info))
     if rc != 0:
         return rc, L.tmvb_last_error().decode("utf-8", "replace")

@@ -17,14 +17,15 @@ is commented out of the reference's train! (src/fCTM.jl:253).  No CPU fallback.
 from __future__ import annotations
 
 import ctypes as C
-import math
+import functools
 
 import numpy as np
 
-from ._lib import TopicModelError, check, lib, P_i64, VP
+from ._lib import CorpusError, TopicModelError, P_i64
+from ._model import DeviceContext, DeviceModel, _op
 from .corpus import dirichlet_rows
 from .ctm import CTM, check_model_ctm
-from .lda import DeviceContext, DeviceCorpus, _F, _pd, _print_delbo, _topic_orders, _validate_train_args
+from .lda import _packed
 
 
 class fCTM(CTM):
@@ -57,126 +58,41 @@ def check_model_fctm(model, rtol: float = 1.5e-8):
         raise TopicModelError("tau must belong to the interval [0,1].")
 
 
-class gpufCTM:
+class gpufCTM(DeviceModel):
     """Device-backed filtered CTM model on libtmvb_hip.so."""
 
-    _FIELDS = ("corp", "K", "M", "V", "N", "C", "topics", "eta", "mu", "sigma", "invsigma", "kappa", "kappa_old", "beta", "beta_old",
-               "lam", "lam_old", "vsq", "logzeta", "tau", "tau_old", "elbo")
+    _ABI, _HOST, _check = "fctm", fCTM, staticmethod(functools.partial(check_model_fctm, rtol=3.5e-4))
+    _STATE = (("eta", ""), ("mu", "K"), ("sigma", "KK"), ("invsigma", "KK"), ("kappa", "V"), ("kappa_old", "V"), ("beta", "KV"),
+              ("beta_old", "KV"), ("lam", "KM"), ("lam_old", "KM"), ("vsq", "KM"), ("logzeta", "M"), ("tau", "N"), ("tau_old", "N"))
 
     def __init__(self, corp, K: int, seed: int = 7, ctx: DeviceContext | None = None, device_id: int = 0, _from: fCTM | None = None):
         if not (isinstance(K, (int, np.integer)) and K > 0):
             raise ValueError("number of topics must be a positive integer.")
-        host = _from if _from is not None else fCTM(corp, K, seed)
-        for k in self._FIELDS:
-            setattr(self, k, getattr(host, k))
-        self.ctx = ctx or DeviceContext(device_id)
-        self.dcorp = DeviceCorpus(self.ctx, self.corp)
-        self.handle = VP()
-        check(lib().tmvb_fctm_create(self.ctx.handle, self.dcorp.handle, C.c_int32(self.K), C.byref(self.handle)))
-        self.M_total = self.M
-        self.update_buffer()
-
-    def update_buffer(self):
-        K, M, V, nnz = self.K, self.M, self.V, self.corp.nnz
-        vec = lambda x, n: np.ascontiguousarray(np.asarray(x, dtype=np.float64).reshape(n))
-        eta, elbo = C.c_double(float(self.eta)), C.c_double(float(self.elbo))
-        check(lib().tmvb_fctm_set_state(self.handle, C.byref(eta), _pd(vec(self.mu, K)), _pd(_F(self.sigma, (K, K))),
-                                        _pd(_F(self.invsigma, (K, K))), _pd(vec(self.kappa, V)), _pd(vec(self.kappa_old, V)),
-                                        _pd(_F(self.beta, (K, V))), _pd(_F(self.beta_old, (K, V))), _pd(_F(self.lam, (K, M))),
-                                        _pd(_F(self.lam_old, (K, M))), _pd(_F(self.vsq, (K, M))), _pd(vec(self.logzeta, M)),
-                                        _pd(vec(self.tau, nnz)), _pd(vec(self.tau_old, nnz)), C.byref(elbo)))
-
-    def update_host(self):
-        K, M, V, nnz = self.K, self.M, self.V, self.corp.nnz
-        eta, elbo = C.c_double(0.0), C.c_double(0.0)
-        self.mu = np.empty(K)
-        self.sigma = np.empty((K, K), order="F"); self.invsigma = np.empty((K, K), order="F")
-        self.kappa = np.empty(V); self.kappa_old = np.empty(V)
-        self.beta = np.empty((K, V), order="F"); self.beta_old = np.empty((K, V), order="F")
-        self.lam = np.empty((K, M), order="F"); self.lam_old = np.empty((K, M), order="F")
-        self.vsq = np.empty((K, M), order="F"); self.logzeta = np.empty(M)
-        self.tau = np.empty(nnz); self.tau_old = np.empty(nnz)
-        check(lib().tmvb_fctm_get_state(self.handle, C.byref(eta), _pd(self.mu), _pd(self.sigma), _pd(self.invsigma), _pd(self.kappa),
-                                        _pd(self.kappa_old), _pd(self.beta), _pd(self.beta_old), _pd(self.lam), _pd(self.lam_old),
-                                        _pd(self.vsq), _pd(self.logzeta), _pd(self.tau), _pd(self.tau_old), C.byref(elbo)))
-        self.eta, self.elbo = eta.value, elbo.value
+        super().__init__(corp, K, seed, ctx, device_id, _from=_from)
 
     def estep(self, niter: int = 1000, ntol: float | None = None, viter: int = 10, vtol: float | None = None):
-        ntol = 1.0 / self.K ** 2 if ntol is None else ntol
-        vtol = 1.0 / self.K ** 2 if vtol is None else vtol
-        check(lib().tmvb_fctm_estep(self.handle, C.c_int32(niter), C.c_double(ntol), C.c_int32(viter), C.c_double(vtol)))
+        self._call("estep", niter, self._default_tol(ntol), viter, self._default_tol(vtol))
 
-    def reduce_docs(self): check(lib().tmvb_fctm_reduce_docs(self.handle))
-    def update_beta(self): check(lib().tmvb_fctm_update_beta(self.handle))          # beta and kappa (src/fCTM.jl:249-250)
-    def update_sigma(self): check(lib().tmvb_fctm_update_sigma(self.handle))
-    def update_mu(self): check(lib().tmvb_fctm_update_mu(self.handle))
+    reduce_docs, update_sigma, update_mu = _op("reduce_docs"), _op("update_sigma"), _op("update_mu")
+    update_beta = _op("update_beta")                    # beta and kappa (src/fCTM.jl:249-250)
 
     def mstep(self):
         self.update_beta(); self.update_sigma(); self.update_mu()
 
-    def elbo_form(self) -> int:
-        """1 if the last update_elbo! took the decomposed form (tmvb_fctm_elbo_form: nothing per token rebuilt), 0 for the token walk."""
-        f = C.c_int32(0)
-        check(lib().tmvb_fctm_elbo_form(self.handle, C.byref(f)))
-        return f.value
-
-    def update_elbo(self) -> float:
-        out = C.c_double(0.0)
-        check(lib().tmvb_fctm_update_elbo(self.handle, C.byref(out)))
-        self.elbo = out.value
-        return out.value
-
     def sweep_hist(self, nbins: int = 11):
         h = np.zeros(nbins, dtype=np.int64)
         ns = C.c_int64(0)
-        check(lib().tmvb_fctm_sweep_hist(self.handle, h.ctypes.data_as(P_i64), C.c_int32(nbins), C.byref(ns)))
+        self._call("sweep_hist", h.ctypes.data_as(P_i64), nbins, C.byref(ns))
         return h, ns.value
-
-    def doc_sweeps(self):
-        out = np.zeros(max(self.M, 1), dtype=np.uint8)
-        check(lib().tmvb_fctm_doc_sweeps(self.handle, out.ctypes.data_as(C.POINTER(C.c_uint8))))
-        return out[:self.M]
 
     def set_comm(self, comm, M_total: int):
         self.M_total = int(M_total) if comm is not None else self.M
-        self._comm = comm
-        check(lib().tmvb_fctm_set_comm(self.handle, comm.handle if comm is not None else VP(None), C.c_int64(self.M_total)))
-
-    def synchronize(self):
-        self.ctx.synchronize()
+        self._set_comm(comm, self.M_total)
 
     def train(self, iter: int = 150, tol: float = 1.0, niter: int = 1000, ntol: float | None = None, viter: int = 10,
               vtol: float | None = None, checkelbo=1, printelbo: bool = True):
         """train!(model::fCTM; ...) src/fCTM.jl:226-262 on the device.  Returns the ELBO trajectory."""
-        ntol = 1.0 / self.K ** 2 if ntol is None else ntol
-        vtol = 1.0 / self.K ** 2 if vtol is None else vtol
-        check_model_fctm(self, rtol=3.5e-4)
-        _validate_train_args([tol, ntol, vtol], [iter, niter, viter], checkelbo)
-        self.update_buffer()
-        ce = 0 if checkelbo == math.inf else int(checkelbo)
-        traj = np.full(max(iter, 1), np.nan)
-        done, base = C.c_int32(0), C.c_double(float(self.elbo))
-        check(lib().tmvb_fctm_train(self.handle, C.c_int32(iter), C.c_double(tol), C.c_int32(niter), C.c_double(ntol), C.c_int32(viter),
-                                    C.c_double(vtol), C.c_int32(ce), _pd(traj), C.byref(done), C.byref(base)))
-        traj = traj[:done.value]
-        self.elbo_baseline = base.value
-        if iter > 0:
-            self.update_host()
-        if printelbo and ce:
-            _print_delbo(traj, base.value)
-        self.topics = _topic_orders(self.ctx, self.beta)   # :260
-        return traj
-
-    def close(self):
-        if getattr(self, "handle", None):
-            lib().tmvb_fctm_destroy(self.handle)
-            self.handle = VP()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return self._train(iter, tol, (niter, self._default_tol(ntol), viter, self._default_tol(vtol)), checkelbo, printelbo)
 
 
 def gpu_train_fctm(model: fCTM, device_id: int = 0, **kwargs):
@@ -204,10 +120,8 @@ def predict_fctm(corp, train_model, iter: int = 10, tol: float | None = None, ni
     K = train_model.K
     tol = 1.0 / K ** 2 if tol is None else tol
     ntol = 1.0 / K ** 2 if ntol is None else ntol
-    from .lda import _packed
     pc = _packed(corp)
     if pc.V != train_model.V:
-        from ._lib import CorpusError
         raise CorpusError("predict corpus and train_model corpus must have identical vocabularies.")
     if tol < 0 or ntol < 0:
         raise ValueError("tolerance parameters must be nonnegative.")

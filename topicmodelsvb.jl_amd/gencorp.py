@@ -16,36 +16,28 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import _copy, _handle, check, lib, P_dbl, P_i32, P_i64
+from ._abi import GenCorpResult  # noqa: F401 (re-exported)
+from ._lib import _copy, _handle, check, lib, P_dbl
 from .corpus import Document, PackedCorpus
 from .lda import call_context
-
-
-class GenCorpResult(C.Structure):
-    """tmvb_gencorp_t"""
-    _fields_ = [("M", C.c_int64), ("nnz", C.c_int64), ("sum_counts", C.c_int64),
-                ("doc_ptr", P_i64), ("terms", P_i32), ("counts", P_i32),
-                ("log_theta", C.POINTER(C.c_float)), ("doc_topic", P_i32), ("topic_term", P_i64),
-                ("ms_tables", C.c_float), ("ms_docs", C.c_float), ("ms_tokens", C.c_float), ("ms_condense", C.c_float)]
 
 
 def gencorp_raw(ctx, K, V, beta, M, mean_C, alpha=None, mu=None, sigma=None, laplace_smooth=0.0, seed=0, doc_offset=0, diagnostics=False):
     """The ABI call.  alpha -> tmvb_lda_gencorp, (mu, sigma) -> tmvb_ctm_gencorp.  ctx: a DeviceContext, or None for a NULL context (the
     library then answers TMVB_ENODEVICE on a machine without a GPU).  Returns (status, dict): nothing raises here."""
     L = lib()
-    L.tmvb_gencorp_free.restype = None
     f64 = lambda a: np.asfortranarray(np.asarray(a, dtype=np.float64))
     beta = f64(beta)
     out = GenCorpResult()
     h = _handle(ctx)
-    tail = (C.c_int64(int(M)), C.c_int64(int(doc_offset)), C.c_double(mean_C), C.c_double(laplace_smooth),
-            C.c_int64(np.uint64(int(seed) % 2 ** 64).astype(np.int64)), C.c_int32(1 if diagnostics else 0), C.byref(out))
+    tail = (int(M), int(doc_offset), mean_C, laplace_smooth,
+            np.uint64(int(seed) % 2 ** 64).astype(np.int64), 1 if diagnostics else 0, C.byref(out))
     if alpha is not None:
         alpha = f64(alpha)
-        rc = L.tmvb_lda_gencorp(h, C.c_int32(K), C.c_int64(V), alpha.ctypes.data_as(P_dbl), beta.ctypes.data_as(P_dbl), *tail)
+        rc = L.tmvb_lda_gencorp(h, K, V, alpha.ctypes.data_as(P_dbl), beta.ctypes.data_as(P_dbl), *tail)
     else:
         mu, sigma = f64(mu), f64(sigma)
-        rc = L.tmvb_ctm_gencorp(h, C.c_int32(K), C.c_int64(V), mu.ctypes.data_as(P_dbl), sigma.ctypes.data_as(P_dbl), beta.ctypes.data_as(P_dbl), *tail)
+        rc = L.tmvb_ctm_gencorp(h, K, V, mu.ctypes.data_as(P_dbl), sigma.ctypes.data_as(P_dbl), beta.ctypes.data_as(P_dbl), *tail)
     if rc != 0:
         return rc, {"error": L.tmvb_last_error().decode("utf-8", "replace")}
     try:

@@ -17,17 +17,10 @@ import ctypes as C
 
 import numpy as np
 
+from ._abi import SplitResult  # noqa: F401 (re-exported)
 from ._lib import CorpusError, TopicModelError, _copy, _csr, _handle, check, lib, P_dbl, P_i32, P_i64
 from .corpus import PackedCorpus
 from .lda import _packed, call_context
-
-
-class SplitResult(C.Structure):
-    """tmvb_split_t"""
-    _fields_ = [("M", C.c_int64), ("nnz_obs", C.c_int64), ("nnz_held", C.c_int64), ("sum_obs", C.c_int64), ("sum_held", C.c_int64),
-                ("obs_ptr", P_i64), ("obs_terms", P_i32), ("obs_counts", P_i32),
-                ("held_ptr", P_i64), ("held_terms", P_i32), ("held_counts", P_i32),
-                ("ms_draw", C.c_float), ("ms_compact", C.c_float)]
 
 
 class HeldoutResult:
@@ -57,12 +50,11 @@ def split_corpus_raw(ctx, M, V, doc_ptr, terms, counts, frac=0.5, seed=0, doc_of
     """The ABI call tmvb_corpus_split.  ctx: a DeviceContext, or None for a NULL context (the library then answers TMVB_ENODEVICE on a
     machine without a GPU).  Returns (status, dict): nothing raises here."""
     L = lib()
-    L.tmvb_split_free.restype = None
     doc_ptr, terms, counts = _csr(doc_ptr, terms, counts)
     out = SplitResult()
-    rc = L.tmvb_corpus_split(_handle(ctx), C.c_int64(int(M)), C.c_int64(int(V)), doc_ptr.ctypes.data_as(P_i64), terms.ctypes.data_as(P_i32),
-                             counts.ctypes.data_as(P_i32), C.c_double(frac), C.c_int64(np.uint64(int(seed) % 2 ** 64).astype(np.int64)),
-                             C.c_int64(int(doc_offset)), C.byref(out))
+    rc = L.tmvb_corpus_split(_handle(ctx), int(M), int(V), doc_ptr.ctypes.data_as(P_i64), terms.ctypes.data_as(P_i32),
+                             counts.ctypes.data_as(P_i32), frac, np.uint64(int(seed) % 2 ** 64).astype(np.int64),
+                             int(doc_offset), C.byref(out))
     if rc != 0:
         return rc, {"error": L.tmvb_last_error().decode("utf-8", "replace")}
     try:
@@ -88,8 +80,8 @@ def heldout_loglik_raw(ctx, K, V, theta, beta, pc, laplace_smooth=0.0):
     M = len(doc_ptr) - 1
     ll = np.zeros(max(M, 1)); tokens = np.zeros(max(M, 1), dtype=np.int64)
     zero, ms = C.c_int64(0), C.c_float(0.0)
-    rc = L.tmvb_heldout_loglik(_handle(ctx), C.c_int32(int(K)), C.c_int64(int(V)), C.c_int64(M), theta.ctypes.data_as(P_dbl), beta.ctypes.data_as(P_dbl),
-                               doc_ptr.ctypes.data_as(P_i64), terms.ctypes.data_as(P_i32), counts.ctypes.data_as(P_i32), C.c_double(laplace_smooth),
+    rc = L.tmvb_heldout_loglik(_handle(ctx), int(K), int(V), M, theta.ctypes.data_as(P_dbl), beta.ctypes.data_as(P_dbl),
+                               doc_ptr.ctypes.data_as(P_i64), terms.ctypes.data_as(P_i32), counts.ctypes.data_as(P_i32), laplace_smooth,
                                ll.ctypes.data_as(P_dbl), tokens.ctypes.data_as(P_i64), C.byref(zero), C.byref(ms))
     if rc != 0:
         return rc, L.tmvb_last_error().decode("utf-8", "replace")

@@ -19,13 +19,9 @@ import ctypes as C
 
 import numpy as np
 
+from ._abi import SviInfo  # noqa: F401 (re-exported)
 from ._lib import TopicModelError, check, lib, P_i32, P_i64, VP
 from .lda import LDA, DeviceContext, _F, _packed, _pd, _topic_orders, check_model
-
-
-class SviInfo(C.Structure):
-    _fields_ = [("B", C.c_int32), ("K", C.c_int32), ("M", C.c_int64), ("V", C.c_int64), ("t", C.c_int64), ("tau0", C.c_double),
-                ("kappa", C.c_double), ("rho", C.c_double), ("c0", C.c_float), ("c1", C.c_float)]
 
 
 def _validate_schedule(tau0, kappa):
@@ -84,9 +80,9 @@ class gpuLDAStochastic:
         self.ctx = ctx or DeviceContext(device_id)
         self.handle = VP()
         c = self.corp
-        check(lib().tmvb_lda_svi_create(self.ctx.handle, C.c_int64(c.M), C.c_int64(c.V), c.doc_ptr.ctypes.data_as(P_i64),
-                                        c.terms.ctypes.data_as(P_i32), c.counts.ctypes.data_as(P_i32), C.c_int32(self.K),
-                                        self.cuts.ctypes.data_as(P_i64), C.c_int32(self.B), C.byref(self.handle)))
+        check(lib().tmvb_lda_svi_create(self.ctx.handle, c.M, c.V, c.doc_ptr.ctypes.data_as(P_i64),
+                                        c.terms.ctypes.data_as(P_i32), c.counts.ctypes.data_as(P_i32), self.K,
+                                        self.cuts.ctypes.data_as(P_i64), self.B, C.byref(self.handle)))
         self.update_buffer()
 
     # ---- marshalling
@@ -122,7 +118,7 @@ class gpuLDAStochastic:
     # ---- operators
     def set_schedule(self, tau0: float = 1.0, kappa: float = 0.7):
         _validate_schedule(tau0, kappa)
-        check(lib().tmvb_lda_svi_set_schedule(self.handle, C.c_double(tau0), C.c_double(kappa)))
+        check(lib().tmvb_lda_svi_set_schedule(self.handle, tau0, kappa))
 
     def run(self, batches, niter: int = 1000, ntol: float | None = None, viter: int = 10, vtol: float | None = None):
         """One step per entry of `batches` (ids in [0, B), repeats allowed); asynchronous."""
@@ -133,13 +129,12 @@ class gpuLDAStochastic:
         if b.size and (b.min() < 0 or b.max() >= self.B):
             raise ValueError(f"batch ids must lie in [0, {self.B}).")
         b = b.astype(np.int32)
-        check(lib().tmvb_lda_svi_run(self.handle, b.ctypes.data_as(P_i32), C.c_int64(b.size), C.c_int32(niter), C.c_double(ntol), C.c_int32(viter),
-                                     C.c_double(vtol)))
+        check(lib().tmvb_lda_svi_run(self.handle, b.ctypes.data_as(P_i32), b.size, niter, ntol, viter, vtol))
 
     def final_pass(self, viter: int = 10, vtol: float | None = None):
         vtol = 1.0 / self.K ** 2 if vtol is None else vtol
         _validate_svi_args([vtol], [viter], 1, 0, 0.0, 1.0)
-        check(lib().tmvb_lda_svi_final_pass(self.handle, C.c_int32(viter), C.c_double(vtol)))
+        check(lib().tmvb_lda_svi_final_pass(self.handle, viter, vtol))
 
     def info(self) -> dict:
         out = SviInfo()

@@ -15,19 +15,14 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import CorpusError, TopicModelError, _handle, check, lib, P_dbl, P_i32
+from ._abi import NeighborsInfo  # noqa: F401 (re-exported)
+from ._lib import CorpusError, TopicModelError, _handle, check, lib, P_dbl, P_f32, P_i32
 from .lda import call_context
 
 DOT, HELLINGER, COSINE = 0, 1, 2        # TMVB_NB_* (include/tmvb.h)
 METRICS = {"dot": DOT, "hellinger": HELLINGER, "cosine": COSINE}
 TOPN_MAX = 64                           # TMVB_NB_TOPN_MAX
 TILE_DB = 128                           # TMVB_NB_TILE_DB: database rows per tile of the scan kernel
-P_f32 = C.POINTER(C.c_float)
-
-
-class NeighborsInfo(C.Structure):
-    """tmvb_neighbors_info_t"""
-    _fields_ = [("splits", C.c_int32), ("kp", C.c_int32), ("ms_prep", C.c_float), ("ms_scan", C.c_float), ("ms_merge", C.c_float)]
 
 
 class NeighborsResult:
@@ -77,8 +72,8 @@ def neighbors_raw(ctx, K, metric, xd, xq=None, q0=0, n=10, splits=0, Mq=None):
     score = np.zeros((rows, cols), dtype=np.float32)
     count = np.zeros(rows, dtype=np.int32)
     info = NeighborsInfo()
-    rc = L.tmvb_topic_neighbors(_handle(ctx), C.c_int32(int(K)), C.c_int32(int(metric)), C.c_int64(Md), xd.ctypes.data_as(P_dbl), C.c_int64(Mq), q_ptr,
-                                C.c_int64(int(q0)), C.c_int32(int(n)), C.c_int32(int(splits)), idx.ctypes.data_as(P_i32), score.ctypes.data_as(P_f32),
+    rc = L.tmvb_topic_neighbors(_handle(ctx), int(K), int(metric), Md, xd.ctypes.data_as(P_dbl), Mq, q_ptr,
+                                int(q0), int(n), int(splits), idx.ctypes.data_as(P_i32), score.ctypes.data_as(P_f32),
                                 count.ctypes.data_as(P_i32), C.byref(info))
     if rc != 0:
         return rc, L.tmvb_last_error().decode("utf-8", "replace")

@@ -18,26 +18,14 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import TopicModelError, _copy, _handle, check, lib, P_dbl, P_i32, P_i64
+from ._abi import ReaderSplit, RecRanksInfo  # noqa: F401 (re-exported)
+from ._lib import TopicModelError, _copy, _handle, check, lib, P_dbl, P_f32, P_i32, P_i64
 from .corpus import PackedCorpus
 from .lda import _packed, call_context
 
 ENTRY, DOCUMENT = 0, 1                  # TMVB_RSPLIT_* (include/tmvb.h)
 MODES = {"entry": ENTRY, "document": DOCUMENT}
 TILE_DB = 128                           # TMVB_NB_TILE_DB: database rows per tile of the scan kernel
-P_f32 = C.POINTER(C.c_float)
-
-
-class ReaderSplit(C.Structure):
-    """tmvb_rsplit_t"""
-    _fields_ = [("M", C.c_int64), ("n_obs", C.c_int64), ("n_held", C.c_int64),
-                ("obs_ptr", P_i64), ("obs_readers", P_i32), ("obs_ratings", P_i32),
-                ("held_ptr", P_i64), ("held_readers", P_i32), ("held_ratings", P_i32)]
-
-
-class RecRanksInfo(C.Structure):
-    """tmvb_recranks_info_t"""
-    _fields_ = [("splits", C.c_int32), ("kp", C.c_int32), ("ms_prep", C.c_float), ("ms_pairs", C.c_float), ("ms_scan", C.c_float), ("ms_fix", C.c_float)]
 
 
 def transpose_csr(ptr, idx, n_cols, vals=None):
@@ -72,13 +60,12 @@ class HeldReaders:
 def split_readers_raw(M, U, rdr_ptr, readers, ratings, frac=0.2, seed=0, doc_offset=0, mode=ENTRY):
     """The ABI call tmvb_readers_split (host only).  Returns (status, dict) or (status, message): nothing raises here."""
     L = lib()
-    L.tmvb_rsplit_free.restype = None
     rdr_ptr = np.ascontiguousarray(rdr_ptr, dtype=np.int64)
     readers = np.ascontiguousarray(readers, dtype=np.int32)
     ratings = np.ascontiguousarray(ratings, dtype=np.int32)
     out = ReaderSplit()
-    rc = L.tmvb_readers_split(C.c_int64(int(M)), C.c_int64(int(U)), rdr_ptr.ctypes.data_as(P_i64), readers.ctypes.data_as(P_i32), ratings.ctypes.data_as(P_i32),
-                              C.c_double(frac), C.c_int64(np.uint64(int(seed) % 2 ** 64).astype(np.int64)), C.c_int64(int(doc_offset)), C.c_int32(int(mode)),
+    rc = L.tmvb_readers_split(int(M), int(U), rdr_ptr.ctypes.data_as(P_i64), readers.ctypes.data_as(P_i32), ratings.ctypes.data_as(P_i32),
+                              frac, np.uint64(int(seed) % 2 ** 64).astype(np.int64), int(doc_offset), int(mode),
                               C.byref(out))
     if rc != 0:
         return rc, L.tmvb_last_error().decode("utf-8", "replace")
@@ -128,9 +115,9 @@ def rec_ranks_raw(ctx, K, xd, xq, excl, tgt, splits=0):
     score = np.zeros(max(nT, 1), dtype=np.float32)
     n_cand = np.zeros(max(Mq, 1), dtype=np.int32)
     info = RecRanksInfo()
-    rc = L.tmvb_score_ranks(_handle(ctx), C.c_int32(int(K)), C.c_int64(Md), xd.ctypes.data_as(P_dbl), C.c_int64(Mq), xq.ctypes.data_as(P_dbl),
+    rc = L.tmvb_score_ranks(_handle(ctx), int(K), Md, xd.ctypes.data_as(P_dbl), Mq, xq.ctypes.data_as(P_dbl),
                             eptr.ctypes.data_as(P_i64), eidx.ctypes.data_as(P_i32), tptr.ctypes.data_as(P_i64), tidx.ctypes.data_as(P_i32),
-                            C.c_int32(int(splits)), rank.ctypes.data_as(P_i32), n_cand.ctypes.data_as(P_i32), score.ctypes.data_as(P_f32), C.byref(info))
+                            int(splits), rank.ctypes.data_as(P_i32), n_cand.ctypes.data_as(P_i32), score.ctypes.data_as(P_f32), C.byref(info))
     if rc != 0:
         return rc, L.tmvb_last_error().decode("utf-8", "replace")
     return rc, {"rank": rank[:nT], "score": score[:nT], "n_cand": n_cand[:Mq], "splits": int(info.splits), "kp": int(info.kp),
@@ -151,7 +138,7 @@ def rank_metrics_raw(tgt_ptr, rank, n_cand, Ns):
     rec, pre, nd = (np.zeros((rows, cols)) for _ in range(3))
     mrr, pct = np.zeros(rows), np.zeros(rows)
     mean, counts = np.zeros(3 * cols + 2), np.zeros(2, dtype=np.int64)
-    rc = L.tmvb_rank_metrics(C.c_int64(Mq), tptr.ctypes.data_as(P_i64), rank.ctypes.data_as(P_i32), n_cand.ctypes.data_as(P_i32), C.c_int32(nN),
+    rc = L.tmvb_rank_metrics(Mq, tptr.ctypes.data_as(P_i64), rank.ctypes.data_as(P_i32), n_cand.ctypes.data_as(P_i32), nN,
                              Ns.ctypes.data_as(P_i32), rec.ctypes.data_as(P_dbl), pre.ctypes.data_as(P_dbl), nd.ctypes.data_as(P_dbl), mrr.ctypes.data_as(P_dbl),
                              pct.ctypes.data_as(P_dbl), mean.ctypes.data_as(P_dbl), counts.ctypes.data_as(P_i64))
     if rc != 0:

@@ -60,9 +60,9 @@ def search_raw(ctx, K, V, theta, beta, q_ptr, q_terms, q_counts, n=10, laplace_s
     score = np.zeros((rows, cols), dtype=np.float32)
     count = np.zeros(rows, dtype=np.int32)
     info = SearchInfo()
-    rc = L.tmvb_topic_search(_handle(ctx), C.c_int32(int(K)), C.c_int64(int(V)), C.c_int64(Md), theta.ctypes.data_as(P_dbl), beta.ctypes.data_as(P_dbl),
-                             C.c_double(float(laplace_smooth)), C.c_int64(Q), q_ptr.ctypes.data_as(P_i64), q_terms.ctypes.data_as(P_i32),
-                             q_counts.ctypes.data_as(P_i32), C.c_int32(int(n)), C.c_int32(int(splits)), idx.ctypes.data_as(P_i32), score.ctypes.data_as(P_f32),
+    rc = L.tmvb_topic_search(_handle(ctx), int(K), int(V), Md, theta.ctypes.data_as(P_dbl), beta.ctypes.data_as(P_dbl),
+                             float(laplace_smooth), Q, q_ptr.ctypes.data_as(P_i64), q_terms.ctypes.data_as(P_i32),
+                             q_counts.ctypes.data_as(P_i32), int(n), int(splits), idx.ctypes.data_as(P_i32), score.ctypes.data_as(P_f32),
                              count.ctypes.data_as(P_i32), C.byref(info))
     if rc != 0:
         return rc, L.tmvb_last_error().decode("utf-8", "replace")

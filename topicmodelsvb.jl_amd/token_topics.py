@@ -28,7 +28,7 @@ def digamma(x):
     """psi(x) in fp64 by the library's host digamma (tmvb_digamma_f64; touches no device)."""
     x = np.ascontiguousarray(x, dtype=np.float64)
     y = np.empty_like(x)
-    check(lib().tmvb_digamma_f64(x.ctypes.data_as(P_dbl), y.ctypes.data_as(P_dbl), C.c_int64(x.size)))
+    check(lib().tmvb_digamma_f64(x.ctypes.data_as(P_dbl), y.ctypes.data_as(P_dbl), x.size))
     return y
 
 
@@ -62,8 +62,8 @@ def token_topics_raw(ctx, K, V, A, B, pc, docs=None, top=1, eps=EPSILON, phi=Fal
         return 1, f"token_topics_raw: {e}"
     info = TokenTopicsInfo()
     p = lambda a, ty: a.ctypes.data_as(ty) if a is not None else None
-    rc = L.tmvb_token_topics(_handle(ctx), C.c_int32(K), C.c_int64(V), C.c_int64(M), p(A, P_dbl), p(B, P_dbl), p(doc_ptr, P_i64), p(terms, P_i32),
-                             p(counts, P_i32), p(d32, P_i32), C.c_int64(Ms), C.c_double(float(eps)), C.c_int32(t), C.c_int64(int(max_chunk_entries)),
+    rc = L.tmvb_token_topics(_handle(ctx), K, V, M, p(A, P_dbl), p(B, P_dbl), p(doc_ptr, P_i64), p(terms, P_i32),
+                             p(counts, P_i32), p(d32, P_i32), Ms, float(eps), t, int(max_chunk_entries),
                              p(top_idx, P_i32), p(top_r, P_f32), p(dense, P_f32), p(hd, P_i64), C.byref(info))
     if rc != 0:
         return rc, L.tmvb_last_error().decode("utf-8", "replace")
