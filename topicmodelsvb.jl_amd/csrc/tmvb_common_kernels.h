@@ -358,20 +358,6 @@ static int dispatch_nslot(int nslot, F&& f)
 static size_t tmvb_tile_bytes(int rows, int KP) { return ((size_t)rows * KP + KP + 3 * (size_t)rows) * sizeof(float); }
 
 
-template <typename T>
-static int dmalloc(T** p, size_t n)
-{
-    *p = nullptr;
-    size_t bytes = std::max<size_t>(n, 1) * sizeof(T);
-    hipError_t e = hipMalloc((void**)p, bytes);
-    if (e != hipSuccess) {
-        tmvb_set_error("hipMalloc(%zu bytes) failed: %s", bytes, hipGetErrorString(e));
-        return TMVB_ENOMEM;
-    }
-    return TMVB_OK;
-}
-
-
 static int upload_f32(tmvb_ctx* ctx, float* dst, const double* src, size_t n)
 {
     std::vector<float> tmp(n);

@@ -27,6 +27,8 @@
 #define TMVB_TS_LOGZ 1            // the log-normaliser forms of the statistics pass (decomposed update_elbo!, see ctm_elbo_kernel)
 #include "tmvb_common_kernels.h"
 #include "tmvb_train.h"
+#include "tmvb_handle.h"
+#include "tmvb_model.h"
 #include "tmvb_filtered.h"
 
 #include <utility>
@@ -1411,22 +1413,13 @@ __global__ __launch_bounds__(1024) void sum_docs_kernel(const double* __restrict
 }
 
 // ------------------------------------------------------------------------------ host side
-struct tmvb_ctm {
-    tmvb_ctx* ctx = nullptr;
-    tmvb_corpus* corp = nullptr;
-    int K = 0, KP = 0;
-    int64_t M = 0, V = 0, M_total = 0;
-    bool distributed = false;
-    tmvb_comm* comm = nullptr;         // document-sharded train!: the all-reduce of the packed statistics (not owned)
-    int nslot = 1;                     // topic slots per lane of the lane = topic kernels ((K + 63) / 64)
+struct tmvb_ctm : tmvb_model_base {       // d_stats: S (K*V) | sum_lambda (K) | sum_vsq (K) | scatter (K*K)
     int NB = 2;                        // 32 x 32 tiles per side of the MFMA scatter product
     bool generic = false;              // K > 60: ctm_estep_generic_kernel
     bool generic_cg = false;           // ... in its conjugate-gradient form (d_cg_iters then carries its trip counts)
     float* d_beta[2] = {nullptr, nullptr};
     float* d_beta_pad = nullptr;       // TMVB_CTM_ROWPAD: [V][64] copy of beta (KP = 52) for the lane-per-document kernel's row gather
     int cur = 0;
-    float* d_stats = nullptr;          // S (K*V) | sum_lambda (K) | sum_vsq (K) | scatter (K*K)
-    bool own_stats = true;
     float* d_lambda = nullptr; float* d_lambda_old = nullptr; float* d_vsq = nullptr; float* d_logzeta = nullptr;
     float* d_wtok = nullptr; float* d_E = nullptr; float* d_ts_partial = nullptr;
     double* d_sigma_work = nullptr; double* d_sigma_work_s = nullptr;   // K > 128: [K][K] workspaces of the sigma inversion (and of the staged one)
@@ -1443,13 +1436,11 @@ struct tmvb_ctm {
     float cg_tol = 1e-4f, cg_abs = 0.05f;   // CG exit: relative residual, and the fraction of ntol it may stop at (TMVB_CTM_CG_TOL / _ABS)
     double* d_sigma = nullptr; double* d_invsigma = nullptr; double* d_mu = nullptr; double* d_logdet = nullptr;
     float* d_scatter_partial = nullptr; int n_scatter_waves = 0; int64_t docs_per_wave = 0;
-    uint8_t* d_sweeps = nullptr; int32_t* d_doc_order = nullptr;
-    double* d_partial = nullptr; double* d_partial_docs = nullptr; double* d_partial_docs2 = nullptr; double* d_rowsum = nullptr; double* d_doc_val = nullptr; double* d_elbo = nullptr;
+    int32_t* d_doc_order = nullptr;
+    double* d_partial = nullptr; double* d_partial_docs = nullptr; double* d_partial_docs2 = nullptr; double* d_rowsum = nullptr; double* d_doc_val = nullptr;
     unsigned long long* d_newton = nullptr; int* d_status = nullptr;
-    double elbo = 0.0;
+    unsigned long long* d_wave_log = nullptr; size_t wave_log_cap = 0;   // TMVB_CTM_WAVE_LOG (diagnostics): per-item records of the last lane-per-document launch
     std::vector<tmvb_bucket> buckets;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    bool timed = false;
     bool tail_fresh = false;           // the statistics tail (sum lambda | sum vsq | scatter) was computed by the last tmvb_ctm_estep
     // ... and, one process, behind it on the same side stream: update_sigma!'s result into staging buffers (tmvb_ctm_update_sigma then
     // only copies them over -- the 115 us fp64 inversion leaves the iteration's critical path) and the regrouping of the documents for
@@ -1463,10 +1454,8 @@ struct tmvb_ctm {
     // decomposed update_elbo! (as LDA's, tmvb_lda.hip): an iteration that train! will check (or every one, TMVB_CTM_ELBO_PARTS=2 at tmvb_ctm_create;
     // 0: never) has its statistics pass leave sum c log2 s per chunk (d_logz), its document kernels sum_i (phi counts)_i (lambda_i - lambda_old_i) per
     // document (d_pdot), and update_beta! sum S (log(beta_new + eps) - log beta_old) (d_pw_partial); update_elbo! then skips its token loop.
-    int parts_env = 1; bool want_parts = false;
     double* d_logz = nullptr; size_t logz_cap = 0; int64_t n_logz = 0; float* d_pdot = nullptr; double* d_pw_partial = nullptr; int pw_blocks = 0;
     bool logz_valid = false, stats_fresh = false, pw_valid = false;
-    int elbo_form = 0; bool force_walk = false;
     // stochastic training (tmvb_ctm_svi.hip): a batch handle reads the globals proper of the driver's first batch handle instead of its own
     // (tmvb_ctm_share_globals); it then owns none of them
     bool own_globals = true;
@@ -1483,54 +1472,8 @@ static bool ctm_kp_supported(int kp) { return kp >= 4 && kp <= 52 && kp % 8 == 4
 extern "C" int tmvb_ctm_destroy(tmvb_ctm* h)
 {
     if (!h) return TMVB_OK;
-    if (h->ctx) (void)hipSetDevice(h->ctx->device);
-    if (h->own_globals) {
-        (void)hipFree(h->d_beta[0]); (void)hipFree(h->d_beta[1]); (void)hipFree(h->d_invsigma_f); (void)hipFree(h->d_mu_f);
-        (void)hipFree(h->d_sigma); (void)hipFree(h->d_invsigma); (void)hipFree(h->d_mu); (void)hipFree(h->d_logdet); (void)hipFree(h->d_status);
-    }
-    (void)hipFree(h->d_beta_pad);
-    if (h->own_stats) (void)hipFree(h->d_stats);
-    (void)hipFree(h->d_lambda); (void)hipFree(h->d_lambda_old); (void)hipFree(h->d_vsq); (void)hipFree(h->d_logzeta);
-    (void)hipFree(h->d_sigma_work); (void)hipFree(h->d_sigma_work_s);
-    (void)hipFree(h->d_wtok); (void)hipFree(h->d_E); (void)hipFree(h->d_ts_partial);
-    (void)hipFree(h->d_q_S); (void)hipFree(h->d_q_sd); (void)hipFree(h->d_q_mu);
-    (void)hipFree(h->d_bt_sdiag); (void)hipFree(h->d_bt_muf); (void)hipFree(h->d_cg_iters); (void)hipFree(h->d_doc_newton); (void)hipFree(h->d_doc_order0); (void)hipFree(h->d_doc_order_q); (void)hipFree(h->d_wave_keys);
-    (void)hipFree(h->d_scatter_partial); (void)hipFree(h->d_sweeps); (void)hipFree(h->d_doc_order);
-    (void)hipFree(h->d_partial); (void)hipFree(h->d_partial_docs); (void)hipFree(h->d_partial_docs2); (void)hipFree(h->d_rowsum); (void)hipFree(h->d_doc_val); (void)hipFree(h->d_elbo);
-    (void)hipFree(h->d_newton); (void)hipFree(h->d_logz); (void)hipFree(h->d_pdot); (void)hipFree(h->d_pw_partial);
-    if (h->ev0) (void)hipEventDestroy(h->ev0);
-    if (h->ev1) (void)hipEventDestroy(h->ev1);
-    if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
-    if (h->ev_spec) (void)hipEventDestroy(h->ev_spec);
-    if (h->ev_spec2) (void)hipEventDestroy(h->ev_spec2);
-    (void)hipFree(h->d_sigma_s); (void)hipFree(h->d_invsigma_s); (void)hipFree(h->d_invsigma_f_s); (void)hipFree(h->d_logdet_s); (void)hipFree(h->d_status_s);
-    for (int a = 0; a < tmvb_ctm::NAUX; ++a) {
-        if (h->ev_join[a]) (void)hipEventDestroy(h->ev_join[a]);
-        tmvb_release_stream(h->aux[a]); h->aux[a] = nullptr;        // pooled streams stay (tmvb_pool_stream)
-    }
+    h->release();
     delete h;
-    return TMVB_OK;
-}
-
-static int ctm_upload_beta(tmvb_ctm* h, float* dst, const double* src)
-{
-    const size_t K = h->K, KP = h->KP, V = h->V;
-    std::vector<float> tmp(V * KP + 4, 0.0f);
-    for (size_t j = 0; j < V; ++j)
-        for (size_t i = 0; i < K; ++i) tmp[j * KP + i] = (float)src[j * K + i];
-    TMVB_HIP(hipMemcpyAsync(dst, tmp.data(), tmp.size() * sizeof(float), hipMemcpyHostToDevice, h->ctx->stream));
-    TMVB_HIP(hipStreamSynchronize(h->ctx->stream));
-    return TMVB_OK;
-}
-
-static int ctm_download_beta(tmvb_ctm* h, double* dst, const float* src)
-{
-    const size_t K = h->K, KP = h->KP, V = h->V;
-    std::vector<float> tmp(V * KP);
-    TMVB_HIP(hipMemcpyAsync(tmp.data(), src, tmp.size() * sizeof(float), hipMemcpyDeviceToHost, h->ctx->stream));
-    TMVB_HIP(hipStreamSynchronize(h->ctx->stream));
-    for (size_t j = 0; j < V; ++j)
-        for (size_t i = 0; i < K; ++i) dst[j * K + i] = (double)tmp[j * KP + i];
     return TMVB_OK;
 }
 
@@ -1561,22 +1504,22 @@ extern "C" int tmvb_ctm_create(tmvb_ctx* ctx, tmvb_corpus* corp, int32_t K, tmvb
     h->docs_per_wave = 256;
     h->n_scatter_waves = (int)std::max<int64_t>(1, (h->M + h->docs_per_wave - 1) / h->docs_per_wave);
     int rc;
-    if ((rc = dmalloc(&h->d_beta[0], KPV)) || (rc = dmalloc(&h->d_beta[1], KPV)) || (rc = dmalloc(&h->d_stats, (size_t)h->stats_len())) ||
-        (rc = dmalloc(&h->d_lambda, KM)) || (rc = dmalloc(&h->d_lambda_old, KM)) || (rc = dmalloc(&h->d_vsq, KM)) ||
-        (rc = dmalloc(&h->d_logzeta, (size_t)h->M)) || (rc = dmalloc(&h->d_wtok, (size_t)corp->info.nnz)) ||
-        (rc = dmalloc(&h->d_E, (size_t)h->KP * h->M + 4)) || (rc = tmvb_corpus_term_index(corp)) ||
-        (rc = dmalloc(&h->d_ts_partial, (size_t)corp->term_index.n_slots * (K + 1))) ||
-        (rc = dmalloc(&h->d_invsigma_f, (size_t)h->KP * h->KP + 64)) || (rc = dmalloc(&h->d_mu_f, K)) ||
-        (rc = dmalloc(&h->d_sigma, (size_t)K * K)) || (rc = dmalloc(&h->d_invsigma, (size_t)K * K)) || (rc = dmalloc(&h->d_mu, K)) ||
-        (rc = dmalloc(&h->d_sigma_s, (size_t)K * K)) || (rc = dmalloc(&h->d_invsigma_s, (size_t)K * K)) || (rc = dmalloc(&h->d_invsigma_f_s, (size_t)h->KP * h->KP + 64)) ||
-        (rc = dmalloc(&h->d_logdet_s, 1)) || (rc = dmalloc(&h->d_status_s, 1)) ||
-        (rc = dmalloc(&h->d_logdet, 1)) || (rc = dmalloc(&h->d_scatter_partial, (size_t)h->n_scatter_waves * h->NB * h->NB * 1024)) ||
-        (rc = dmalloc(&h->d_sweeps, (size_t)h->M)) || (rc = dmalloc(&h->d_doc_order, (size_t)h->M)) ||
-        (rc = dmalloc(&h->d_partial, (size_t)TMVB_REDUCE_BLOCKS * K)) || (rc = dmalloc(&h->d_partial_docs, (size_t)TMVB_REDUCE_BLOCKS * K)) || (rc = dmalloc(&h->d_partial_docs2, (size_t)TMVB_REDUCE_BLOCKS * K)) ||
-        (rc = dmalloc(&h->d_rowsum, K)) ||
-        (rc = dmalloc(&h->d_doc_val, (size_t)h->M)) || (rc = dmalloc(&h->d_pdot, (size_t)std::max<int64_t>(h->M, 1))) || (rc = dmalloc(&h->d_pw_partial, 2048)) || (rc = dmalloc(&h->d_elbo, 1)) || (rc = dmalloc(&h->d_newton, 1)) ||
-        (rc = dmalloc(&h->d_status, 1)) ||
-        (K > 128 && ((rc = dmalloc(&h->d_sigma_work, (size_t)K * K)) || (rc = dmalloc(&h->d_sigma_work_s, (size_t)K * K))))) {
+    if ((rc = h->mem.alloc(&h->d_beta[0], KPV)) || (rc = h->mem.alloc(&h->d_beta[1], KPV)) || (rc = h->mem.alloc(&h->d_stats, (size_t)h->stats_len())) ||
+        (rc = h->mem.alloc(&h->d_lambda, KM)) || (rc = h->mem.alloc(&h->d_lambda_old, KM)) || (rc = h->mem.alloc(&h->d_vsq, KM)) ||
+        (rc = h->mem.alloc(&h->d_logzeta, (size_t)h->M)) || (rc = h->mem.alloc(&h->d_wtok, (size_t)corp->info.nnz)) ||
+        (rc = h->mem.alloc(&h->d_E, (size_t)h->KP * h->M + 4)) || (rc = tmvb_corpus_term_index(corp)) ||
+        (rc = h->mem.alloc(&h->d_ts_partial, (size_t)corp->term_index.n_slots * (K + 1))) ||
+        (rc = h->mem.alloc(&h->d_invsigma_f, (size_t)h->KP * h->KP + 64)) || (rc = h->mem.alloc(&h->d_mu_f, K)) ||
+        (rc = h->mem.alloc(&h->d_sigma, (size_t)K * K)) || (rc = h->mem.alloc(&h->d_invsigma, (size_t)K * K)) || (rc = h->mem.alloc(&h->d_mu, K)) ||
+        (rc = h->mem.alloc(&h->d_sigma_s, (size_t)K * K)) || (rc = h->mem.alloc(&h->d_invsigma_s, (size_t)K * K)) || (rc = h->mem.alloc(&h->d_invsigma_f_s, (size_t)h->KP * h->KP + 64)) ||
+        (rc = h->mem.alloc(&h->d_logdet_s, 1)) || (rc = h->mem.alloc(&h->d_status_s, 1)) ||
+        (rc = h->mem.alloc(&h->d_logdet, 1)) || (rc = h->mem.alloc(&h->d_scatter_partial, (size_t)h->n_scatter_waves * h->NB * h->NB * 1024)) ||
+        (rc = h->mem.alloc(&h->d_sweeps, (size_t)h->M)) || (rc = h->mem.alloc(&h->d_doc_order, (size_t)h->M)) ||
+        (rc = h->mem.alloc(&h->d_partial, (size_t)TMVB_REDUCE_BLOCKS * K)) || (rc = h->mem.alloc(&h->d_partial_docs, (size_t)TMVB_REDUCE_BLOCKS * K)) || (rc = h->mem.alloc(&h->d_partial_docs2, (size_t)TMVB_REDUCE_BLOCKS * K)) ||
+        (rc = h->mem.alloc(&h->d_rowsum, K)) ||
+        (rc = h->mem.alloc(&h->d_doc_val, (size_t)h->M)) || (rc = h->mem.alloc(&h->d_pdot, (size_t)std::max<int64_t>(h->M, 1))) || (rc = h->mem.alloc(&h->d_pw_partial, 2048)) || (rc = h->mem.alloc(&h->d_elbo, 1)) || (rc = h->mem.alloc(&h->d_newton, 1)) ||
+        (rc = h->mem.alloc(&h->d_status, 1)) ||
+        (K > 128 && ((rc = h->mem.alloc(&h->d_sigma_work, (size_t)K * K)) || (rc = h->mem.alloc(&h->d_sigma_work_s, (size_t)K * K))))) {
         return rc;
     }
     {
@@ -1589,9 +1532,9 @@ extern "C" int tmvb_ctm_create(tmvb_ctx* ctx, tmvb_corpus* corp, int32_t K, tmvb
                    tmvb_env_on("TMVB_CTM_BATCH", true);
         if (const char* t = tmvb_env_str("TMVB_CTM_CG_TOL")) h->cg_tol = std::max(1e-7f, (float)atof(t));
         if (const char* t = tmvb_env_str("TMVB_CTM_CG_ABS")) h->cg_abs = std::max(0.0f, (float)atof(t));
-        if ((rc = dmalloc(&h->d_bt_sdiag, 64)) || (rc = dmalloc(&h->d_bt_muf, 64)) || (rc = dmalloc(&h->d_cg_iters, 16)) ||
-            (rc = dmalloc(&h->d_q_S, (size_t)4 * (((size_t)h->KP * h->KP / 4 + 15) / 16 * 16) + 64)) || (rc = dmalloc(&h->d_q_sd, 64)) || (rc = dmalloc(&h->d_q_mu, 64)) ||
-            (rc = dmalloc(&h->d_doc_newton, (size_t)std::max<int64_t>(h->M, 1))) || (rc = dmalloc(&h->d_doc_order0, (size_t)std::max<int64_t>(h->M, 1))) || (rc = dmalloc(&h->d_doc_order_q, (size_t)std::max<int64_t>(h->M, 1))) || (rc = dmalloc(&h->d_wave_keys, CTM_WAVESORT_MAX)))
+        if ((rc = h->mem.alloc(&h->d_bt_sdiag, 64)) || (rc = h->mem.alloc(&h->d_bt_muf, 64)) || (rc = h->mem.alloc(&h->d_cg_iters, 16)) ||
+            (rc = h->mem.alloc(&h->d_q_S, (size_t)4 * (((size_t)h->KP * h->KP / 4 + 15) / 16 * 16) + 64)) || (rc = h->mem.alloc(&h->d_q_sd, 64)) || (rc = h->mem.alloc(&h->d_q_mu, 64)) ||
+            (rc = h->mem.alloc(&h->d_doc_newton, (size_t)std::max<int64_t>(h->M, 1))) || (rc = h->mem.alloc(&h->d_doc_order0, (size_t)std::max<int64_t>(h->M, 1))) || (rc = h->mem.alloc(&h->d_doc_order_q, (size_t)std::max<int64_t>(h->M, 1))) || (rc = h->mem.alloc(&h->d_wave_keys, CTM_WAVESORT_MAX)))
             return rc;
         // regrouping pays when a chunk of the length-sorted order is still homogeneous in length: corpora of >= 4 chunks
         h->reorder = h->batch && h->M >= 4 * CTM_REORDER_CHUNK && tmvb_env_on("TMVB_CTM_REORDER", true);
@@ -1623,15 +1566,10 @@ extern "C" int tmvb_ctm_create(tmvb_ctx* ctx, tmvb_corpus* corp, int32_t K, tmvb
     TMVB_HIP(hipMemsetAsync(h->d_status, 0, sizeof(int), ctx->stream));
     TMVB_HIP(hipMemsetAsync(h->d_beta[0], 0, KPV * sizeof(float), ctx->stream));
     TMVB_HIP(hipMemsetAsync(h->d_beta[1], 0, KPV * sizeof(float), ctx->stream));
-    TMVB_HIP(hipEventCreate(&h->ev0));
-    TMVB_HIP(hipEventCreate(&h->ev1));
-    TMVB_HIP(hipEventCreateWithFlags(&h->ev_fork, tmvb_event_flags()));
-    TMVB_HIP(hipEventCreateWithFlags(&h->ev_spec, tmvb_event_flags()));
-    TMVB_HIP(hipEventCreateWithFlags(&h->ev_spec2, tmvb_event_flags()));
+    if ((rc = h->mem.event(&h->ev0, hipEventDefault)) || (rc = h->mem.event(&h->ev1, hipEventDefault)) || (rc = h->mem.event(&h->ev_fork, tmvb_event_flags())) ||
+        (rc = h->mem.event(&h->ev_spec, tmvb_event_flags())) || (rc = h->mem.event(&h->ev_spec2, tmvb_event_flags()))) return rc;
     for (int a = 0; a < tmvb_ctm::NAUX; ++a) {
-        h->aux[a] = tmvb_pool_stream(ctx->device, 1 + a);
-        TMVB_REQUIRE(h->aux[a] != nullptr, TMVB_EHIP, "hipStreamCreate failed");
-        TMVB_HIP(hipEventCreateWithFlags(&h->ev_join[a], tmvb_event_flags()));
+        if ((rc = h->mem.aux(&h->aux[a], ctx->device, 1 + a, false)) || (rc = h->mem.event(&h->ev_join[a], tmvb_event_flags()))) return rc;
     }
     TMVB_HIP(hipStreamSynchronize(ctx->stream));
     // constructor state, src/CTM.jl:37-48: mu = 0, sigma = invsigma = I, lambda = 0, vsq = 1, logzeta = 0.5; beta uniform
@@ -1696,10 +1634,10 @@ extern "C" int tmvb_ctm_set_state(tmvb_ctm* h, const double* mu, const double* s
         TMVB_HIP(hipStreamSynchronize(ctx->stream));
     }
     if (beta) {
-        if ((rc = ctm_upload_beta(h, h->d_beta[h->cur], beta))) return rc;
-        if (!beta_old && (rc = ctm_upload_beta(h, h->d_beta[h->cur ^ 1], beta))) return rc;
+        if ((rc = tmvb_model_upload_beta(h, h->d_beta[h->cur], beta))) return rc;
+        if (!beta_old && (rc = tmvb_model_upload_beta(h, h->d_beta[h->cur ^ 1], beta))) return rc;
     }
-    if (beta_old && (rc = ctm_upload_beta(h, h->d_beta[h->cur ^ 1], beta_old))) return rc;
+    if (beta_old && (rc = tmvb_model_upload_beta(h, h->d_beta[h->cur ^ 1], beta_old))) return rc;
     if (lambda) {
         if ((rc = upload_f32(ctx, h->d_lambda, lambda, KM))) return rc;
         if (!lambda_old && (rc = upload_f32(ctx, h->d_lambda_old, lambda, KM))) return rc;
@@ -1727,8 +1665,8 @@ extern "C" int tmvb_ctm_get_state(tmvb_ctm* h, double* mu, double* sigma, double
     if (sigma) TMVB_HIP(hipMemcpyAsync(sigma, h->d_sigma, K * K * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     if (invsigma) TMVB_HIP(hipMemcpyAsync(invsigma, h->d_invsigma, K * K * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     TMVB_HIP(hipStreamSynchronize(ctx->stream));
-    if (beta && (rc = ctm_download_beta(h, beta, h->d_beta[h->cur]))) return rc;
-    if (beta_old && (rc = ctm_download_beta(h, beta_old, h->d_beta[h->cur ^ 1]))) return rc;
+    if (beta && (rc = tmvb_model_download_beta(h, beta, h->d_beta[h->cur]))) return rc;
+    if (beta_old && (rc = tmvb_model_download_beta(h, beta_old, h->d_beta[h->cur ^ 1]))) return rc;
     if (lambda && (rc = download_f32(ctx, lambda, h->d_lambda, KM))) return rc;
     if (lambda_old && (rc = download_f32(ctx, lambda_old, h->d_lambda_old, KM))) return rc;
     if (vsq && (rc = download_f32(ctx, vsq, h->d_vsq, KM))) return rc;
@@ -1837,8 +1775,8 @@ static int ctm_launch_quad(tmvb_ctm* h, const CtmParams& p, double ntol)
     CtmBatchArgs ba;
     ba.p = p; ba.p.doc_order = h->queue_sorted ? h->d_doc_order_q : p.doc_order + h->n_long; ba.p.doc_newton = h->d_doc_newton; ba.tb = tb; ba.M = Mb;
     if (!h->d_beta_pad || h->beta_pad_cpr != CPR) {
-        (void)hipFree(h->d_beta_pad); h->d_beta_pad = nullptr;
-        int prc = dmalloc(&h->d_beta_pad, (size_t)h->V * CPR * 4 + 64); if (prc) return prc;
+        h->mem.drop(&h->d_beta_pad);
+        int prc = h->mem.alloc(&h->d_beta_pad, (size_t)h->V * CPR * 4 + 64); if (prc) return prc;
         h->beta_pad_cpr = CPR;
     }
     hipLaunchKernelGGL(ctm_rowpad_generic_kernel, dim3((unsigned)((h->V * CPR + 255) / 256)), dim3(256), 0, ctx->stream, (const float4*)p.beta, (float4*)h->d_beta_pad, h->V, LPRv, CPR);
@@ -1893,7 +1831,7 @@ static int ctm_launch_batch(tmvb_ctm* h, const CtmParams& p, double ntol)
     CtmBatchArgs ba;
     ba.p = p; ba.p.doc_order = (h->queue_sorted && !FILT) ? h->d_doc_order_q : p.doc_order + h->n_long; ba.p.doc_newton = h->d_doc_newton; ba.tb = tb; ba.M = Mb;
     if (cb_rowb<52, FILT>::value == 256u && h->KP == 52) {
-        if (!h->d_beta_pad) { int prc = dmalloc(&h->d_beta_pad, (size_t)h->V * 64); if (prc) return prc; }
+        if (!h->d_beta_pad) { int prc = h->mem.alloc(&h->d_beta_pad, (size_t)h->V * 64); if (prc) return prc; }
         hipLaunchKernelGGL(ctm_rowpad_kernel, dim3((unsigned)((h->V * 16 + 255) / 256)), dim3(256), 0, ctx->stream, (const float4*)p.beta, (float4*)h->d_beta_pad, h->V);
         TMVB_HIP(hipGetLastError());
         ba.p.beta = h->d_beta_pad;
@@ -1902,11 +1840,14 @@ static int ctm_launch_batch(tmvb_ctm* h, const CtmParams& p, double ntol)
     static const bool prof = tmvb_env_on("TMVB_CTM_PROF", false);
     // TMVB_CTM_WAVE_LOG=<file> (with TMVB_CTM_PROF=1): per-item start / end / placement of this launch, written after a synchronisation (diagnostics only)
     static const char* wave_log = tmvb_env_str("TMVB_CTM_WAVE_LOG");
-    static unsigned long long* d_wl = nullptr; static size_t wl_cap = 0;
     const bool logging = prof && h->KP == 52 && wave_log;
     if (logging) {
-        if (wl_cap < (size_t)n_items * 4) { (void)hipFree(d_wl); wl_cap = (size_t)n_items * 4; TMVB_HIP(hipMalloc((void**)&d_wl, wl_cap * sizeof(unsigned long long))); }
-        ba.tb.wave_log = d_wl;
+        if (h->wave_log_cap < (size_t)n_items * 4) {
+            h->mem.drop(&h->d_wave_log); h->wave_log_cap = 0;
+            int wrc = h->mem.alloc(&h->d_wave_log, (size_t)n_items * 4); if (wrc) return wrc;
+            h->wave_log_cap = (size_t)n_items * 4;
+        }
+        ba.tb.wave_log = h->d_wave_log;
     }
 #define CTM_BCASE(KPV) case KPV: hipLaunchKernelGGL((ctm_estep_batch_kernel<KPV, false, FILT>), grid, block, lds, ctx->stream, ba); break;
     if (prof && h->KP == 52) hipLaunchKernelGGL((ctm_estep_batch_kernel<52, true, FILT>), grid, block, lds, ctx->stream, ba);
@@ -1916,7 +1857,7 @@ static int ctm_launch_batch(tmvb_ctm* h, const CtmParams& p, double ntol)
     TMVB_HIP(hipGetLastError());
     if (logging) {
         std::vector<unsigned long long> wl((size_t)n_items * 4);
-        TMVB_HIP(hipMemcpyAsync(wl.data(), d_wl, wl.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+        TMVB_HIP(hipMemcpyAsync(wl.data(), h->d_wave_log, wl.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
         TMVB_HIP(hipStreamSynchronize(ctx->stream));
         if (FILE* f = fopen(wave_log, "wb")) { fwrite(wl.data(), sizeof(unsigned long long), wl.size(), f); fclose(f); }
     }
@@ -1946,8 +1887,8 @@ extern "C" int tmvb_ctm_estep(tmvb_ctm* h, int32_t niter, double ntol, int32_t v
     if (collect) {
         const size_t need = (size_t)std::max<int64_t>(h->corp->term_index.n_chunks, 1);
         if (need > h->logz_cap) {
-            (void)hipFree(h->d_logz); h->d_logz = nullptr; h->logz_cap = 0;
-            int arc = dmalloc(&h->d_logz, need);
+            h->mem.drop(&h->d_logz); h->logz_cap = 0;
+            int arc = h->mem.alloc(&h->d_logz, need);
             if (arc) return arc;
             h->logz_cap = need;
         }
@@ -2117,17 +2058,10 @@ extern "C" int tmvb_ctm_stats(tmvb_ctm* h, void** dev_ptr, int64_t* n_f32)
 
 extern "C" int tmvb_ctm_bind_stats(tmvb_ctm* h, void* dev_ptr, int64_t n_f32)
 {
-    TMVB_REQUIRE(h && dev_ptr, TMVB_EINVAL, "tmvb_ctm_bind_stats: NULL argument");
-    TMVB_REQUIRE(n_f32 >= h->stats_len(), TMVB_ESHAPE, "tmvb_ctm_bind_stats: buffer holds %lld floats, need %lld", (long long)n_f32, (long long)h->stats_len());
-    TMVB_HIP(hipSetDevice(h->ctx->device));
-    h->sigma_staged = false;                                    // as tmvb_ctm_stats: the tail leaves the library's hands
-    { int jrc = ctm_join_spec(h); if (jrc) return jrc; }
-    TMVB_HIP(hipMemcpyAsync(dev_ptr, h->d_stats, (size_t)h->stats_len() * sizeof(float), hipMemcpyDeviceToDevice, h->ctx->stream));
-    TMVB_HIP(hipStreamSynchronize(h->ctx->stream));
-    if (h->own_stats) (void)hipFree(h->d_stats);
-    h->d_stats = (float*)dev_ptr;
-    h->own_stats = false;
-    return TMVB_OK;
+    return tmvb_model_bind_stats("tmvb_ctm_bind_stats", h, dev_ptr, n_f32, h ? h->stats_len() : 0, [&] {
+        h->sigma_staged = false;                                // as tmvb_ctm_stats: the tail leaves the library's hands
+        return ctm_join_spec(h);
+    });
 }
 
 extern "C" int tmvb_ctm_set_distributed(tmvb_ctm* h, int64_t M_total, int32_t distributed)
@@ -2263,12 +2197,7 @@ extern "C" int tmvb_ctm_update_elbo(tmvb_ctm* h, double* elbo)
     return TMVB_OK;
 }
 
-extern "C" int tmvb_ctm_elbo_form(tmvb_ctm* h, int32_t* form)
-{
-    TMVB_REQUIRE(h && form, TMVB_EINVAL, "tmvb_ctm_elbo_form: NULL argument");
-    *form = h->elbo_form;
-    return TMVB_OK;
-}
+extern "C" int tmvb_ctm_elbo_form(tmvb_ctm* h, int32_t* form) { return tmvb_model_elbo_form("tmvb_ctm_elbo_form", h, form); }
 
 extern "C" int tmvb_ctm_set_comm(tmvb_ctm* h, tmvb_comm* comm, int64_t M_total)
 {
@@ -2280,12 +2209,11 @@ extern "C" int tmvb_ctm_set_comm(tmvb_ctm* h, tmvb_comm* comm, int64_t M_total)
 }
 
 namespace {
-struct CtmTrainOps {
+struct CtmTrainOps : tmvb_base_train_ops<tmvb_ctm> {
     int niter, viter; double ntol, vtol;
     int estep(tmvb_ctm* h) { return tmvb_ctm_estep(h, niter, ntol, viter, vtol); }     // src/CTM.jl:194-205
     int reduce(tmvb_ctm* h) { return tmvb_ctm_reduce_docs(h); }
     int before_allreduce(tmvb_ctm*) { return TMVB_OK; }
-    float* stats(tmvb_ctm* h) { return h->d_stats; }
     int64_t stats_len(tmvb_ctm* h) { return h->stats_len(); }
     int mstep(tmvb_ctm* h)
     {
@@ -2295,22 +2223,6 @@ struct CtmTrainOps {
         return rc;
     }
     int elbo_local(tmvb_ctm* h, double* s, double* once) { *once = 0.0; return tmvb_ctm_update_elbo(h, s); }
-    int elbo_form(tmvb_ctm* h) { return h->elbo_form; }
-    void force_walk(tmvb_ctm* h, bool on, bool doubled = true) { h->force_walk = on; if (!on && doubled) h->elbo_form = 1; }   // (switched off behind the one evaluation that doubled a decomposed one)
-    void will_check(tmvb_ctm* h, bool checked) { h->want_parts = checked; }             // the coming iteration ends in check_elbo!
-    double* elbo_dev(tmvb_ctm* h) { return h->d_elbo; }
-    tmvb_comm* comm(tmvb_ctm* h) { return h->comm; }
-    bool distributed(tmvb_ctm* h) { return h->distributed; }
-    tmvb_ctx* ctx(tmvb_ctm* h) { return h->ctx; }
-    int64_t nnz(tmvb_ctm* h) { return h->corp->info.nnz; }
-    void set_elbo(tmvb_ctm* h, double v) { h->elbo = v; }
-    double get_elbo(tmvb_ctm* h) { return h->elbo; }
-    int finish(tmvb_ctm* h)
-    {
-        TMVB_HIP(hipSetDevice(h->ctx->device));
-        TMVB_HIP(hipStreamSynchronize(h->ctx->stream));
-        return TMVB_OK;
-    }
 };
 }  // namespace
 
@@ -2319,7 +2231,7 @@ extern "C" int tmvb_ctm_train_group(tmvb_ctm* const* hs, int32_t n, int32_t iter
 {
     TMVB_REQUIRE(tol >= 0 && ntol >= 0 && vtol >= 0, TMVB_EINVAL, "tolerance parameters must be nonnegative.");   // src/gpuCTM.jl:489
     TMVB_REQUIRE(iter >= 0 && niter >= 0 && viter >= 0, TMVB_EINVAL, "iteration parameters must be nonnegative."); // :490
-    CtmTrainOps ops{niter, viter, ntol, vtol};
+    CtmTrainOps ops{{}, niter, viter, ntol, vtol};
     return tmvb_train_group_loop("tmvb_ctm_train", hs, n, iter, tol, checkelbo, elbo_traj, iters_done, elbo_baseline, ops);
 }
 
@@ -2348,39 +2260,21 @@ extern "C" int tmvb_ctm_solver_stats(tmvb_ctm* h, int64_t* out9)
     return TMVB_OK;
 }
 
-extern "C" int tmvb_ctm_doc_sweeps(tmvb_ctm* h, uint8_t* out)
-{
-    TMVB_REQUIRE(h && (out || h->M == 0), TMVB_EINVAL, "tmvb_ctm_doc_sweeps: NULL argument");
-    TMVB_HIP(hipSetDevice(h->ctx->device));
-    if (h->M) TMVB_HIP(hipMemcpyAsync(out, h->d_sweeps, (size_t)h->M, hipMemcpyDeviceToHost, h->ctx->stream));
-    TMVB_HIP(hipStreamSynchronize(h->ctx->stream));
-    return TMVB_OK;
-}
+extern "C" int tmvb_ctm_doc_sweeps(tmvb_ctm* h, uint8_t* out) { return tmvb_model_doc_sweeps("tmvb_ctm_doc_sweeps", h, out); }
 
 extern "C" int tmvb_ctm_sweep_hist(tmvb_ctm* h, int64_t* hist, int32_t nbins, int64_t* newton_steps)
 {
-    TMVB_REQUIRE(h && hist && nbins > 0, TMVB_EINVAL, "tmvb_ctm_sweep_hist: bad argument");
-    std::vector<uint8_t> sw((size_t)h->M);
+    const int rc = tmvb_model_sweep_hist("tmvb_ctm_sweep_hist", h, hist, nbins);
+    if (rc || !newton_steps) return rc;
     unsigned long long ns = 0;
-    TMVB_HIP(hipSetDevice(h->ctx->device));
-    if (h->M) TMVB_HIP(hipMemcpyAsync(sw.data(), h->d_sweeps, (size_t)h->M, hipMemcpyDeviceToHost, h->ctx->stream));
     TMVB_HIP(hipMemcpyAsync(&ns, h->d_newton, sizeof(ns), hipMemcpyDeviceToHost, h->ctx->stream));
     TMVB_HIP(hipStreamSynchronize(h->ctx->stream));
-    for (int b = 0; b < nbins; ++b) hist[b] = 0;
-    for (uint8_t s : sw) hist[std::min<int>(s, nbins - 1)]++;
-    if (newton_steps) *newton_steps = (int64_t)ns;
+    *newton_steps = (int64_t)ns;
     return TMVB_OK;
 }
 
-extern "C" int tmvb_ctm_last_estep_ms(tmvb_ctm* h, float* ms)
-{
-    TMVB_REQUIRE(h && ms, TMVB_EINVAL, "tmvb_ctm_last_estep_ms: NULL argument");
-    TMVB_REQUIRE(h->timed, TMVB_EINVAL, "tmvb_ctm_last_estep_ms: no E-step has run");
-    TMVB_HIP(hipSetDevice(h->ctx->device));
-    TMVB_HIP(hipEventSynchronize(h->ev1));
-    TMVB_HIP(hipEventElapsedTime(ms, h->ev0, h->ev1));
-    return TMVB_OK;
-}
+// (CTM records its two timing events at every E-step: no TMVB_ESTEP_TIMING switch to refuse on)
+extern "C" int tmvb_ctm_last_estep_ms(tmvb_ctm* h, float* ms) { return tmvb_model_last_estep_ms("tmvb_ctm_last_estep_ms", h, ms, false); }
 
 // ---- stochastic training (tmvb_ctm_svi.hip): the additive hooks a driver over per-batch handles needs.  None of them is reached from the entry points above.
 // h gives up its own globals proper -- the beta pair, mu, sigma, invsigma (fp64 and the padded fp32 copies), logdet, the inversion's status -- and reads
@@ -2395,8 +2289,8 @@ int tmvb_ctm_share_globals(tmvb_ctm* h, tmvb_ctm* owner)
     TMVB_HIP(hipSetDevice(h->ctx->device));
     { int jrc = ctm_join_spec(h); if (jrc) return jrc; }
     TMVB_HIP(hipStreamSynchronize(h->ctx->stream));
-    (void)hipFree(h->d_beta[0]); (void)hipFree(h->d_beta[1]); (void)hipFree(h->d_invsigma_f); (void)hipFree(h->d_mu_f);
-    (void)hipFree(h->d_sigma); (void)hipFree(h->d_invsigma); (void)hipFree(h->d_mu); (void)hipFree(h->d_logdet); (void)hipFree(h->d_status);
+    h->mem.drop(&h->d_beta[0]); h->mem.drop(&h->d_beta[1]); h->mem.drop(&h->d_invsigma_f); h->mem.drop(&h->d_mu_f);
+    h->mem.drop(&h->d_sigma); h->mem.drop(&h->d_invsigma); h->mem.drop(&h->d_mu); h->mem.drop(&h->d_logdet); h->mem.drop(&h->d_status);
     h->d_beta[0] = owner->d_beta[0]; h->d_beta[1] = owner->d_beta[1]; h->d_invsigma_f = owner->d_invsigma_f; h->d_mu_f = owner->d_mu_f;
     h->d_sigma = owner->d_sigma; h->d_invsigma = owner->d_invsigma; h->d_mu = owner->d_mu; h->d_logdet = owner->d_logdet; h->d_status = owner->d_status;
     h->cur = owner->cur;
@@ -2596,15 +2490,14 @@ __global__ __launch_bounds__(64) void fctm_elbo_doc_parts_kernel(int K, const in
     if (lane == 0) doc_val[d] = tot;
 }
 
-struct tmvb_fctm {
+struct tmvb_fctm : tmvb_elbo_form {        // parts_env: TMVB_FCTM_ELBO_PARTS
     tmvb_ctm* base = nullptr;
+    tmvb_owned mem;                       // the ten buffers of its own; everything else is the base handle's
     int64_t nnz = 0;
     double eta = 0.5;                     // update_eta! is commented out in the reference's train! (src/fCTM.jl:253): a parameter
     float* d_L = nullptr; float* d_kappa = nullptr; float* d_kappa_old = nullptr;
     float* d_tau = nullptr; float* d_tau_old = nullptr; float* d_lse = nullptr;
     float* d_aold = nullptr;              // [nnz] decomposed update_elbo!: the per-token exponent of the last sweep (CtmParams::aold)
-    int parts_env = 1;                    // TMVB_FCTM_ELBO_PARTS at creation: 0 never, 1 the iterations train! checks, 2 every E-step collects
-    bool want_parts = false, force_walk = false; int elbo_form = 0;      // as tmvb_flda
     float* d_stats = nullptr;             // the base handle is bound to this buffer
     double* d_eta_scratch = nullptr; double* d_ksum = nullptr;
     int64_t stats_len() const { return base->stats_len() + base->V; }
@@ -2614,10 +2507,11 @@ struct tmvb_fctm {
 extern "C" int tmvb_fctm_destroy(tmvb_fctm* h)
 {
     if (!h) return TMVB_OK;
-    if (h->base && h->base->ctx) { (void)hipSetDevice(h->base->ctx->device); (void)hipStreamSynchronize(h->base->ctx->stream); }
-    (void)tmvb_ctm_destroy(h->base);      // does not free the bound statistics buffer
-    (void)hipFree(h->d_aold); (void)hipFree(h->d_L); (void)hipFree(h->d_kappa); (void)hipFree(h->d_kappa_old); (void)hipFree(h->d_tau); (void)hipFree(h->d_tau_old);
-    (void)hipFree(h->d_lse); (void)hipFree(h->d_stats); (void)hipFree(h->d_eta_scratch); (void)hipFree(h->d_ksum);
+    if (h->base) {                        // the base first: its release waits for the side streams that may still read this handle's buffers
+        tmvb_ctx* ctx = h->base->ctx;
+        (void)tmvb_ctm_destroy(h->base);  // (does not free the statistics buffer it is bound to: that one is this handle's)
+        h->mem.release(ctx->device, ctx->stream);
+    }
     delete h;
     return TMVB_OK;
 }
@@ -2648,9 +2542,9 @@ extern "C" int tmvb_fctm_create(tmvb_ctx* ctx, tmvb_corpus* corp, int32_t K, tmv
     tmvb_ctm* b = h->base;
     h->nnz = corp->info.nnz;
     const size_t V = (size_t)b->V, NZ = (size_t)h->nnz, KPV = (size_t)b->KP * b->V + 4;
-    if ((rc = dmalloc(&h->d_L, KPV)) || (rc = dmalloc(&h->d_kappa, V)) || (rc = dmalloc(&h->d_kappa_old, V)) || (rc = dmalloc(&h->d_tau, NZ)) ||
-        (rc = dmalloc(&h->d_tau_old, NZ)) || (rc = dmalloc(&h->d_lse, NZ)) || (rc = dmalloc(&h->d_stats, (size_t)h->stats_len())) ||
-        (rc = dmalloc(&h->d_aold, std::max<size_t>(NZ, 1))) || (rc = dmalloc(&h->d_eta_scratch, 1)) || (rc = dmalloc(&h->d_ksum, 1)))
+    if ((rc = h->mem.alloc(&h->d_L, KPV)) || (rc = h->mem.alloc(&h->d_kappa, V)) || (rc = h->mem.alloc(&h->d_kappa_old, V)) || (rc = h->mem.alloc(&h->d_tau, NZ)) ||
+        (rc = h->mem.alloc(&h->d_tau_old, NZ)) || (rc = h->mem.alloc(&h->d_lse, NZ)) || (rc = h->mem.alloc(&h->d_stats, (size_t)h->stats_len())) ||
+        (rc = h->mem.alloc(&h->d_aold, std::max<size_t>(NZ, 1))) || (rc = h->mem.alloc(&h->d_eta_scratch, 1)) || (rc = h->mem.alloc(&h->d_ksum, 1)))
         return rc;
     h->parts_env = tmvb_env_int("TMVB_FCTM_ELBO_PARTS", 1);
     TMVB_HIP(hipMemsetAsync(h->d_stats, 0, (size_t)h->stats_len() * sizeof(float), ctx->stream));
@@ -2845,12 +2739,7 @@ extern "C" int tmvb_fctm_update_elbo(tmvb_fctm* h, double* elbo)
     return TMVB_OK;
 }
 
-extern "C" int tmvb_fctm_elbo_form(tmvb_fctm* h, int32_t* form)
-{
-    TMVB_REQUIRE(h && form, TMVB_EINVAL, "tmvb_fctm_elbo_form: NULL argument");
-    *form = h->elbo_form;
-    return TMVB_OK;
-}
+extern "C" int tmvb_fctm_elbo_form(tmvb_fctm* h, int32_t* form) { return tmvb_model_elbo_form("tmvb_fctm_elbo_form", h, form); }
 
 extern "C" int tmvb_fctm_set_comm(tmvb_fctm* h, tmvb_comm* comm, int64_t M_total)
 {
@@ -2858,13 +2747,14 @@ extern "C" int tmvb_fctm_set_comm(tmvb_fctm* h, tmvb_comm* comm, int64_t M_total
     return tmvb_ctm_set_comm(h->base, comm, M_total);
 }
 
+static inline tmvb_model_base* tmvb_model_core(tmvb_fctm* h) { return h->base; }
+
 namespace {
-struct FctmTrainOps {
+struct FctmTrainOps : tmvb_base_train_ops<tmvb_fctm> {
     int niter, viter; double ntol, vtol;
     int estep(tmvb_fctm* h) { return tmvb_fctm_estep(h, niter, ntol, viter, vtol); }   // src/fCTM.jl:233-248
     int reduce(tmvb_fctm* h) { return tmvb_fctm_reduce_docs(h); }
     int before_allreduce(tmvb_fctm*) { return TMVB_OK; }
-    float* stats(tmvb_fctm* h) { return h->d_stats; }
     int64_t stats_len(tmvb_fctm* h) { return h->stats_len(); }
     int mstep(tmvb_fctm* h)
     {
@@ -2874,22 +2764,6 @@ struct FctmTrainOps {
         return rc;
     }
     int elbo_local(tmvb_fctm* h, double* s, double* once) { *once = 0.0; return tmvb_fctm_update_elbo(h, s); }
-    int elbo_form(tmvb_fctm* h) { return h->elbo_form; }
-    void force_walk(tmvb_fctm* h, bool on, bool doubled = true) { h->force_walk = on; if (!on && doubled) h->elbo_form = 1; }   // (as LdaTrainOps)
-    void will_check(tmvb_fctm* h, bool checked) { h->want_parts = checked; }
-    double* elbo_dev(tmvb_fctm* h) { return h->base->d_elbo; }
-    tmvb_comm* comm(tmvb_fctm* h) { return h->base->comm; }
-    bool distributed(tmvb_fctm* h) { return h->base->distributed; }
-    tmvb_ctx* ctx(tmvb_fctm* h) { return h->base->ctx; }
-    int64_t nnz(tmvb_fctm* h) { return h->nnz; }
-    void set_elbo(tmvb_fctm* h, double v) { h->base->elbo = v; }
-    double get_elbo(tmvb_fctm* h) { return h->base->elbo; }
-    int finish(tmvb_fctm* h)
-    {
-        TMVB_HIP(hipSetDevice(h->base->ctx->device));
-        TMVB_HIP(hipStreamSynchronize(h->base->ctx->stream));
-        return TMVB_OK;
-    }
 };
 }  // namespace
 
@@ -2898,7 +2772,7 @@ extern "C" int tmvb_fctm_train_group(tmvb_fctm* const* hs, int32_t n, int32_t it
 {
     TMVB_REQUIRE(tol >= 0 && ntol >= 0 && vtol >= 0, TMVB_EINVAL, "tolerance parameters must be nonnegative.");   // src/fCTM.jl:228
     TMVB_REQUIRE(iter >= 0 && niter >= 0 && viter >= 0, TMVB_EINVAL, "iteration parameters must be nonnegative."); // :229
-    FctmTrainOps ops{niter, viter, ntol, vtol};
+    FctmTrainOps ops{{}, niter, viter, ntol, vtol};
     return tmvb_train_group_loop("tmvb_fctm_train", hs, n, iter, tol, checkelbo, elbo_traj, iters_done, elbo_baseline, ops);
 }
 

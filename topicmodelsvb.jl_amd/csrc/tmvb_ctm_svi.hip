@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "tmvb_internal.h"
+#include "tmvb_handle.h"
 #include "tmvb_common_kernels.h"
 #include "tmvb_svi_kernels.h"
 
@@ -81,6 +82,7 @@ struct tmvb_ctm_svi {
     bool timing = false;               // TMVB_ESTEP_TIMING=1 at create: four events per step of the last run
     std::vector<hipEvent_t> ev;
     int64_t timed_steps = 0;
+    tmvb_owned mem;                    // the driver's own buffers and events (tmvb_handle.h)
     size_t T() const { return 2 * (size_t)K + (size_t)K * (size_t)K; }
 };
 
@@ -90,9 +92,7 @@ extern "C" int tmvb_ctm_svi_destroy(tmvb_ctm_svi* h)
     if (h->ctx) { (void)hipSetDevice(h->ctx->device); (void)hipDeviceSynchronize(); }       // the handles' side streams included
     for (size_t b = h->hs.size(); b-- > 0;) (void)tmvb_ctm_destroy(h->hs[b]);               // the first handle owns what the others share: last
     for (tmvb_corpus* c : h->corps) (void)tmvb_corpus_destroy(c);
-    (void)hipFree(h->d_sb); (void)hipFree(h->d_sbar); (void)hipFree(h->d_tbar[0]); (void)hipFree(h->d_tbar[1]);
-    (void)hipFree(h->d_mref[0]); (void)hipFree(h->d_mref[1]); (void)hipFree(h->d_partial);
-    for (hipEvent_t e : h->ev) if (e) (void)hipEventDestroy(e);
+    if (h->ctx) h->mem.release(h->ctx->device, h->ctx->stream);
     delete h;
     return TMVB_OK;
 }
@@ -135,8 +135,8 @@ extern "C" int tmvb_ctm_svi_create(tmvb_ctx* ctx, int64_t M, int64_t V, const in
     }
     const size_t KV = (size_t)K * (size_t)V, T = h->T();
     const size_t nbmax = std::max<size_t>(SVI_BLEND_BLOCKS, ((size_t)K + SVI_WG - 1) / SVI_WG);
-    if ((rc = dmalloc(&h->d_sb, KV + T)) || (rc = dmalloc(&h->d_sbar, KV)) || (rc = dmalloc(&h->d_tbar[0], T)) || (rc = dmalloc(&h->d_tbar[1], T)) ||
-        (rc = dmalloc(&h->d_mref[0], (size_t)K)) || (rc = dmalloc(&h->d_mref[1], (size_t)K)) || (rc = dmalloc(&h->d_partial, nbmax * K))) return rc;
+    if ((rc = h->mem.alloc(&h->d_sb, KV + T)) || (rc = h->mem.alloc(&h->d_sbar, KV)) || (rc = h->mem.alloc(&h->d_tbar[0], T)) || (rc = h->mem.alloc(&h->d_tbar[1], T)) ||
+        (rc = h->mem.alloc(&h->d_mref[0], (size_t)K)) || (rc = h->mem.alloc(&h->d_mref[1], (size_t)K)) || (rc = h->mem.alloc(&h->d_partial, nbmax * K))) return rc;
     TMVB_HIP(hipMemsetAsync(h->d_sb, 0, (KV + T) * sizeof(float), ctx->stream));
     TMVB_HIP(hipMemsetAsync(h->d_sbar, 0, KV * sizeof(float), ctx->stream));
     for (int q = 0; q < 2; ++q) {
@@ -328,7 +328,7 @@ extern "C" int tmvb_ctm_svi_run(tmvb_ctm_svi* h, const int32_t* batches, int64_t
     if (h->timing) {
         while ((int64_t)h->ev.size() < 4 * n) {
             hipEvent_t e = nullptr;
-            TMVB_HIP(hipEventCreateWithFlags(&e, hipEventDisableSystemFence));
+            if ((rc = h->mem.event(&e, hipEventDisableSystemFence))) return rc;
             h->ev.push_back(e);
         }
         h->timed_steps = 0;

@@ -28,6 +28,8 @@
 #define TMVB_CTPF_XI_RATE(bet, vav) (vav)
 #endif
 #include "tmvb_train.h"
+#include "tmvb_handle.h"
+#include "tmvb_model.h"
 #include "tmvb_regtile.h"
 #include "tmvb_gridtile.h"
 
@@ -1324,25 +1326,19 @@ __global__ __launch_bounds__(1024) void ctpf_elbo_final_parts_kernel(const doubl
 }
 
 // ------------------------------------------------------------------------------ host side
-struct tmvb_ctpf {
-    tmvb_ctx* ctx = nullptr;
-    tmvb_corpus* corp = nullptr;
-    int K = 0, KP = 0, nslot = 1;
-    int64_t M = 0, V = 0, U = 0;
-    bool distributed = false;
-    tmvb_comm* comm = nullptr;          // document-sharded train!: the all-reduce of the packed statistics (not owned)
+struct tmvb_ctpf : tmvb_model_base {     // d_stats: alef_stats (K*V) | he_stats (K*U) | sum_gimel (K) | sum_zayin (K)
+    int64_t U = 0;
     double hyper[8] = {0.1, 0.1, 0.1, 0.1, 0.1, 0.1, 0.1, 0.1};   // a..h, src/CTPF.jl:81
     float* d_alef = nullptr; float* d_alef_old = nullptr;          // [V][K] dense
     float* d_he = nullptr; float* d_he_old = nullptr;              // [U][K] dense
     float* d_TA = nullptr; float* d_TH = nullptr;                  // padded tables
-    float* d_stats = nullptr; bool own_stats = true;               // alef_stats (K*V) | he_stats (K*U) | sum_gimel (K) | sum_zayin (K)
     double* d_rates = nullptr; float* d_lrates = nullptr;          // [8][K], [4][K]
     double* d_lrates_d = nullptr;                                  // [8][K] log(rates) in fp64 for update_elbo! (filled per call)
     bool rs_fresh = false;                                         // d_rs_alef / d_rs_he are the row sums of the current alef / he
     // decomposed update_elbo! (ctpf_elbo_doc_parts_kernel): TMVB_CTPF_ELBO_PARTS at creation -- 1 (default) the iterations train! will check, 2 every E-step,
     // 0 never.  A collecting E-step leaves the softmax shifts (d_shift) and the statistics passes' log-normaliser sums (d_logz: term chunks, then reader chunks).
     int lds_limit = -1; int elbo_lds_set = 0;                      // the device's per-workgroup LDS limit (read once); dynamic-LDS attribute already set
-    int parts_env = 1; bool want_parts = false; bool logz_valid = false; int msteps_after = 0; int elbo_form = 0; bool force_walk = false;
+    bool logz_valid = false; int msteps_after = 0;
     float* d_shift = nullptr; double* d_logz = nullptr; int64_t n_logz = 0; double* d_crd = nullptr;
     static constexpr int ELBO = 0;                                 // aux[0]: ctpf_elbo_doc_parts_kernel's stream (enqueued by the collecting E-step behind the join of
                                                                    // the document kernels: aux[0] is idle by then.  aux[2] landed on the context stream's own hardware
@@ -1355,21 +1351,17 @@ struct tmvb_ctpf {
     int estride = 0;                                                // row stride of d_E1 / d_E2 (CtpfParams::estride)
     bool e_padded = true;                                           // rows of KP (or 64) floats with zero pads; false: dense K floats (KP / 4 > 64)
     float* d_ts_partial = nullptr; float* d_ts_partial2 = nullptr;   // multi-chunk partials of the term / reader statistics passes
-    uint8_t* d_sweeps = nullptr; int32_t* d_doc_order = nullptr;
-    double* d_doc_val = nullptr; double* d_elbo_partial = nullptr; double* d_elbo = nullptr;
+    int32_t* d_doc_order = nullptr;
+    double* d_doc_val = nullptr; double* d_elbo_partial = nullptr;
     // fast update_elbo!: per-call tables exp(psi(X_old)) / psi(X) - psi(X_old) of both shape matrices (allocated at the first call)
     // and the per-document constants sum lgamma(count + 1) + sum lgamma(rating + 1)
     float* d_TAo = nullptr; float* d_DA = nullptr; float* d_THo = nullptr; float* d_DH = nullptr; double* d_lg_doc = nullptr;
     double* d_partial = nullptr; double* d_partial2 = nullptr; double* d_rs_alef = nullptr; double* d_rs_he = nullptr; double* d_sum_g = nullptr; double* d_sum_z = nullptr;
-    double elbo = 0.0;
     int* d_topic_of_lane = nullptr;     // register-tile kernel: topic owned by each lane after the reduce-scatter
     int* d_grid_topic_of_lane = nullptr;   // grid-tile kernel (tmvb_gridtile.h): the same for its 16-lane reduce-scatter
     bool grid_path = false;             // KP <= 60: documents of <= 512 terms and <= 512 readers use the grid-tile kernels (ctpf_estep_grid_*_kernel)
     bool reg_path = false;              // KP = 4 * odd <= 60: short documents (<= 128 terms, <= 64 readers) use ctpf_estep_reg_kernel
     std::vector<tmvb_bucket> buckets;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    bool timed = false;
-    bool timing = false;               // TMVB_ESTEP_TIMING=1 (read at creation): record the events behind tmvb_ctpf_last_estep_ms
     static constexpr int NAUX = 4;
     hipStream_t aux[NAUX] = {nullptr, nullptr, nullptr, nullptr};
     hipEvent_t ev_fork = nullptr, ev_join[NAUX] = {nullptr, nullptr, nullptr, nullptr};
@@ -1383,27 +1375,7 @@ static size_t ctpf_tile_bytes(int rows, int KP) { return ((size_t)rows * KP + 2 
 extern "C" int tmvb_ctpf_destroy(tmvb_ctpf* h)
 {
     if (!h) return TMVB_OK;
-    if (h->ctx) (void)hipSetDevice(h->ctx->device);
-    (void)hipFree(h->d_alef); (void)hipFree(h->d_alef_old); (void)hipFree(h->d_he); (void)hipFree(h->d_he_old);
-    (void)hipFree(h->d_TA); (void)hipFree(h->d_TH); (void)hipFree(h->d_topic_of_lane); (void)hipFree(h->d_grid_topic_of_lane);
-    if (h->own_stats) (void)hipFree(h->d_stats);
-    (void)hipFree(h->d_rates); (void)hipFree(h->d_lrates); (void)hipFree(h->d_lrates_d); (void)hipFree(h->d_gimel); (void)hipFree(h->d_gimel_old);
-    (void)hipFree(h->d_zayin); (void)hipFree(h->d_zayin_old); (void)hipFree(h->d_wtok); (void)hipFree(h->d_wrdr);
-    (void)hipFree(h->d_E1); (void)hipFree(h->d_E2); (void)hipFree(h->d_ts_partial); (void)hipFree(h->d_ts_partial2); (void)hipFree(h->d_sweeps);
-    (void)hipFree(h->d_doc_order); (void)hipFree(h->d_partial); (void)hipFree(h->d_partial2); (void)hipFree(h->d_rs_alef); (void)hipFree(h->d_rs_he);
-    (void)hipFree(h->d_mstep_counter);
-    (void)hipFree(h->d_sum_g); (void)hipFree(h->d_sum_z); (void)hipFree(h->d_doc_val); (void)hipFree(h->d_elbo_partial); (void)hipFree(h->d_elbo);
-    (void)hipFree(h->d_TAo); (void)hipFree(h->d_DA); (void)hipFree(h->d_THo); (void)hipFree(h->d_DH); (void)hipFree(h->d_lg_doc);
-    (void)hipFree(h->d_shift); (void)hipFree(h->d_logz); (void)hipFree(h->d_crd);
-    if (h->ev0) (void)hipEventDestroy(h->ev0);
-    if (h->ev1) (void)hipEventDestroy(h->ev1);
-    if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
-    if (h->ev_docs_done) (void)hipEventDestroy(h->ev_docs_done);
-    if (h->ev_elbo) (void)hipEventDestroy(h->ev_elbo);
-    for (int a = 0; a < tmvb_ctpf::NAUX; ++a) {
-        if (h->ev_join[a]) (void)hipEventDestroy(h->ev_join[a]);
-        tmvb_release_stream(h->aux[a]); h->aux[a] = nullptr;        // pooled streams stay (tmvb_pool_stream)
-    }
+    h->release();
     delete h;
     return TMVB_OK;
 }
@@ -1446,17 +1418,17 @@ extern "C" int tmvb_ctpf_create(tmvb_ctx* ctx, tmvb_corpus* corp, int32_t K, tmv
     int rc;
     if ((rc = tmvb_corpus_term_index(corp)) || (rc = tmvb_corpus_reader_index(corp))) return rc;
     const size_t slots = (size_t)std::max(corp->term_index.n_slots, corp->reader_index.n_slots);
-    if ((rc = dmalloc(&h->d_alef, KV)) || (rc = dmalloc(&h->d_alef_old, KV)) || (rc = dmalloc(&h->d_he, KU)) || (rc = dmalloc(&h->d_he_old, KU)) ||
-        (rc = dmalloc(&h->d_TA, (size_t)h->KP * h->V + 4)) || (rc = dmalloc(&h->d_TH, (size_t)h->KP * h->U + 4)) ||
-        (rc = dmalloc(&h->d_stats, (size_t)h->stats_len())) || (rc = dmalloc(&h->d_rates, 8 * (size_t)K)) || (rc = dmalloc(&h->d_lrates, 4 * (size_t)K)) ||
-        (rc = dmalloc(&h->d_gimel, KM)) || (rc = dmalloc(&h->d_gimel_old, KM)) || (rc = dmalloc(&h->d_zayin, KM)) || (rc = dmalloc(&h->d_zayin_old, KM)) ||
-        (rc = dmalloc(&h->d_wtok, (size_t)corp->info.nnz)) || (rc = dmalloc(&h->d_wrdr, (size_t)corp->info.nR)) ||
-        (rc = dmalloc(&h->d_E1, (size_t)h->estride * h->M + 4)) || (rc = dmalloc(&h->d_E2, (size_t)h->estride * h->M + 4)) ||
-        (rc = dmalloc(&h->d_ts_partial, slots * (K + 1))) || (rc = dmalloc(&h->d_ts_partial2, slots * (K + 1))) || (rc = dmalloc(&h->d_sweeps, (size_t)h->M)) || (rc = dmalloc(&h->d_doc_order, (size_t)h->M)) ||
-        (rc = dmalloc(&h->d_partial, (size_t)TMVB_REDUCE_BLOCKS * K)) || (rc = dmalloc(&h->d_partial2, (size_t)TMVB_REDUCE_BLOCKS * K)) || (rc = dmalloc(&h->d_rs_alef, K)) || (rc = dmalloc(&h->d_rs_he, K)) ||
-        (rc = dmalloc(&h->d_mstep_counter, 1)) ||
-        (rc = dmalloc(&h->d_sum_g, K)) || (rc = dmalloc(&h->d_sum_z, K)) || (rc = dmalloc(&h->d_doc_val, (size_t)h->M)) ||
-        (rc = dmalloc(&h->d_elbo_partial, 1024)) || (rc = dmalloc(&h->d_elbo, 2))) {
+    if ((rc = h->mem.alloc(&h->d_alef, KV)) || (rc = h->mem.alloc(&h->d_alef_old, KV)) || (rc = h->mem.alloc(&h->d_he, KU)) || (rc = h->mem.alloc(&h->d_he_old, KU)) ||
+        (rc = h->mem.alloc(&h->d_TA, (size_t)h->KP * h->V + 4)) || (rc = h->mem.alloc(&h->d_TH, (size_t)h->KP * h->U + 4)) ||
+        (rc = h->mem.alloc(&h->d_stats, (size_t)h->stats_len())) || (rc = h->mem.alloc(&h->d_rates, 8 * (size_t)K)) || (rc = h->mem.alloc(&h->d_lrates, 4 * (size_t)K)) ||
+        (rc = h->mem.alloc(&h->d_gimel, KM)) || (rc = h->mem.alloc(&h->d_gimel_old, KM)) || (rc = h->mem.alloc(&h->d_zayin, KM)) || (rc = h->mem.alloc(&h->d_zayin_old, KM)) ||
+        (rc = h->mem.alloc(&h->d_wtok, (size_t)corp->info.nnz)) || (rc = h->mem.alloc(&h->d_wrdr, (size_t)corp->info.nR)) ||
+        (rc = h->mem.alloc(&h->d_E1, (size_t)h->estride * h->M + 4)) || (rc = h->mem.alloc(&h->d_E2, (size_t)h->estride * h->M + 4)) ||
+        (rc = h->mem.alloc(&h->d_ts_partial, slots * (K + 1))) || (rc = h->mem.alloc(&h->d_ts_partial2, slots * (K + 1))) || (rc = h->mem.alloc(&h->d_sweeps, (size_t)h->M)) || (rc = h->mem.alloc(&h->d_doc_order, (size_t)h->M)) ||
+        (rc = h->mem.alloc(&h->d_partial, (size_t)TMVB_REDUCE_BLOCKS * K)) || (rc = h->mem.alloc(&h->d_partial2, (size_t)TMVB_REDUCE_BLOCKS * K)) || (rc = h->mem.alloc(&h->d_rs_alef, K)) || (rc = h->mem.alloc(&h->d_rs_he, K)) ||
+        (rc = h->mem.alloc(&h->d_mstep_counter, 1)) ||
+        (rc = h->mem.alloc(&h->d_sum_g, K)) || (rc = h->mem.alloc(&h->d_sum_z, K)) || (rc = h->mem.alloc(&h->d_doc_val, (size_t)h->M)) ||
+        (rc = h->mem.alloc(&h->d_elbo_partial, 1024)) || (rc = h->mem.alloc(&h->d_elbo, 2))) {
         return rc;
     }
     TMVB_HIP(hipMemset(h->d_mstep_counter, 0, sizeof(unsigned int)));
@@ -1468,7 +1440,7 @@ extern "C" int tmvb_ctpf_create(tmvb_ctx* ctx, tmvb_corpus* corp, int32_t K, tmv
     if (h->reg_path) {
         std::vector<int> tol, lot;
         tmvb_reg_lane_maps(h->KP, tol, lot);
-        if ((rc = dmalloc(&h->d_topic_of_lane, tol.size()))) return rc;
+        if ((rc = h->mem.alloc(&h->d_topic_of_lane, tol.size()))) return rc;
         TMVB_HIP(hipMemcpy(h->d_topic_of_lane, tol.data(), tol.size() * sizeof(int), hipMemcpyHostToDevice));
     }
     // grid-tile kernel: KP <= 60, both tables addressable by 32-bit byte offsets; TMVB_CTPF_GRID=0 keeps the lane = token tiles
@@ -1484,7 +1456,7 @@ extern "C" int tmvb_ctpf_create(tmvb_ctx* ctx, tmvb_corpus* corp, int32_t K, tmv
             default: h->grid_path = false;
         }
         if (h->grid_path) {
-            if ((rc = dmalloc(&h->d_grid_topic_of_lane, tol.size()))) return rc;
+            if ((rc = h->mem.alloc(&h->d_grid_topic_of_lane, tol.size()))) return rc;
             TMVB_HIP(hipMemcpy(h->d_grid_topic_of_lane, tol.data(), tol.size() * sizeof(int), hipMemcpyHostToDevice));
         }
     }
@@ -1535,18 +1507,13 @@ extern "C" int tmvb_ctpf_create(tmvb_ctx* ctx, tmvb_corpus* corp, int32_t K, tmv
     //  recorded unconditionally they cost every 0.15 ms iteration two barrier packets; round 4, as LDA has it)
     h->timing = tmvb_env_on("TMVB_ESTEP_TIMING", false);
     h->parts_env = tmvb_env_int("TMVB_CTPF_ELBO_PARTS", 1);
-    TMVB_HIP(hipEventCreate(&h->ev0));
-    TMVB_HIP(hipEventCreate(&h->ev1));
-    TMVB_HIP(hipEventCreateWithFlags(&h->ev_fork, tmvb_event_flags()));
-    TMVB_HIP(hipEventCreateWithFlags(&h->ev_docs_done, tmvb_event_flags()));
-    TMVB_HIP(hipEventCreateWithFlags(&h->ev_elbo, tmvb_event_flags()));
+    if ((rc = h->mem.event(&h->ev0, hipEventDefault)) || (rc = h->mem.event(&h->ev1, hipEventDefault)) || (rc = h->mem.event(&h->ev_fork, tmvb_event_flags())) ||
+        (rc = h->mem.event(&h->ev_docs_done, tmvb_event_flags())) || (rc = h->mem.event(&h->ev_elbo, tmvb_event_flags()))) return rc;
     for (int a = 0; a < tmvb_ctpf::NAUX; ++a) {
         // aux[1] carries the few multi-wave (long) documents next to the chain's one big launch: at the default priority its 512-thread
         // workgroups find no CU with eight free wave slots until the chain's launch drains and then add their whole run time to the
         // E-step; on a high-priority queue they are placed first
-        h->aux[a] = tmvb_pool_stream(ctx->device, 1 + a, a == 1);
-        TMVB_REQUIRE(h->aux[a] != nullptr, TMVB_EHIP, "hipStreamCreate failed");
-        TMVB_HIP(hipEventCreateWithFlags(&h->ev_join[a], tmvb_event_flags()));
+        if ((rc = h->mem.aux(&h->aux[a], ctx->device, 1 + a, a == 1)) || (rc = h->mem.event(&h->ev_join[a], tmvb_event_flags()))) return rc;
     }
     TMVB_HIP(hipStreamSynchronize(ctx->stream));
     // constructor state src/CTPF.jl:81-100: he = 1, rates = 1, gimel = zayin = 1; alef is drawn with Julia's RNG (:83): 1 here
@@ -1688,8 +1655,8 @@ static int ctpf_elbo_consts(tmvb_ctpf* h)
     tmvb_ctx* ctx = h->ctx;
     int rc;
     // (a shard without documents -- sharded handles take the decomposed form whatever their shard holds -- still needs the rate logarithms: one element each)
-    if ((rc = dmalloc(&h->d_lrates_d, 8 * (size_t)h->K)) || (rc = dmalloc(&h->d_lg_doc, (size_t)std::max<int64_t>(h->M, 1))) ||
-        (rc = dmalloc(&h->d_crd, 2 * (size_t)std::max<int64_t>(h->M, 1)))) return rc;
+    if ((rc = h->mem.alloc(&h->d_lrates_d, 8 * (size_t)h->K)) || (rc = h->mem.alloc(&h->d_lg_doc, (size_t)std::max<int64_t>(h->M, 1))) ||
+        (rc = h->mem.alloc(&h->d_crd, 2 * (size_t)std::max<int64_t>(h->M, 1)))) return rc;
     if (h->M == 0) return TMVB_OK;
     std::vector<double> lg((size_t)h->M, 0.0), crd(2 * (size_t)h->M, 0.0);
     const tmvb_corpus* c = h->corp;
@@ -1744,8 +1711,8 @@ extern "C" int tmvb_ctpf_estep(tmvb_ctpf* h, int32_t viter, double vtol)
     }
     if (collect) {
         { int crc = ctpf_elbo_consts(h); if (crc) return crc; }
-        if (!h->d_shift) { int arc = dmalloc(&h->d_shift, 2 * (size_t)h->M); if (arc) return arc; }
-        if (!h->d_logz) { int arc = dmalloc(&h->d_logz, (size_t)std::max<int64_t>(nct + ncr, 1)); if (arc) return arc; }
+        if (!h->d_shift) { int arc = h->mem.alloc(&h->d_shift, 2 * (size_t)h->M); if (arc) return arc; }
+        if (!h->d_logz) { int arc = h->mem.alloc(&h->d_logz, (size_t)std::max<int64_t>(nct + ncr, 1)); if (arc) return arc; }
         p.shift = h->d_shift;
     }
     if (h->timing) TMVB_HIP(hipEventRecord(h->ev0, ctx->stream));
@@ -1926,16 +1893,7 @@ extern "C" int tmvb_ctpf_stats(tmvb_ctpf* h, void** dev_ptr, int64_t* n_f32)
 
 extern "C" int tmvb_ctpf_bind_stats(tmvb_ctpf* h, void* dev_ptr, int64_t n_f32)
 {
-    TMVB_REQUIRE(h && dev_ptr, TMVB_EINVAL, "tmvb_ctpf_bind_stats: NULL argument");
-    TMVB_REQUIRE(n_f32 >= h->stats_len(), TMVB_ESHAPE, "tmvb_ctpf_bind_stats: buffer holds %lld floats, need %lld", (long long)n_f32, (long long)h->stats_len());
-    TMVB_HIP(hipSetDevice(h->ctx->device));
-    { int frc = ctpf_flush_docs(h); if (frc) return frc; }
-    TMVB_HIP(hipMemcpyAsync(dev_ptr, h->d_stats, (size_t)h->stats_len() * sizeof(float), hipMemcpyDeviceToDevice, h->ctx->stream));
-    TMVB_HIP(hipStreamSynchronize(h->ctx->stream));
-    if (h->own_stats) (void)hipFree(h->d_stats);
-    h->d_stats = (float*)dev_ptr;
-    h->own_stats = false;
-    return TMVB_OK;
+    return tmvb_model_bind_stats("tmvb_ctpf_bind_stats", h, dev_ptr, n_f32, h ? h->stats_len() : 0, [&] { return ctpf_flush_docs(h); });
 }
 
 extern "C" int tmvb_ctpf_set_distributed(tmvb_ctpf* h, int32_t distributed)
@@ -2057,7 +2015,7 @@ extern "C" int tmvb_ctpf_update_elbo_parts(tmvb_ctpf* h, double* doc_part, doubl
     if (h->M > 0 && !legacy_elbo) {
         if (!h->d_TAo) {                                  // first call of the table form: its tables
             const size_t na = (size_t)h->V * h->KP + 4, nh = (size_t)std::max<int64_t>(h->U, 1) * h->KP + 4;
-            if ((rc = dmalloc(&h->d_TAo, na)) || (rc = dmalloc(&h->d_DA, na)) || (rc = dmalloc(&h->d_THo, nh)) || (rc = dmalloc(&h->d_DH, nh))) return rc;
+            if ((rc = h->mem.alloc(&h->d_TAo, na)) || (rc = h->mem.alloc(&h->d_DA, na)) || (rc = h->mem.alloc(&h->d_THo, nh)) || (rc = h->mem.alloc(&h->d_DH, nh))) return rc;
         }
         int nbt = (int)std::min<int64_t>(2048, std::max<int64_t>(1, ((int64_t)h->KP * h->V + 255) / 256));
         hipLaunchKernelGGL(ctpf_elbo_tables_kernel, dim3(nbt), dim3(256), 0, ctx->stream, h->d_alef, h->d_alef_old, h->d_TAo, h->d_DA, h->K, h->KP, h->V,
@@ -2101,12 +2059,7 @@ extern "C" int tmvb_ctpf_update_elbo_parts(tmvb_ctpf* h, double* doc_part, doubl
     return TMVB_OK;
 }
 
-extern "C" int tmvb_ctpf_elbo_form(tmvb_ctpf* h, int32_t* form)
-{
-    TMVB_REQUIRE(h && form, TMVB_EINVAL, "tmvb_ctpf_elbo_form: NULL argument");
-    *form = h->elbo_form;
-    return TMVB_OK;
-}
+extern "C" int tmvb_ctpf_elbo_form(tmvb_ctpf* h, int32_t* form) { return tmvb_model_elbo_form("tmvb_ctpf_elbo_form", h, form); }
 
 extern "C" int tmvb_ctpf_update_elbo(tmvb_ctpf* h, double* elbo)
 {
@@ -2129,35 +2082,18 @@ extern "C" int tmvb_ctpf_set_comm(tmvb_ctpf* h, tmvb_comm* comm)
 }
 
 namespace {
-struct CtpfTrainOps {
+struct CtpfTrainOps : tmvb_base_train_ops<tmvb_ctpf> {
     int viter; double vtol;
     int estep(tmvb_ctpf* h) { return tmvb_ctpf_estep(h, viter, vtol); }               // src/CTPF.jl:353-365
     int reduce(tmvb_ctpf* h) { return tmvb_ctpf_reduce_docs(h); }
     int before_allreduce(tmvb_ctpf*) { return TMVB_OK; }
-    float* stats(tmvb_ctpf* h) { return h->d_stats; }
     int64_t stats_len(tmvb_ctpf* h) { return h->stats_len(); }
     int mstep(tmvb_ctpf* h) { return tmvb_ctpf_mstep(h); }                            // :366-371
     // the per-document part adds up over the shards; the (beta, eta) part is global and identical on every rank
     int elbo_local(tmvb_ctpf* h, double* s, double* once) { return tmvb_ctpf_update_elbo_parts(h, s, once); }
-    int elbo_form(tmvb_ctpf* h) { return h->elbo_form; }
-    void force_walk(tmvb_ctpf* h, bool on, bool doubled = true) { h->force_walk = on; if (!on && doubled) h->elbo_form = 1; }   // (switched off behind the one evaluation that doubled a decomposed one)
-    void will_check(tmvb_ctpf* h, bool checked) { h->want_parts = checked; }          // the coming iteration ends in check_elbo!
     // an unchecked iteration may be replayed from a hipGraph (tmvb_train.h): no pointer of the iteration alternates, no flag outlives it; not while an
     // update_elbo! kernel of a checked iteration is still pending on its side stream (the E-step would wait for an event recorded outside the capture)
     bool graph_ok(tmvb_ctpf* h) { return !h->distributed && !h->elbo_pending && !h->docs_pending && h->M > 0 && !h->timing; }
-    double* elbo_dev(tmvb_ctpf* h) { return h->d_elbo; }
-    tmvb_comm* comm(tmvb_ctpf* h) { return h->comm; }
-    bool distributed(tmvb_ctpf* h) { return h->distributed; }
-    tmvb_ctx* ctx(tmvb_ctpf* h) { return h->ctx; }
-    int64_t nnz(tmvb_ctpf* h) { return h->corp->info.nnz; }
-    void set_elbo(tmvb_ctpf* h, double v) { h->elbo = v; }
-    double get_elbo(tmvb_ctpf* h) { return h->elbo; }
-    int finish(tmvb_ctpf* h)
-    {
-        TMVB_HIP(hipSetDevice(h->ctx->device));
-        TMVB_HIP(hipStreamSynchronize(h->ctx->stream));
-        return TMVB_OK;
-    }
 };
 }  // namespace
 
@@ -2166,7 +2102,7 @@ extern "C" int tmvb_ctpf_train_group(tmvb_ctpf* const* hs, int32_t n, int32_t it
 {
     TMVB_REQUIRE(tol >= 0 && vtol >= 0, TMVB_EINVAL, "tolerance parameters must be nonnegative.");     // src/gpuCTPF.jl:679
     TMVB_REQUIRE(iter >= 0 && viter >= 0, TMVB_EINVAL, "iteration parameters must be nonnegative.");   // :680
-    CtpfTrainOps ops{viter, vtol};
+    CtpfTrainOps ops{{}, viter, vtol};
     return tmvb_train_group_loop("tmvb_ctpf_train", hs, n, iter, tol, checkelbo, elbo_traj, iters_done, elbo_baseline, ops);
 }
 
@@ -2185,36 +2121,6 @@ int tmvb_ctpf_view_of(tmvb_ctpf* h, tmvb_ctpf_view* v)
     return TMVB_OK;
 }
 
-// per-document sweep counts of the last E-step (document order of the corpus), for parity tests that compare the
-// state of exactly those documents whose exit sweep agrees with the oracle's
-extern "C" int tmvb_ctpf_doc_sweeps(tmvb_ctpf* h, uint8_t* out)
-{
-    TMVB_REQUIRE(h && (out || h->M == 0), TMVB_EINVAL, "tmvb_ctpf_doc_sweeps: NULL argument");
-    TMVB_HIP(hipSetDevice(h->ctx->device));
-    if (h->M) TMVB_HIP(hipMemcpyAsync(out, h->d_sweeps, (size_t)h->M, hipMemcpyDeviceToHost, h->ctx->stream));
-    TMVB_HIP(hipStreamSynchronize(h->ctx->stream));
-    return TMVB_OK;
-}
-
-extern "C" int tmvb_ctpf_sweep_hist(tmvb_ctpf* h, int64_t* hist, int32_t nbins)
-{
-    TMVB_REQUIRE(h && hist && nbins > 0, TMVB_EINVAL, "tmvb_ctpf_sweep_hist: bad argument");
-    std::vector<uint8_t> sw((size_t)h->M);
-    TMVB_HIP(hipSetDevice(h->ctx->device));
-    if (h->M) TMVB_HIP(hipMemcpyAsync(sw.data(), h->d_sweeps, (size_t)h->M, hipMemcpyDeviceToHost, h->ctx->stream));
-    TMVB_HIP(hipStreamSynchronize(h->ctx->stream));
-    for (int b = 0; b < nbins; ++b) hist[b] = 0;
-    for (uint8_t s : sw) hist[std::min<int>(s, nbins - 1)]++;
-    return TMVB_OK;
-}
-
-extern "C" int tmvb_ctpf_last_estep_ms(tmvb_ctpf* h, float* ms)
-{
-    TMVB_REQUIRE(h && ms, TMVB_EINVAL, "tmvb_ctpf_last_estep_ms: NULL argument");
-    TMVB_REQUIRE(h->timing, TMVB_EINVAL, "tmvb_ctpf_last_estep_ms: E-step timing is off (set TMVB_ESTEP_TIMING=1 before creating the model)");
-    TMVB_REQUIRE(h->timed, TMVB_EINVAL, "tmvb_ctpf_last_estep_ms: no E-step has run");
-    TMVB_HIP(hipSetDevice(h->ctx->device));
-    TMVB_HIP(hipEventSynchronize(h->ev1));
-    TMVB_HIP(hipEventElapsedTime(ms, h->ev0, h->ev1));
-    return TMVB_OK;
-}
+extern "C" int tmvb_ctpf_doc_sweeps(tmvb_ctpf* h, uint8_t* out) { return tmvb_model_doc_sweeps("tmvb_ctpf_doc_sweeps", h, out); }
+extern "C" int tmvb_ctpf_sweep_hist(tmvb_ctpf* h, int64_t* hist, int32_t nbins) { return tmvb_model_sweep_hist("tmvb_ctpf_sweep_hist", h, hist, nbins); }
+extern "C" int tmvb_ctpf_last_estep_ms(tmvb_ctpf* h, float* ms) { return tmvb_model_last_estep_ms("tmvb_ctpf_last_estep_ms", h, ms, true); }

@@ -24,6 +24,8 @@
 // makes the reference's tau_n exactly 0); fp32 beta cannot represent the distinction below 1e-38 anyway.
 #include "tmvb_common_kernels.h"
 #include "tmvb_train.h"
+#include "tmvb_handle.h"
+#include "tmvb_model.h"
 #include "tmvb_dirichlet.h"
 #include "tmvb_filtered.h"
 
@@ -351,39 +353,26 @@ __global__ __launch_bounds__(64) void flda_elbo_doc_parts_kernel(int K, const in
 }
 
 // ------------------------------------------------------------------------------ host side
-struct tmvb_flda {
-    tmvb_ctx* ctx = nullptr;
-    tmvb_corpus* corp = nullptr;
-    int K = 0, KP = 0, nslot = 1;
-    int64_t M = 0, V = 0, M_total = 0, nnz = 0;
+struct tmvb_flda : tmvb_model_base {     // d_stats: S (K*V) | kstat (V) | Elogtheta_sum (K)
+    int64_t nnz = 0;
     double C_total = 0.0;
-    bool distributed = false;
-    tmvb_comm* comm = nullptr;
     double* d_alpha_d = nullptr; float* d_alpha_f = nullptr;
     float* d_beta[2] = {nullptr, nullptr}; int cur = 0;        // padded [V][KP]
     float* d_L = nullptr;                                      // log(beta + eps)
     float* d_kappa = nullptr; float* d_kappa_old = nullptr;    // [V]
     double* d_eta = nullptr; double* d_ksum = nullptr;
-    float* d_stats = nullptr;                                  // S (K*V) | kstat (V) | Elogtheta_sum (K)
     float* d_gamma = nullptr; float* d_elog = nullptr; float* d_elog_old = nullptr;
     float* d_tau = nullptr; float* d_tau_old = nullptr; float* d_lse = nullptr;
     // decomposed update_elbo! (flda_elbo_doc_parts_kernel): the per-token exponent of the last sweep, the alpha the collecting E-step read, update_beta!'s
     // partial sums of S (log beta_new - log beta_old)
     float* d_aold = nullptr; float* d_alpha_e = nullptr; double* d_pw_partial = nullptr; int pw_blocks = 0;
-    int parts_env = 1;                 // TMVB_FLDA_ELBO_PARTS at creation: 0 never, 1 the iterations train! checks, 2 every E-step collects
-    bool want_parts = false;           // train!: the coming iteration ends in check_elbo!
     bool parts_pending = false;        // the last E-step collected (aold, alpha_e belong to it) and update_beta! has not run behind it yet
     bool parts_valid = false;          // ... it has: d_pw_partial belongs to that E-step too and nothing was set from outside since
-    bool force_walk = false;           // train!'s like-with-like evaluation at the switch of forms (tmvb_train.h)
-    int elbo_form = 0;                 // the last update_elbo!: 1 decomposed, 0 token walk (tmvb_flda_elbo_form)
     float* d_ts_partial = nullptr;
-    uint8_t* d_sweeps = nullptr; int32_t* d_doc_order = nullptr;
-    double* d_partial = nullptr; double* d_rowsum = nullptr; double* d_esum = nullptr; double* d_doc_val = nullptr; double* d_elbo = nullptr;
+    int32_t* d_doc_order = nullptr;
+    double* d_partial = nullptr; double* d_rowsum = nullptr; double* d_esum = nullptr; double* d_doc_val = nullptr;
     int* d_iters = nullptr;
-    double elbo = 0.0;
     std::vector<tmvb_bucket> buckets;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    bool timed = false;
     int64_t stats_len() const { return (int64_t)K * V + V + K; }
     float* kstat() const { return d_stats + (size_t)K * V; }
     float* esum_f() const { return d_stats + (size_t)K * V + (size_t)V; }
@@ -392,38 +381,8 @@ struct tmvb_flda {
 extern "C" int tmvb_flda_destroy(tmvb_flda* h)
 {
     if (!h) return TMVB_OK;
-    if (h->ctx) { (void)hipSetDevice(h->ctx->device); (void)hipStreamSynchronize(h->ctx->stream); }
-    (void)hipFree(h->d_aold); (void)hipFree(h->d_alpha_e); (void)hipFree(h->d_pw_partial);
-    (void)hipFree(h->d_alpha_d); (void)hipFree(h->d_alpha_f); (void)hipFree(h->d_beta[0]); (void)hipFree(h->d_beta[1]); (void)hipFree(h->d_L);
-    (void)hipFree(h->d_kappa); (void)hipFree(h->d_kappa_old); (void)hipFree(h->d_eta); (void)hipFree(h->d_ksum); (void)hipFree(h->d_stats);
-    (void)hipFree(h->d_gamma); (void)hipFree(h->d_elog); (void)hipFree(h->d_elog_old); (void)hipFree(h->d_tau); (void)hipFree(h->d_tau_old);
-    (void)hipFree(h->d_lse); (void)hipFree(h->d_ts_partial); (void)hipFree(h->d_sweeps); (void)hipFree(h->d_doc_order); (void)hipFree(h->d_partial);
-    (void)hipFree(h->d_rowsum); (void)hipFree(h->d_esum); (void)hipFree(h->d_doc_val); (void)hipFree(h->d_elbo); (void)hipFree(h->d_iters);
-    if (h->ev0) (void)hipEventDestroy(h->ev0);
-    if (h->ev1) (void)hipEventDestroy(h->ev1);
+    h->release();
     delete h;
-    return TMVB_OK;
-}
-
-static int flda_upload_beta(tmvb_flda* h, float* dst, const double* src)
-{
-    const size_t K = h->K, KP = h->KP, V = h->V;
-    std::vector<float> tmp(V * KP + 4, 0.0f);
-    for (size_t j = 0; j < V; ++j)
-        for (size_t i = 0; i < K; ++i) tmp[j * KP + i] = (float)src[j * K + i];
-    TMVB_HIP(hipMemcpyAsync(dst, tmp.data(), tmp.size() * sizeof(float), hipMemcpyHostToDevice, h->ctx->stream));
-    TMVB_HIP(hipStreamSynchronize(h->ctx->stream));
-    return TMVB_OK;
-}
-
-static int flda_download_beta(tmvb_flda* h, double* dst, const float* src)
-{
-    const size_t K = h->K, KP = h->KP, V = h->V;
-    std::vector<float> tmp(V * KP);
-    TMVB_HIP(hipMemcpyAsync(tmp.data(), src, tmp.size() * sizeof(float), hipMemcpyDeviceToHost, h->ctx->stream));
-    TMVB_HIP(hipStreamSynchronize(h->ctx->stream));
-    for (size_t j = 0; j < V; ++j)
-        for (size_t i = 0; i < K; ++i) dst[j * K + i] = (double)tmp[j * KP + i];
     return TMVB_OK;
 }
 
@@ -456,16 +415,16 @@ extern "C" int tmvb_flda_create(tmvb_ctx* ctx, tmvb_corpus* corp, int32_t K, tmv
     const size_t KM = (size_t)K * h->M, KPV = (size_t)h->KP * h->V + 4, NZ = (size_t)h->nnz;
     int rc;
     if ((rc = tmvb_corpus_term_index(corp))) return rc;
-    if ((rc = dmalloc(&h->d_alpha_d, K)) || (rc = dmalloc(&h->d_alpha_f, K)) || (rc = dmalloc(&h->d_beta[0], KPV)) || (rc = dmalloc(&h->d_beta[1], KPV)) ||
-        (rc = dmalloc(&h->d_L, KPV)) || (rc = dmalloc(&h->d_kappa, (size_t)h->V)) || (rc = dmalloc(&h->d_kappa_old, (size_t)h->V)) ||
-        (rc = dmalloc(&h->d_eta, 1)) || (rc = dmalloc(&h->d_ksum, 1)) || (rc = dmalloc(&h->d_stats, (size_t)h->stats_len())) ||
-        (rc = dmalloc(&h->d_gamma, KM)) || (rc = dmalloc(&h->d_elog, KM)) || (rc = dmalloc(&h->d_elog_old, KM)) ||
-        (rc = dmalloc(&h->d_tau, NZ)) || (rc = dmalloc(&h->d_tau_old, NZ)) || (rc = dmalloc(&h->d_lse, NZ)) ||
-        (rc = dmalloc(&h->d_aold, std::max<size_t>(NZ, 1))) || (rc = dmalloc(&h->d_alpha_e, K)) || (rc = dmalloc(&h->d_pw_partial, 2048)) ||
-        (rc = dmalloc(&h->d_ts_partial, (size_t)corp->term_index.n_slots * (K + 1))) || (rc = dmalloc(&h->d_sweeps, (size_t)h->M)) ||
-        (rc = dmalloc(&h->d_doc_order, (size_t)h->M)) || (rc = dmalloc(&h->d_partial, (size_t)TMVB_REDUCE_BLOCKS * K)) ||
-        (rc = dmalloc(&h->d_rowsum, K)) || (rc = dmalloc(&h->d_esum, K)) || (rc = dmalloc(&h->d_doc_val, (size_t)h->M)) ||
-        (rc = dmalloc(&h->d_elbo, 1)) || (rc = dmalloc(&h->d_iters, 1)))
+    if ((rc = h->mem.alloc(&h->d_alpha_d, K)) || (rc = h->mem.alloc(&h->d_alpha_f, K)) || (rc = h->mem.alloc(&h->d_beta[0], KPV)) || (rc = h->mem.alloc(&h->d_beta[1], KPV)) ||
+        (rc = h->mem.alloc(&h->d_L, KPV)) || (rc = h->mem.alloc(&h->d_kappa, (size_t)h->V)) || (rc = h->mem.alloc(&h->d_kappa_old, (size_t)h->V)) ||
+        (rc = h->mem.alloc(&h->d_eta, 1)) || (rc = h->mem.alloc(&h->d_ksum, 1)) || (rc = h->mem.alloc(&h->d_stats, (size_t)h->stats_len())) ||
+        (rc = h->mem.alloc(&h->d_gamma, KM)) || (rc = h->mem.alloc(&h->d_elog, KM)) || (rc = h->mem.alloc(&h->d_elog_old, KM)) ||
+        (rc = h->mem.alloc(&h->d_tau, NZ)) || (rc = h->mem.alloc(&h->d_tau_old, NZ)) || (rc = h->mem.alloc(&h->d_lse, NZ)) ||
+        (rc = h->mem.alloc(&h->d_aold, std::max<size_t>(NZ, 1))) || (rc = h->mem.alloc(&h->d_alpha_e, K)) || (rc = h->mem.alloc(&h->d_pw_partial, 2048)) ||
+        (rc = h->mem.alloc(&h->d_ts_partial, (size_t)corp->term_index.n_slots * (K + 1))) || (rc = h->mem.alloc(&h->d_sweeps, (size_t)h->M)) ||
+        (rc = h->mem.alloc(&h->d_doc_order, (size_t)h->M)) || (rc = h->mem.alloc(&h->d_partial, (size_t)TMVB_REDUCE_BLOCKS * K)) ||
+        (rc = h->mem.alloc(&h->d_rowsum, K)) || (rc = h->mem.alloc(&h->d_esum, K)) || (rc = h->mem.alloc(&h->d_doc_val, (size_t)h->M)) ||
+        (rc = h->mem.alloc(&h->d_elbo, 1)) || (rc = h->mem.alloc(&h->d_iters, 1)))
         return rc;
     h->parts_env = tmvb_env_int("TMVB_FLDA_ELBO_PARTS", 1);
     std::vector<int32_t> order((size_t)h->M);
@@ -484,8 +443,7 @@ extern "C" int tmvb_flda_create(tmvb_ctx* ctx, tmvb_corpus* corp, int32_t K, tmv
     TMVB_HIP(hipMemsetAsync(h->d_beta[1], 0, KPV * sizeof(float), ctx->stream));
     TMVB_HIP(hipMemsetAsync(h->d_lse, 0, std::max<size_t>(NZ, 1) * sizeof(float), ctx->stream));
     TMVB_HIP(hipMemsetAsync(h->d_ksum, 0, sizeof(double), ctx->stream));
-    TMVB_HIP(hipEventCreate(&h->ev0));
-    TMVB_HIP(hipEventCreate(&h->ev1));
+    if ((rc = h->mem.event(&h->ev0, hipEventDefault)) || (rc = h->mem.event(&h->ev1, hipEventDefault))) return rc;
     TMVB_HIP(hipStreamSynchronize(ctx->stream));
     // constructor state, src/fLDA.jl:38-52: eta = 0.5, alpha = 1, gamma = 1, Elogtheta = psi(1) - psi(K), tau = eta;
     // kappa and beta are drawn from Dirichlet(V, 1) with Julia's RNG in the reference: uniform until tmvb_flda_set_state
@@ -526,11 +484,11 @@ extern "C" int tmvb_flda_set_state(tmvb_flda* h, const double* eta, const double
     }
     if (kappa_old && (rc = upload_f32(ctx, h->d_kappa_old, kappa_old, V))) return rc;
     if (beta) {
-        if ((rc = flda_upload_beta(h, h->d_beta[h->cur], beta))) return rc;
-        if (!beta_old && (rc = flda_upload_beta(h, h->d_beta[h->cur ^ 1], beta))) return rc;
+        if ((rc = tmvb_model_upload_beta(h, h->d_beta[h->cur], beta))) return rc;
+        if (!beta_old && (rc = tmvb_model_upload_beta(h, h->d_beta[h->cur ^ 1], beta))) return rc;
         if ((rc = flda_refresh_L(h))) return rc;
     }
-    if (beta_old && (rc = flda_upload_beta(h, h->d_beta[h->cur ^ 1], beta_old))) return rc;
+    if (beta_old && (rc = tmvb_model_upload_beta(h, h->d_beta[h->cur ^ 1], beta_old))) return rc;
     if (gamma && (rc = upload_f32(ctx, h->d_gamma, gamma, KM))) return rc;
     if (Elogtheta) {
         if ((rc = upload_f32(ctx, h->d_elog, Elogtheta, KM))) return rc;
@@ -562,8 +520,8 @@ extern "C" int tmvb_flda_get_state(tmvb_flda* h, double* eta, double* alpha, dou
     TMVB_HIP(hipStreamSynchronize(ctx->stream));
     if (kappa && (rc = download_f32(ctx, kappa, h->d_kappa, V))) return rc;
     if (kappa_old && (rc = download_f32(ctx, kappa_old, h->d_kappa_old, V))) return rc;
-    if (beta && (rc = flda_download_beta(h, beta, h->d_beta[h->cur]))) return rc;
-    if (beta_old && (rc = flda_download_beta(h, beta_old, h->d_beta[h->cur ^ 1]))) return rc;
+    if (beta && (rc = tmvb_model_download_beta(h, beta, h->d_beta[h->cur]))) return rc;
+    if (beta_old && (rc = tmvb_model_download_beta(h, beta_old, h->d_beta[h->cur ^ 1]))) return rc;
     if (gamma && (rc = download_f32(ctx, gamma, h->d_gamma, KM))) return rc;
     if (Elogtheta && (rc = download_f32(ctx, Elogtheta, h->d_elog, KM))) return rc;
     if (Elogtheta_old && (rc = download_f32(ctx, Elogtheta_old, h->d_elog_old, KM))) return rc;
@@ -755,12 +713,11 @@ extern "C" int tmvb_flda_update_elbo(tmvb_flda* h, double* elbo)
 }
 
 namespace {
-struct FldaTrainOps {
+struct FldaTrainOps : tmvb_base_train_ops<tmvb_flda> {
     int niter, viter; double ntol, vtol;
     int estep(tmvb_flda* h) { return tmvb_flda_estep(h, viter, vtol); }                  // src/fLDA.jl:222-236
     int reduce(tmvb_flda* h) { return tmvb_flda_reduce_docs(h); }
     int before_allreduce(tmvb_flda*) { return TMVB_OK; }
-    float* stats(tmvb_flda* h) { return h->d_stats; }
     int64_t stats_len(tmvb_flda* h) { return h->stats_len(); }
     int mstep(tmvb_flda* h)
     {
@@ -770,22 +727,6 @@ struct FldaTrainOps {
         return rc;
     }
     int elbo_local(tmvb_flda* h, double* s, double* once) { *once = 0.0; return tmvb_flda_update_elbo(h, s); }
-    int elbo_form(tmvb_flda* h) { return h->elbo_form; }
-    void force_walk(tmvb_flda* h, bool on, bool doubled = true) { h->force_walk = on; if (!on && doubled) h->elbo_form = 1; }   // (as LdaTrainOps)
-    void will_check(tmvb_flda* h, bool checked) { h->want_parts = checked; }
-    double* elbo_dev(tmvb_flda* h) { return h->d_elbo; }
-    tmvb_comm* comm(tmvb_flda* h) { return h->comm; }
-    bool distributed(tmvb_flda* h) { return h->distributed; }
-    tmvb_ctx* ctx(tmvb_flda* h) { return h->ctx; }
-    int64_t nnz(tmvb_flda* h) { return h->corp->info.nnz; }
-    void set_elbo(tmvb_flda* h, double v) { h->elbo = v; }
-    double get_elbo(tmvb_flda* h) { return h->elbo; }
-    int finish(tmvb_flda* h)
-    {
-        TMVB_HIP(hipSetDevice(h->ctx->device));
-        TMVB_HIP(hipStreamSynchronize(h->ctx->stream));
-        return TMVB_OK;
-    }
 };
 }  // namespace
 
@@ -796,7 +737,7 @@ extern "C" int tmvb_flda_train_group(tmvb_flda* const* hs, int32_t n, int32_t it
 {
     TMVB_REQUIRE(tol >= 0 && ntol >= 0 && vtol >= 0, TMVB_EINVAL, "tolerance parameters must be nonnegative.");   // src/fLDA.jl:215
     TMVB_REQUIRE(iter >= 0 && niter >= 0 && viter >= 0, TMVB_EINVAL, "iteration parameters must be nonnegative."); // :216
-    FldaTrainOps ops{niter, viter, ntol, vtol};
+    FldaTrainOps ops{{}, niter, viter, ntol, vtol};
     return tmvb_train_group_loop("tmvb_flda_train", hs, n, iter, tol, checkelbo, elbo_traj, iters_done, elbo_baseline, ops);
 }
 
@@ -808,28 +749,7 @@ extern "C" int tmvb_flda_train(tmvb_flda* h, int32_t iter, double tol, int32_t n
     return tmvb_flda_train_group(&h, 1, iter, tol, niter, ntol, viter, vtol, checkelbo, elbo_traj, iters_done, elbo_baseline);
 }
 
-extern "C" int tmvb_flda_elbo_form(tmvb_flda* h, int32_t* form)
-{
-    TMVB_REQUIRE(h && form, TMVB_EINVAL, "tmvb_flda_elbo_form: NULL argument");
-    *form = h->elbo_form;
-    return TMVB_OK;
-}
-
-extern "C" int tmvb_flda_doc_sweeps(tmvb_flda* h, uint8_t* out)
-{
-    TMVB_REQUIRE(h && (out || h->M == 0), TMVB_EINVAL, "tmvb_flda_doc_sweeps: NULL argument");
-    TMVB_HIP(hipSetDevice(h->ctx->device));
-    if (h->M) TMVB_HIP(hipMemcpyAsync(out, h->d_sweeps, (size_t)h->M, hipMemcpyDeviceToHost, h->ctx->stream));
-    TMVB_HIP(hipStreamSynchronize(h->ctx->stream));
-    return TMVB_OK;
-}
-
-extern "C" int tmvb_flda_last_estep_ms(tmvb_flda* h, float* ms)
-{
-    TMVB_REQUIRE(h && ms, TMVB_EINVAL, "tmvb_flda_last_estep_ms: NULL argument");
-    TMVB_REQUIRE(h->timed, TMVB_EINVAL, "tmvb_flda_last_estep_ms: no E-step has run");
-    TMVB_HIP(hipSetDevice(h->ctx->device));
-    TMVB_HIP(hipEventSynchronize(h->ev1));
-    TMVB_HIP(hipEventElapsedTime(ms, h->ev0, h->ev1));
-    return TMVB_OK;
-}
+extern "C" int tmvb_flda_elbo_form(tmvb_flda* h, int32_t* form) { return tmvb_model_elbo_form("tmvb_flda_elbo_form", h, form); }
+extern "C" int tmvb_flda_doc_sweeps(tmvb_flda* h, uint8_t* out) { return tmvb_model_doc_sweeps("tmvb_flda_doc_sweeps", h, out); }
+// (fLDA records its two timing events at every E-step: no TMVB_ESTEP_TIMING switch to refuse on)
+extern "C" int tmvb_flda_last_estep_ms(tmvb_flda* h, float* ms) { return tmvb_model_last_estep_ms("tmvb_flda_last_estep_ms", h, ms, false); }

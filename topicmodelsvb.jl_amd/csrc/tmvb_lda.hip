@@ -30,6 +30,9 @@
 #define TMVB_TS_LOGZ 1            // this translation unit instantiates the log-normaliser forms of the statistics pass (update_elbo!)
 #include "tmvb_common_kernels.h"
 #include "tmvb_train.h"
+#include "tmvb_call.h"
+#include "tmvb_handle.h"
+#include "tmvb_model.h"
 #include "tmvb_dirichlet.h"
 #include "tmvb_regtile.h"
 #include "tmvb_gridtile.h"
@@ -1090,32 +1093,23 @@ static void lda_launch_reg(int tiles, dim3 grid, dim3 block, hipStream_t st, con
 }
 
 // ------------------------------------------------------------------------------ host side
-struct tmvb_lda {
-    tmvb_ctx* ctx = nullptr;
-    tmvb_corpus* corp = nullptr;
-    int K = 0, KP = 0, nslot = 1;
-    int64_t M = 0, V = 0;
-    int64_t M_total = 0;
-    bool distributed = false;
-    tmvb_comm* comm = nullptr;         // document-sharded train!: the all-reduce of the packed statistics (not owned)
+struct tmvb_lda : tmvb_model_base {      // d_stats: S (K*V) | Elogtheta_sum (K)
     // device state
     double* d_alpha_d = nullptr;
     float* d_alpha_f = nullptr;
     float* d_beta[2] = {nullptr, nullptr};
     int cur = 0;                       // d_beta[cur] = beta, d_beta[cur^1] = beta_old
-    float* d_stats = nullptr;          // S (K*V) | Elogtheta_sum (K)
     // round 5: the LAST statistics pass of the pipelined E-step writes its own buffer (and its own multi-chunk partials), so that it starts behind the last
     // document kernel instead of behind the passes before it (which accumulate in order on aux[0]); update_beta! merges (colsum_merge_partial_kernel)
     float* d_stats_b = nullptr; float* d_ts_partial_b = nullptr;
     bool stats_b_live = false;         // d_stats_b holds statistics that d_stats does not
     bool events_system_scope = false;  // a communicator was attached: the ordering events carry the system-scope fence (tmvb_lda_set_comm)
-    bool own_stats = true;
+    bool own_stats = true;             // d_stats is the library's own buffer (the split below needs that; release does not)
     int lds_limit = -1;                // hipDeviceAttributeMaxSharedMemoryPerBlock of the context's device (read once)
     int elbo_doc_lds_set = 0;          // dynamic-LDS attribute already set on lda_elbo_doc_kernel
     float* d_gamma = nullptr;
     float* d_elog = nullptr;
     float* d_elog_old = nullptr;
-    uint8_t* d_sweeps = nullptr;
     float* d_wtok = nullptr;           // [nnz]
     float* d_E = nullptr;              // [M][estride]
     int estride = 0;
@@ -1131,12 +1125,8 @@ struct tmvb_lda {
     double* d_rowsum = nullptr;        // [K]
     double* d_esum = nullptr;          // [K]
     double* d_doc_val = nullptr;       // [M]
-    double* d_elbo = nullptr;          // [1]
     int* d_iters = nullptr;
-    double elbo = 0.0;
     std::vector<tmvb_bucket> buckets;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    bool timed = false;
     // the length buckets of one E-step are independent: they are issued round-robin on a few
     // auxiliary streams (fork/join on the context's stream) so that their tails overlap
     static constexpr int NAUX = 4;
@@ -1157,7 +1147,6 @@ struct tmvb_lda {
     double* d_partial_side = nullptr;
     bool esum_fresh = false;           // d_esum / statistics tail hold the sums of the current Elogtheta
     bool esum_side = false;            // ... and they were produced on the side stream by the last E-step
-    bool timing = false;               // TMVB_ESTEP_TIMING=1: record the events behind tmvb_lda_last_estep_ms
     bool mark_valid = false;           // ev_mark was recorded at the entry of the preceding update_beta call
     // E_q[log p(w)] = sum S .* log(beta_new + eps) falls out of update_beta! (the statistics ARE sum_n c_n phi_in), so the
     // ELBO pass right after an iteration needs neither the beta rows nor their logarithms.  A document-sharded rank
@@ -1170,8 +1159,6 @@ struct tmvb_lda {
     // decomposed update_elbo! (lda_elbo_doc_kernel): an iteration that WILL be checked (train!: known before its E-step; TMVB_LDA_ELBO_PARTS=2: every
     // iteration, =0: never) collects the chunks' log-normaliser sums in its statistics passes, keeps the alpha its E-step read, and has update_beta!
     // leave sum S (log beta_new - log beta_old); update_elbo! then needs one per-document kernel instead of a second walk over the corpus.
-    bool want_parts = false;           // set for the coming iteration
-    int parts_env = 1;                 // TMVB_LDA_ELBO_PARTS at tmvb_lda_create: 0 never, 1 the iterations train! will check, 2 every E-step
     double* d_logz = nullptr; size_t logz_cap = 0; int64_t n_logz = 0;
     double* d_lz_partial = nullptr;    // [2048] per-block sums of d_logz, by beta_norm_kernel
     static constexpr int ELBO = 2;     // aux[2]: lda_elbo_doc_kernel's stream
@@ -1181,8 +1168,6 @@ struct tmvb_lda {
     int64_t n_elbo_blocks = 0;         // d_doc_val[0, n_elbo_blocks): lda_elbo_doc_kernel's values, enqueued by that E-step on its side stream
     bool logz_valid = false;           // d_logz[0, n_logz) and those values belong to the last E-step (every statistics pass of it)
     bool pw_diff = false;              // d_pw_partial holds the (log beta_new - log beta_old) form
-    int elbo_form = 0;                 // the last update_elbo!: 1 decomposed, 0 token walk (tmvb_lda_elbo_form)
-    bool force_walk = false;           // train!'s like-with-like evaluation at the switch of forms (tmvb_train.h)
     bool side_pending = false;         // ev_side marks side-stream work the context's stream has not waited for yet
     // tmvb_lda_estep_allreduce (document-sharded run): the LAST statistics pass is issued in vocabulary slices, and the slab of S
     // a slice completes is all-reduced on aux[AR] while the next slice's pass runs on the context's stream.  Cuts and order are
@@ -1369,62 +1354,10 @@ static int lda_merge_stats(tmvb_lda* h)
 extern "C" int tmvb_lda_destroy(tmvb_lda* h)
 {
     if (!h) return TMVB_OK;
-    if (h->ctx) (void)hipSetDevice(h->ctx->device);
-    for (int a = 0; a < tmvb_lda::NAUX; ++a) if (h->aux[a]) (void)hipStreamSynchronize(h->aux[a]);
-    if (h->ctx) (void)hipStreamSynchronize(h->ctx->stream);
-    if (h->own_globals) { (void)hipFree(h->d_alpha_d); (void)hipFree(h->d_alpha_f); (void)hipFree(h->d_beta[0]); (void)hipFree(h->d_beta[1]); }
-    (void)hipFree(h->d_stats_b); (void)hipFree(h->d_ts_partial_b);
-    if (h->own_stats) (void)hipFree(h->d_stats);
-    (void)hipFree(h->d_wtok); (void)hipFree(h->d_E); (void)hipFree(h->d_ts_partial);
-    (void)hipFree(h->d_topic_of_lane); (void)hipFree(h->d_grid_topic_of_lane);
-    (void)hipFree(h->d_gamma); (void)hipFree(h->d_elog); (void)hipFree(h->d_elog_old); (void)hipFree(h->d_sweeps);
-    (void)hipFree(h->d_doc_order); (void)hipFree(h->d_partial); (void)hipFree(h->d_rowsum); (void)hipFree(h->d_esum);
-    (void)hipFree(h->d_doc_val); (void)hipFree(h->d_elbo); (void)hipFree(h->d_iters);
-    if (h->ev0) (void)hipEventDestroy(h->ev0);
-    if (h->ev1) (void)hipEventDestroy(h->ev1);
-    if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
-    if (h->ev_docs) (void)hipEventDestroy(h->ev_docs);
-    if (h->ev_side) (void)hipEventDestroy(h->ev_side);
-    if (h->ev_chain) (void)hipEventDestroy(h->ev_chain);
-    if (h->ev_acopy) (void)hipEventDestroy(h->ev_acopy);
-    if (h->ev_elbo) (void)hipEventDestroy(h->ev_elbo);
-    if (h->ev_mark) (void)hipEventDestroy(h->ev_mark);
-    (void)hipFree(h->d_partial_side); (void)hipFree(h->d_pw_partial); (void)hipFree(h->d_logz); (void)hipFree(h->d_lz_partial); (void)hipFree(h->d_alpha_e);
+    h->release();
     for (tmvb_inv_index& ix : h->pieces) tmvb_free_inv_index(&ix);
     if (h->ar_index.built) tmvb_free_inv_index(&h->ar_index);
-    for (hipEvent_t e : h->ev_slice) if (e) (void)hipEventDestroy(e);
-    if (h->ev_comm) (void)hipEventDestroy(h->ev_comm);
-    if (h->ev_tail) (void)hipEventDestroy(h->ev_tail);
-    for (hipEvent_t e : h->ev_piece) if (e) (void)hipEventDestroy(e);
-    for (int a = 0; a < tmvb_lda::NAUX; ++a) {
-        if (h->ev_join[a]) (void)hipEventDestroy(h->ev_join[a]);
-        if (h->own_aux) tmvb_release_stream(h->aux[a]);             // pooled streams stay (tmvb_pool_stream)
-        h->aux[a] = nullptr;
-    }
     delete h;
-    return TMVB_OK;
-}
-
-// host K x V (column-major) <-> device [V][KP] padded
-static int upload_beta(tmvb_lda* h, float* dst, const double* src)
-{
-    const size_t K = h->K, KP = h->KP, V = h->V;
-    std::vector<float> tmp(V * KP + 4, 0.0f);
-    for (size_t j = 0; j < V; ++j)
-        for (size_t i = 0; i < K; ++i) tmp[j * KP + i] = (float)src[j * K + i];
-    TMVB_HIP(hipMemcpyAsync(dst, tmp.data(), tmp.size() * sizeof(float), hipMemcpyHostToDevice, h->ctx->stream));
-    TMVB_HIP(hipStreamSynchronize(h->ctx->stream));
-    return TMVB_OK;
-}
-
-static int download_beta(tmvb_lda* h, double* dst, const float* src)
-{
-    const size_t K = h->K, KP = h->KP, V = h->V;
-    std::vector<float> tmp(V * KP);
-    TMVB_HIP(hipMemcpyAsync(tmp.data(), src, tmp.size() * sizeof(float), hipMemcpyDeviceToHost, h->ctx->stream));
-    TMVB_HIP(hipStreamSynchronize(h->ctx->stream));
-    for (size_t j = 0; j < V; ++j)
-        for (size_t i = 0; i < K; ++i) dst[j * K + i] = (double)tmp[j * KP + i];
     return TMVB_OK;
 }
 
@@ -1446,21 +1379,21 @@ extern "C" int tmvb_lda_create(tmvb_ctx* ctx, tmvb_corpus* corp, int32_t K, tmvb
     const size_t KV = (size_t)K * h->V, KM = (size_t)K * h->M;
     const size_t KPV = (size_t)h->KP * h->V + 4;      // padded gather layout (+ slack for 16-byte reads)
     int rc;
-    if ((rc = dmalloc(&h->d_alpha_d, K)) || (rc = dmalloc(&h->d_alpha_f, K)) || (rc = dmalloc(&h->d_beta[0], KPV)) ||
-        (rc = dmalloc(&h->d_beta[1], KPV)) || (rc = dmalloc(&h->d_stats, KV + K)) || (rc = dmalloc(&h->d_gamma, KM)) ||
-        (rc = dmalloc(&h->d_elog, KM)) || (rc = dmalloc(&h->d_elog_old, KM)) || (rc = dmalloc(&h->d_sweeps, (size_t)h->M)) ||
-        (rc = dmalloc(&h->d_doc_order, (size_t)h->M)) || (rc = dmalloc(&h->d_partial, (size_t)TMVB_REDUCE_BLOCKS * K)) ||
-        (rc = dmalloc(&h->d_rowsum, K)) || (rc = dmalloc(&h->d_esum, K)) ||  (rc = dmalloc(&h->d_doc_val, (size_t)h->M)) ||
-        (rc = dmalloc(&h->d_elbo, 1)) || (rc = dmalloc(&h->d_iters, 1)) || (rc = dmalloc(&h->d_wtok, tmvb_termstats_recomputes(h->KP, h->KP / 4 <= 64) ? (size_t)1 : (size_t)corp->info.nnz)) ||   // stored weights: K > 128 only
+    if ((rc = h->mem.alloc(&h->d_alpha_d, K)) || (rc = h->mem.alloc(&h->d_alpha_f, K)) || (rc = h->mem.alloc(&h->d_beta[0], KPV)) ||
+        (rc = h->mem.alloc(&h->d_beta[1], KPV)) || (rc = h->mem.alloc(&h->d_stats, KV + K)) || (rc = h->mem.alloc(&h->d_gamma, KM)) ||
+        (rc = h->mem.alloc(&h->d_elog, KM)) || (rc = h->mem.alloc(&h->d_elog_old, KM)) || (rc = h->mem.alloc(&h->d_sweeps, (size_t)h->M)) ||
+        (rc = h->mem.alloc(&h->d_doc_order, (size_t)h->M)) || (rc = h->mem.alloc(&h->d_partial, (size_t)TMVB_REDUCE_BLOCKS * K)) ||
+        (rc = h->mem.alloc(&h->d_rowsum, K)) || (rc = h->mem.alloc(&h->d_esum, K)) ||  (rc = h->mem.alloc(&h->d_doc_val, (size_t)h->M)) ||
+        (rc = h->mem.alloc(&h->d_elbo, 1)) || (rc = h->mem.alloc(&h->d_iters, 1)) || (rc = h->mem.alloc(&h->d_wtok, tmvb_termstats_recomputes(h->KP, h->KP / 4 <= 64) ? (size_t)1 : (size_t)corp->info.nnz)) ||   // stored weights: K > 128 only
        
-        (rc = dmalloc(&h->d_E, (size_t)((h->KP + 31) / 32 * 32) * h->M + 4))) {
+        (rc = h->mem.alloc(&h->d_E, (size_t)((h->KP + 31) / 32 * 32) * h->M + 4))) {
         return rc;
     }
     h->reg_path = (K <= 128) && lda_reg_lpr_supported(h->KP / 4);
     if (h->reg_path) {
         std::vector<int> tol, lot;
         tmvb_reg_lane_maps(h->KP, tol, lot);
-        if ((rc = dmalloc(&h->d_topic_of_lane, tol.size()))) return rc;
+        if ((rc = h->mem.alloc(&h->d_topic_of_lane, tol.size()))) return rc;
         TMVB_HIP(hipMemcpy(h->d_topic_of_lane, tol.data(), tol.size() * sizeof(int), hipMemcpyHostToDevice));
     }
     // grid-tile kernel (tmvb_gridtile.h): KP <= 100 (LPR <= 25; up to 6 / 4 / 3 token pairs per lane for KP <= 60 / 76 / 100 within 256 VGPRs), statistics pass
@@ -1480,7 +1413,7 @@ extern "C" int tmvb_lda_create(tmvb_ctx* ctx, tmvb_corpus* corp, int32_t K, tmvb
             default: h->grid_path = false;
         }
         if (h->grid_path) {
-            if ((rc = dmalloc(&h->d_grid_topic_of_lane, tol.size()))) return rc;
+            if ((rc = h->mem.alloc(&h->d_grid_topic_of_lane, tol.size()))) return rc;
             TMVB_HIP(hipMemcpy(h->d_grid_topic_of_lane, tol.data(), tol.size() * sizeof(int), hipMemcpyHostToDevice));
         }
     }
@@ -1516,32 +1449,27 @@ extern "C" int tmvb_lda_create(tmvb_ctx* ctx, tmvb_corpus* corp, int32_t K, tmvb
             for (int q = 0; q < P && !rc; ++q) {
                 if (prc[(size_t)q]) { rc = prc[(size_t)q]; tmvb_set_error("%s", pmsg[(size_t)q].c_str()); break; }
                 slots = std::max(slots, (size_t)h->pieces[q].n_slots);
-                if (hipEventCreateWithFlags(&h->ev_piece[q], tmvb_event_flags()) != hipSuccess) rc = TMVB_EHIP;
+                rc = h->mem.event(&h->ev_piece[q], tmvb_event_flags());
             }
         } else {
             rc = tmvb_corpus_term_index(corp);
             slots = (size_t)corp->term_index.n_slots;
             h->ev_piece.assign(1, nullptr);
-            if (!rc && hipEventCreateWithFlags(&h->ev_piece[0], tmvb_event_flags()) != hipSuccess) rc = TMVB_EHIP;
+            if (!rc) rc = h->mem.event(&h->ev_piece[0], tmvb_event_flags());
         }
-        if (!rc) rc = dmalloc(&h->d_ts_partial, slots * (K + 1));
+        if (!rc) rc = h->mem.alloc(&h->d_ts_partial, slots * (K + 1));
         if (rc) return rc;
     }
     if (h->M) TMVB_HIP(hipMemcpyAsync(h->d_doc_order, order.data(), (size_t)h->M * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
     TMVB_HIP(hipMemsetAsync(h->d_stats, 0, (KV + K) * sizeof(float), ctx->stream));
     TMVB_HIP(hipMemsetAsync(h->d_sweeps, 0, std::max<size_t>((size_t)h->M, 1), ctx->stream));
     h->timing = tmvb_env_on("TMVB_ESTEP_TIMING", false);
-    TMVB_HIP(hipEventCreate(&h->ev0));
-    TMVB_HIP(hipEventCreate(&h->ev1));
-    TMVB_HIP(hipEventCreateWithFlags(&h->ev_fork, tmvb_event_flags()));
-    TMVB_HIP(hipEventCreateWithFlags(&h->ev_docs, tmvb_event_flags()));
-    TMVB_HIP(hipEventCreateWithFlags(&h->ev_side, tmvb_event_flags()));
-    TMVB_HIP(hipEventCreateWithFlags(&h->ev_chain, tmvb_event_flags()));
-    TMVB_HIP(hipEventCreateWithFlags(&h->ev_acopy, tmvb_event_flags()));
-    TMVB_HIP(hipEventCreateWithFlags(&h->ev_elbo, tmvb_event_flags()));
-    TMVB_HIP(hipEventCreateWithFlags(&h->ev_mark, hipEventDisableTiming /* may sit behind a collective: keeps the system-scope fence */));
+    if ((rc = h->mem.event(&h->ev0, hipEventDefault)) || (rc = h->mem.event(&h->ev1, hipEventDefault))) return rc;
+    for (hipEvent_t* e : {&h->ev_fork, &h->ev_docs, &h->ev_side, &h->ev_chain, &h->ev_acopy, &h->ev_elbo})
+        if ((rc = h->mem.event(e, tmvb_event_flags()))) return rc;
+    if ((rc = h->mem.event(&h->ev_mark, hipEventDisableTiming /* may sit behind a collective: keeps the system-scope fence */))) return rc;
     h->parts_env = tmvb_env_int("TMVB_LDA_ELBO_PARTS", 1);
-    if ((rc = dmalloc(&h->d_partial_side, (size_t)TMVB_REDUCE_BLOCKS * K)) || (rc = dmalloc(&h->d_pw_partial, 2048)) || (rc = dmalloc(&h->d_lz_partial, 2048)) || (rc = dmalloc(&h->d_alpha_e, (size_t)K))) return rc;
+    if ((rc = h->mem.alloc(&h->d_partial_side, (size_t)TMVB_REDUCE_BLOCKS * K)) || (rc = h->mem.alloc(&h->d_pw_partial, 2048)) || (rc = h->mem.alloc(&h->d_lz_partial, 2048)) || (rc = h->mem.alloc(&h->d_alpha_e, (size_t)K))) return rc;
     // Round 7: in the three-piece plan aux[1] (the long documents, then the side chain: Elogtheta column sums and update_alpha!) is a HIGH-PRIORITY stream.
     // In a process started with GPU_MAX_HW_QUEUES=4 the kernel trace shows aux[1]'s kernels on the context stream's hardware queue: the long documents' kernels
     // in front of the chain's first, the side chain in a row with update_beta! (profiles/r7_lda_k50_timeline_before.txt).  As a high-priority stream it is on
@@ -1549,9 +1477,7 @@ extern "C" int tmvb_lda_create(tmvb_ctx* ctx, tmvb_corpus* corp, int32_t K, tmvb
     // measured 0.65 % slower with it and keeps a normal stream (profiles/r7_lda_tail_bench.json).  TMVB_LDA_SIDE_PRIORITY=0: a normal-priority stream everywhere.
     const bool side_priority = h->pieces.size() >= 3 && tmvb_env_on("TMVB_LDA_SIDE_PRIORITY", true);
     for (int a = 0; a < tmvb_lda::NAUX; ++a) {
-        h->aux[a] = tmvb_pool_stream(ctx->device, 1 + a, a == 1 && side_priority);
-        TMVB_REQUIRE(h->aux[a] != nullptr, TMVB_EHIP, "hipStreamCreate failed");
-        TMVB_HIP(hipEventCreateWithFlags(&h->ev_join[a], tmvb_event_flags()));
+        if ((rc = h->mem.aux(&h->aux[a], ctx->device, 1 + a, a == 1 && side_priority)) || (rc = h->mem.event(&h->ev_join[a], tmvb_event_flags()))) return rc;
     }
     TMVB_HIP(hipMemsetAsync(h->d_beta[0], 0, KPV * sizeof(float), ctx->stream));
     TMVB_HIP(hipMemsetAsync(h->d_beta[1], 0, KPV * sizeof(float), ctx->stream));
@@ -1586,10 +1512,10 @@ extern "C" int tmvb_lda_set_state(tmvb_lda* h, const double* alpha, const double
         if ((rc = upload_f32(ctx, h->d_alpha_f, alpha, K))) return rc;
     }
     if (beta) {
-        if ((rc = upload_beta(h, h->d_beta[h->cur], beta))) return rc;
-        if (!beta_old && (rc = upload_beta(h, h->d_beta[h->cur ^ 1], beta))) return rc;
+        if ((rc = tmvb_model_upload_beta(h, h->d_beta[h->cur], beta))) return rc;
+        if (!beta_old && (rc = tmvb_model_upload_beta(h, h->d_beta[h->cur ^ 1], beta))) return rc;
     }
-    if (beta_old && (rc = upload_beta(h, h->d_beta[h->cur ^ 1], beta_old))) return rc;
+    if (beta_old && (rc = tmvb_model_upload_beta(h, h->d_beta[h->cur ^ 1], beta_old))) return rc;
     if (gamma && (rc = upload_f32(ctx, h->d_gamma, gamma, KM))) return rc;
     if (Elogtheta) {
         if ((rc = upload_f32(ctx, h->d_elog, Elogtheta, KM))) return rc;
@@ -1615,8 +1541,8 @@ extern "C" int tmvb_lda_get_state(tmvb_lda* h, double* alpha, double* beta, doub
         TMVB_HIP(hipMemcpyAsync(alpha, h->d_alpha_d, K * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
         TMVB_HIP(hipStreamSynchronize(ctx->stream));
     }
-    if (beta && (rc = download_beta(h, beta, h->d_beta[h->cur]))) return rc;
-    if (beta_old && (rc = download_beta(h, beta_old, h->d_beta[h->cur ^ 1]))) return rc;
+    if (beta && (rc = tmvb_model_download_beta(h, beta, h->d_beta[h->cur]))) return rc;
+    if (beta_old && (rc = tmvb_model_download_beta(h, beta_old, h->d_beta[h->cur ^ 1]))) return rc;
     if (gamma && (rc = download_f32(ctx, gamma, h->d_gamma, KM))) return rc;
     if (Elogtheta && (rc = download_f32(ctx, Elogtheta, h->d_elog, KM))) return rc;
     if (Elogtheta_old && (rc = download_f32(ctx, Elogtheta_old, h->d_elog_old, KM))) return rc;
@@ -1739,9 +1665,9 @@ static int lda_estep_impl(tmvb_lda* h, int32_t viter, double vtol)
     if (collect) {
         for (int q = 0; q < P; ++q) logz_off[(size_t)q + 1] = logz_off[(size_t)q] + stats_index(q).n_chunks;
         const size_t need = (size_t)std::max<int64_t>(logz_off[(size_t)P], 1);
-        if (need > h->logz_cap) {                                 // (first checked iteration of a plan; hipFree synchronises)
-            (void)hipFree(h->d_logz); h->d_logz = nullptr; h->logz_cap = 0;
-            int arc = dmalloc(&h->d_logz, need);
+        if (need > h->logz_cap) {                                 // (first checked iteration of a plan; the drop synchronises)
+            h->mem.drop(&h->d_logz); h->logz_cap = 0;
+            int arc = h->mem.alloc(&h->d_logz, need);
             if (arc) return arc;
             h->logz_cap = need;
         }
@@ -1762,8 +1688,8 @@ static int lda_estep_impl(tmvb_lda* h, int32_t viter, double vtol)
     if (split_out && !h->d_stats_b) {
         size_t slots = 1;
         for (const tmvb_inv_index& ix : h->pieces) slots = std::max(slots, (size_t)ix.n_slots);
-        int arc = dmalloc(&h->d_stats_b, (size_t)h->K * h->V);
-        if (!arc) arc = dmalloc(&h->d_ts_partial_b, slots * (size_t)(h->K + 1));
+        int arc = h->mem.alloc(&h->d_stats_b, (size_t)h->K * h->V);
+        if (!arc) arc = h->mem.alloc(&h->d_ts_partial_b, slots * (size_t)(h->K + 1));
         if (arc) return arc;
         TMVB_HIP(hipMemsetAsync(h->d_stats_b, 0, (size_t)h->K * h->V * sizeof(float), ctx->stream));
     }
@@ -1974,17 +1900,13 @@ static int lda_ar_prepare(tmvb_lda* h)
     std::vector<double> cnt((size_t)V, 0.0);
     for (int32_t t : h->corp->h_terms) cnt[(size_t)t] += 1.0;
     {   // the collective every rank takes part in, sliced or not (a rank must not decide alone)
+        tmvb_call c("tmvb_lda_estep_allreduce", ctx->device, ctx->stream);
         double* d = nullptr;
-        int rc = dmalloc(&d, (size_t)V);
-        if (rc) return rc;
-        hipError_t e = hipMemcpyAsync(d, cnt.data(), (size_t)V * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e == hipSuccess) rc = tmvb_comm_allreduce(h->comm, d, V, TMVB_F64);
-        if (e == hipSuccess && !rc) e = hipMemcpyAsync(cnt.data(), d, (size_t)V * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess && !rc) e = hipStreamSynchronize(ctx->stream);
-        (void)hipFree(d);
-        if (rc) return rc;
-        TMVB_HIP(e);
+        TMVB_CALL_TRY(c, c.upload(&d, (const double*)cnt.data(), (size_t)V));
+        TMVB_CALL_HIP(c, hipStreamSynchronize(ctx->stream));
+        TMVB_CALL_TRY(c, tmvb_comm_allreduce(h->comm, d, V, TMVB_F64));
+        TMVB_CALL_HIP(c, hipMemcpyAsync(cnt.data(), d, (size_t)V * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        TMVB_CALL_HIP(c, hipStreamSynchronize(ctx->stream));
     }
     {   // cuts and order from the GLOBAL counts: a host function of its own (tmvb_allreduce_plan, tmvb_comm.hip), tested on the CPU
         std::vector<int64_t> cuts((size_t)S + 1);
@@ -2011,7 +1933,7 @@ static int lda_ar_prepare(tmvb_lda* h)
                      (long long)slot.n_slots, (long long)old_slots);
         while ((int)h->ev_slice.size() < S) {
             hipEvent_t ev = nullptr;
-            TMVB_HIP(hipEventCreateWithFlags(&ev, h->events_system_scope ? (unsigned)hipEventDisableTiming : tmvb_event_flags()));
+            if ((rc = h->mem.event(&ev, h->events_system_scope ? (unsigned)hipEventDisableTiming : tmvb_event_flags()))) return rc;
             h->ev_slice.push_back(ev);
         }
     }
@@ -2046,8 +1968,8 @@ extern "C" int tmvb_lda_estep_allreduce(tmvb_lda* h, int32_t viter, double vtol)
     hipStream_t cs = h->aux[tmvb_lda::AR];
     // the two events recorded BEHIND collectives keep the default system-scope fence: what they order was written with the help of other
     // devices (the ordering events of the single-device plans do without it, tmvb_event_flags)
-    if (!h->ev_comm) TMVB_HIP(hipEventCreateWithFlags(&h->ev_comm, hipEventDisableTiming));
-    if (!h->ev_tail) TMVB_HIP(hipEventCreateWithFlags(&h->ev_tail, hipEventDisableTiming));
+    if (!h->ev_comm && (rc = h->mem.event(&h->ev_comm, hipEventDisableTiming))) return rc;
+    if (!h->ev_tail && (rc = h->mem.event(&h->ev_tail, hipEventDisableTiming))) return rc;
     if (tail_on_side) {
         TMVB_HIP(hipStreamWaitEvent(cs, h->ev_side, 0));                  // NOT the context's stream: the statistics pass is queued on it
     } else {
@@ -2084,19 +2006,13 @@ extern "C" int tmvb_lda_stats(tmvb_lda* h, void** dev_ptr, int64_t* n_f32)
 
 extern "C" int tmvb_lda_bind_stats(tmvb_lda* h, void* dev_ptr, int64_t n_f32)
 {
-    TMVB_REQUIRE(h && dev_ptr, TMVB_EINVAL, "tmvb_lda_bind_stats: NULL argument");
-    const int64_t need = (int64_t)h->K * h->V + h->K;
-    TMVB_REQUIRE(n_f32 >= need, TMVB_ESHAPE, "tmvb_lda_bind_stats: buffer holds %lld floats, need %lld", (long long)n_f32, (long long)need);
-    h->mark_valid = false;
-    TMVB_HIP(hipSetDevice(h->ctx->device));
-    { int jrc = lda_join_side(h); if (jrc) return jrc; }
-    { int mrc = lda_merge_stats(h); if (mrc) return mrc; }
-    TMVB_HIP(hipMemcpyAsync(dev_ptr, h->d_stats, (size_t)need * sizeof(float), hipMemcpyDeviceToDevice, h->ctx->stream));
-    TMVB_HIP(hipStreamSynchronize(h->ctx->stream));
-    if (h->own_stats) (void)hipFree(h->d_stats);
-    h->d_stats = (float*)dev_ptr;
-    h->own_stats = false;
-    return TMVB_OK;
+    const int rc = tmvb_model_bind_stats("tmvb_lda_bind_stats", h, dev_ptr, n_f32, h ? (int64_t)h->K * h->V + h->K : 0, [&]() -> int {
+        h->mark_valid = false;
+        const int jrc = lda_join_side(h);
+        return jrc ? jrc : lda_merge_stats(h);
+    });
+    if (!rc) h->own_stats = false;
+    return rc;
 }
 
 extern "C" int tmvb_lda_set_distributed(tmvb_lda* h, int64_t M_total, int32_t distributed)
@@ -2271,15 +2187,11 @@ extern "C" int tmvb_lda_set_comm(tmvb_lda* h, tmvb_comm* comm, int64_t M_total)
         TMVB_HIP(hipSetDevice(h->ctx->device));
         TMVB_HIP(hipStreamSynchronize(h->ctx->stream));
         for (int a = 0; a < tmvb_lda::NAUX; ++a) if (h->aux[a]) TMVB_HIP(hipStreamSynchronize(h->aux[a]));
-        auto remake = [](hipEvent_t& ev) -> hipError_t {
-            if (!ev) return hipSuccess;
-            (void)hipEventDestroy(ev); ev = nullptr;
-            return hipEventCreateWithFlags(&ev, hipEventDisableTiming);
-        };
-        TMVB_HIP(remake(h->ev_fork)); TMVB_HIP(remake(h->ev_docs)); TMVB_HIP(remake(h->ev_side)); TMVB_HIP(remake(h->ev_chain));
-        for (int a = 0; a < tmvb_lda::NAUX; ++a) TMVB_HIP(remake(h->ev_join[a]));
-        for (hipEvent_t& ev : h->ev_piece) TMVB_HIP(remake(ev));
-        for (hipEvent_t& ev : h->ev_slice) TMVB_HIP(remake(ev));
+        std::vector<hipEvent_t*> evs = {&h->ev_fork, &h->ev_docs, &h->ev_side, &h->ev_chain};
+        for (hipEvent_t& ev : h->ev_join) evs.push_back(&ev);
+        for (hipEvent_t& ev : h->ev_piece) evs.push_back(&ev);
+        for (hipEvent_t& ev : h->ev_slice) evs.push_back(&ev);
+        for (hipEvent_t* ev : evs) if ((rc = h->mem.remake(ev, hipEventDisableTiming))) return rc;
         h->side_pending = false; h->mark_valid = false; h->elbo_pending = false;
         h->events_system_scope = true;
     }
@@ -2287,28 +2199,17 @@ extern "C" int tmvb_lda_set_comm(tmvb_lda* h, tmvb_comm* comm, int64_t M_total)
 }
 
 namespace {
-struct LdaTrainOps {
+struct LdaTrainOps : tmvb_base_train_ops<tmvb_lda> {
     int niter, viter; double ntol, vtol;
     int estep(tmvb_lda* h) { return tmvb_lda_estep(h, viter, vtol); }                 // src/LDA.jl:170-180
     int reduce(tmvb_lda* h) { return tmvb_lda_reduce_docs(h); }                       // :98
     int estep_allreduce(tmvb_lda* h) { return tmvb_lda_estep_allreduce(h, viter, vtol); }   // one process per GPU: the three steps with the collective sliced
     int before_allreduce(tmvb_lda* h) { TMVB_HIP(hipSetDevice(h->ctx->device)); int rc = lda_join_side(h); return rc ? rc : lda_merge_stats(h); }
-    float* stats(tmvb_lda* h) { return h->d_stats; }
     int64_t stats_len(tmvb_lda* h) { return (int64_t)h->K * h->V + h->K; }
     int mstep(tmvb_lda* h) { int rc = tmvb_lda_update_beta(h); return rc ? rc : tmvb_lda_update_alpha(h, niter, ntol); }   // :181-182
-    int elbo_form(tmvb_lda* h) { return h->elbo_form; }
-    void force_walk(tmvb_lda* h, bool on, bool doubled = true) { h->force_walk = on; if (!on && doubled) h->elbo_form = 1; }   // (switched off behind the one evaluation that doubled a decomposed one)
-    void will_check(tmvb_lda* h, bool checked) { h->want_parts = checked; }           // the coming iteration ends in check_elbo!: collect update_elbo!'s parts on the way
     int elbo_local(tmvb_lda* h, double* s, double* once) { *once = 0.0; return tmvb_lda_update_elbo(h, s); }
     int elbo_enqueue(tmvb_lda* h, double* once) { *once = 0.0; TMVB_HIP(hipSetDevice(h->ctx->device)); return lda_elbo_enqueue(h); }   // -> elbo_dev(h), no sync
-    double* elbo_dev(tmvb_lda* h) { return h->d_elbo; }
-    tmvb_comm* comm(tmvb_lda* h) { return h->comm; }
-    bool distributed(tmvb_lda* h) { return h->distributed; }
-    tmvb_ctx* ctx(tmvb_lda* h) { return h->ctx; }
-    int64_t nnz(tmvb_lda* h) { return h->corp->info.nnz; }
-    void set_elbo(tmvb_lda* h, double v) { h->elbo = v; }
-    double get_elbo(tmvb_lda* h) { return h->elbo; }
-    int finish(tmvb_lda* h)
+    int finish(tmvb_lda* h)                                                           // joins the side chain first
     {
         TMVB_HIP(hipSetDevice(h->ctx->device));
         int rc = lda_join_side(h);
@@ -2325,7 +2226,7 @@ extern "C" int tmvb_lda_train_group(tmvb_lda* const* hs, int32_t n, int32_t iter
     // src/gpuLDA.jl:349-351
     TMVB_REQUIRE(tol >= 0 && ntol >= 0 && vtol >= 0, TMVB_EINVAL, "tolerance parameters must be nonnegative.");
     TMVB_REQUIRE(iter >= 0 && niter >= 0 && viter >= 0, TMVB_EINVAL, "iteration parameters must be nonnegative.");
-    LdaTrainOps ops{niter, viter, ntol, vtol};
+    LdaTrainOps ops{{}, niter, viter, ntol, vtol};
     return tmvb_train_group_loop("tmvb_lda_train", hs, n, iter, tol, checkelbo, elbo_traj, iters_done, elbo_baseline, ops);
 }
 
@@ -2336,35 +2237,9 @@ extern "C" int tmvb_lda_train(tmvb_lda* h, int32_t iter, double tol, int32_t nit
     return tmvb_lda_train_group(&h, 1, iter, tol, niter, ntol, viter, vtol, checkelbo, elbo_traj, iters_done, elbo_baseline);
 }
 
-extern "C" int tmvb_lda_elbo_form(tmvb_lda* h, int32_t* form)
-{
-    TMVB_REQUIRE(h && form, TMVB_EINVAL, "tmvb_lda_elbo_form: NULL argument");
-    *form = h->elbo_form;
-    return TMVB_OK;
-}
-
-// per-document sweep counts of the last E-step (document order of the corpus), for parity tests that compare the
-// state of exactly those documents whose exit sweep agrees with the oracle's
-extern "C" int tmvb_lda_doc_sweeps(tmvb_lda* h, uint8_t* out)
-{
-    TMVB_REQUIRE(h && (out || h->M == 0), TMVB_EINVAL, "tmvb_lda_doc_sweeps: NULL argument");
-    TMVB_HIP(hipSetDevice(h->ctx->device));
-    if (h->M) TMVB_HIP(hipMemcpyAsync(out, h->d_sweeps, (size_t)h->M, hipMemcpyDeviceToHost, h->ctx->stream));
-    TMVB_HIP(hipStreamSynchronize(h->ctx->stream));
-    return TMVB_OK;
-}
-
-extern "C" int tmvb_lda_sweep_hist(tmvb_lda* h, int64_t* hist, int32_t nbins)
-{
-    TMVB_REQUIRE(h && hist && nbins > 0, TMVB_EINVAL, "tmvb_lda_sweep_hist: bad argument");
-    std::vector<uint8_t> sw((size_t)h->M);
-    TMVB_HIP(hipSetDevice(h->ctx->device));
-    if (h->M) TMVB_HIP(hipMemcpyAsync(sw.data(), h->d_sweeps, (size_t)h->M, hipMemcpyDeviceToHost, h->ctx->stream));
-    TMVB_HIP(hipStreamSynchronize(h->ctx->stream));
-    for (int b = 0; b < nbins; ++b) hist[b] = 0;
-    for (uint8_t s : sw) hist[std::min<int>(s, nbins - 1)]++;
-    return TMVB_OK;
-}
+extern "C" int tmvb_lda_elbo_form(tmvb_lda* h, int32_t* form) { return tmvb_model_elbo_form("tmvb_lda_elbo_form", h, form); }
+extern "C" int tmvb_lda_doc_sweeps(tmvb_lda* h, uint8_t* out) { return tmvb_model_doc_sweeps("tmvb_lda_doc_sweeps", h, out); }
+extern "C" int tmvb_lda_sweep_hist(tmvb_lda* h, int64_t* hist, int32_t nbins) { return tmvb_model_sweep_hist("tmvb_lda_sweep_hist", h, hist, nbins); }
 
 extern "C" int tmvb_lda_estep_launches(tmvb_lda* h, int32_t* n)
 {
@@ -2381,16 +2256,7 @@ extern "C" int tmvb_lda_estep_pieces(tmvb_lda* h, int32_t* pieces)
     return TMVB_OK;
 }
 
-extern "C" int tmvb_lda_last_estep_ms(tmvb_lda* h, float* ms)
-{
-    TMVB_REQUIRE(h && ms, TMVB_EINVAL, "tmvb_lda_last_estep_ms: NULL argument");
-    TMVB_REQUIRE(h->timing, TMVB_EINVAL, "tmvb_lda_last_estep_ms: E-step timing is off (set TMVB_ESTEP_TIMING=1 before creating the model)");
-    TMVB_REQUIRE(h->timed, TMVB_EINVAL, "tmvb_lda_last_estep_ms: no E-step has run");
-    TMVB_HIP(hipSetDevice(h->ctx->device));
-    TMVB_HIP(hipEventSynchronize(h->ev1));
-    TMVB_HIP(hipEventElapsedTime(ms, h->ev0, h->ev1));
-    return TMVB_OK;
-}
+extern "C" int tmvb_lda_last_estep_ms(tmvb_lda* h, float* ms) { return tmvb_model_last_estep_ms("tmvb_lda_last_estep_ms", h, ms, true); }
 
 // ---- stochastic training (tmvb_lda_svi.hip): the additive hooks a driver over per-batch handles needs.  None of them is reached from the entry points above.
 // h gives up its own alpha / beta pair and auxiliary streams and uses `owner`'s from here on (same context, K and V): the batch handles of one driver run one
@@ -2404,11 +2270,11 @@ int tmvb_lda_share_globals(tmvb_lda* h, tmvb_lda* owner)
     { int jrc = lda_join_side(h); if (jrc) return jrc; }
     for (int a = 0; a < tmvb_lda::NAUX; ++a) TMVB_HIP(hipStreamSynchronize(h->aux[a]));
     TMVB_HIP(hipStreamSynchronize(h->ctx->stream));
-    (void)hipFree(h->d_alpha_d); (void)hipFree(h->d_alpha_f); (void)hipFree(h->d_beta[0]); (void)hipFree(h->d_beta[1]);
+    h->mem.drop(&h->d_alpha_d); h->mem.drop(&h->d_alpha_f); h->mem.drop(&h->d_beta[0]); h->mem.drop(&h->d_beta[1]);
     h->d_alpha_d = owner->d_alpha_d; h->d_alpha_f = owner->d_alpha_f; h->d_beta[0] = owner->d_beta[0]; h->d_beta[1] = owner->d_beta[1];
     h->cur = owner->cur;
     h->own_globals = false;
-    for (int a = 0; a < tmvb_lda::NAUX; ++a) { tmvb_release_stream(h->aux[a]); h->aux[a] = owner->aux[a]; }
+    for (int a = 0; a < tmvb_lda::NAUX; ++a) h->mem.borrow(&h->aux[a], owner->aux[a]);
     h->own_aux = false;
     return TMVB_OK;
 }

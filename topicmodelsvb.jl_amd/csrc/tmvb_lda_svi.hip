@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "tmvb_internal.h"
+#include "tmvb_handle.h"
 #include "tmvb_common_kernels.h"
 #include "tmvb_svi_kernels.h"
 
@@ -43,6 +44,7 @@ struct tmvb_lda_svi {
     bool timing = false;               // TMVB_ESTEP_TIMING=1 at create: four events per step of the last run
     std::vector<hipEvent_t> ev;
     int64_t timed_steps = 0;
+    tmvb_owned mem;                    // the driver's own buffers and events (tmvb_handle.h)
 };
 
 extern "C" int tmvb_lda_svi_destroy(tmvb_lda_svi* h)
@@ -51,8 +53,7 @@ extern "C" int tmvb_lda_svi_destroy(tmvb_lda_svi* h)
     if (h->ctx) { (void)hipSetDevice(h->ctx->device); (void)hipStreamSynchronize(h->ctx->stream); }
     for (size_t b = h->hs.size(); b-- > 0;) (void)tmvb_lda_destroy(h->hs[b]);          // the first handle owns what the others share: last
     for (tmvb_corpus* c : h->corps) (void)tmvb_corpus_destroy(c);
-    (void)hipFree(h->d_sb); (void)hipFree(h->d_sbar); (void)hipFree(h->d_ebar); (void)hipFree(h->d_partial);
-    for (hipEvent_t e : h->ev) if (e) (void)hipEventDestroy(e);
+    if (h->ctx) h->mem.release(h->ctx->device, h->ctx->stream);
     delete h;
     return TMVB_OK;
 }
@@ -83,7 +84,7 @@ extern "C" int tmvb_lda_svi_create(tmvb_ctx* ctx, int64_t M, int64_t V, const in
         h->cuts.assign(cuts, cuts + B + 1);
         const size_t KV = (size_t)K * (size_t)V;
         const size_t nbmax = std::max<size_t>(SVI_BLEND_BLOCKS, ((size_t)K + SVI_WG - 1) / SVI_WG);
-        if ((rc = dmalloc(&h->d_sb, KV + K)) || (rc = dmalloc(&h->d_sbar, KV)) || (rc = dmalloc(&h->d_ebar, (size_t)K)) || (rc = dmalloc(&h->d_partial, nbmax * K))) return rc;
+        if ((rc = h->mem.alloc(&h->d_sb, KV + K)) || (rc = h->mem.alloc(&h->d_sbar, KV)) || (rc = h->mem.alloc(&h->d_ebar, (size_t)K)) || (rc = h->mem.alloc(&h->d_partial, nbmax * K))) return rc;
         TMVB_HIP(hipMemsetAsync(h->d_sb, 0, (KV + K) * sizeof(float), ctx->stream));
         TMVB_HIP(hipMemsetAsync(h->d_sbar, 0, KV * sizeof(float), ctx->stream));
         TMVB_HIP(hipMemsetAsync(h->d_ebar, 0, (size_t)K * sizeof(float), ctx->stream));
@@ -233,7 +234,7 @@ extern "C" int tmvb_lda_svi_run(tmvb_lda_svi* h, const int32_t* batches, int64_t
     if (h->timing) {
         while ((int64_t)h->ev.size() < 4 * n) {
             hipEvent_t e = nullptr;
-            TMVB_HIP(hipEventCreateWithFlags(&e, hipEventDisableSystemFence));
+            if ((rc = h->mem.event(&e, hipEventDisableSystemFence))) return rc;
             h->ev.push_back(e);
         }
         h->timed_steps = 0;
