@@ -1092,6 +1092,69 @@ int tmvb_ctm_svi_doc_sweeps(tmvb_ctm_svi* h, uint8_t* out);
  * *steps steps of the E-step (src/CTM.jl:194-205), the fused update (blend + normalise + tail) and update_sigma! + update_mu! (:207-208), in ms. */
 int tmvb_ctm_svi_last_run_ms(tmvb_ctm_svi* h, float* ms_estep, float* ms_update, float* ms_sigma_mu, int64_t* steps);
 
+/* ============================== compare topics: divergences, assignment, relevant terms ==============================
+ * The topic side of a trained model (the reference has no such functions): how far apart are the rows of one or two K x V topic-word matrices
+ * (near-duplicate topics, matching the topics of two runs: gensim's LdaModel.diff), and which terms say what a topic is about (the relevance
+ * ranking of LDAvis, Sievert & Shirley 2014; distinctiveness and saliency of Chuang et al. 2012).
+ *
+ * ---- tmvb_topic_divergence.  a is column-major KA x V fp64 on the HOST, the layout of beta in tmvb_topic_order: row i is a[i + KA w].  b is
+ * KB x V likewise, or NULL: then b = a and KB is ignored.  D[i KB + j] (row-major, fp64) is the divergence of row i of a from row j of b.
+ * Arithmetic, all fp64, every operation rounded on its own (no fused multiply-add).  With p = a_iw, q = b_jw, s = p + q the term of w is
+ *   TMVB_TD_JS         0.5 * (x + y),  x = p > 0 ? p * log((2 * p) / s) : 0,  y = q > 0 ? q * log((2 * q) / s) : 0;     D = max(0, sum)
+ *   TMVB_TD_HELLINGER  0.5 * (d * d),  d = sqrt(p) - sqrt(q), the roots correctly rounded;                              D = sqrt(sum)
+ *   TMVB_TD_TV         0.5 * |p - q|;                                                                                   D = sum
+ *   TMVB_TD_KL         p' > 0 ? p' * log(p' / q') : 0,  p' = (p + smooth) / (1 + (double)V * smooth), q' likewise; the term is +inf where
+ *                      q' = 0 < p';                                                                                      D = max(0, sum)
+ * log is the device's fp64 logarithm (within 1 ulp, log(1) = 0 exactly); smooth must be 0 for the other three metrics.
+ * Order of every sum: the terms are cut into runs of TMVB_TD_RUN consecutive w, ascending; each run is summed sequentially ascending from 0;
+ * the run sums are added sequentially ascending from 0.
+ * Purity: the result is a pure function of the inputs.  It does not depend on `splits` (0 = the library's choice: the runs are cut into groups
+ * of whole runs only when there are too few pair tiles to fill the device; > 0 forces that many groups, for tests), on tile sizes or on the order
+ * in which workgroups finish; two calls give the same bytes; rows [i0, i1) of a call equal the call on that slice of a.  No floating-point
+ * atomics.  Bit for bit: D(i, j) = 0 when the two rows are equal ((2 p) / (p + p) is exactly 1); for JS, HELLINGER and TV D[i][j] of (a, b)
+ * equals D[j][i] of (b, a), and with b == NULL their matrix is symmetric (tiles below the diagonal are mirrored, not computed).
+ * Device path: a prep kernel transposes each operand to row-major rows padded with zeros to whole runs (HELLINGER: sqrt, KL: the smoothing,
+ * once per element); the pair kernel is register-tiled like a GEMM -- a workgroup owns 32 x 32 pairs and a group of whole runs, stages the two
+ * row panels through LDS (fp64, padded rows, one 16-byte load per lane), each thread keeps 2 x 2 pair sums in registers and walks the run in
+ * ascending w --; with more than one group it stores one sum per run and a merge kernel adds them in order.
+ * info (or NULL): splits = groups used, runs, ms_prep / ms_pairs / ms_merge = device time of the kernels (HIP events around the kernels only).
+ * Errors, judged before the device is touched: KA or KB outside [1, TMVB_TD_KMAX], V <= 0, KA V or KB V >= 2^31, an unknown metric, splits < 0
+ * or greater than the number of runs, smooth negative or not finite or nonzero for a metric other than KL, a or D NULL -> TMVB_EINVAL; a
+ * non-finite or negative entry, a row sum off 1 by more than 1e-6 -> TMVB_ESHAPE; then ctx == NULL without a visible device ->
+ * TMVB_ENODEVICE (there is no CPU path).
+ *
+ * ---- tmvb_term_relevance.  beta K x V as above, pw[V] the marginal term probabilities, pi[K] the topic shares, lambda in [0, 1], 1 <= n <= V.
+ * r(k, w) = lambda * log(phi) + (1 - lambda) * log(phi / p_w) with phi = beta_kw, fp64, every operation rounded on its own; -inf where phi = 0
+ * or p_w = 0.  Per topic the n best terms under the total order (score descending, term id ascending on equal scores): idx[K][n] (0-based),
+ * score[K][n], count[k] = min(n, number of terms with a finite score); slots past count[k] hold -1 and -inf.  dense (or NULL) receives all
+ * K x V scores, row-major.  The selection is the stable descending segmented radix sort that tmvb_topic_order sorts with.
+ * Per term, when distinct and saliency are given (both or neither): den = sum_j pi_j beta_jw over j ascending from 0; P(k|w) = (pi_k beta_kw) /
+ * den; distinct[w] = sum_k (P > 0 ? P * log(P / pi_k) : 0) over k ascending from 0; saliency[w] = p_w * distinct[w]; both 0 where den = 0.
+ * info (or NULL): ms_score / ms_select / ms_terms = device time of the score kernel, the sort with the selection, and the per-term kernel.
+ * Errors, judged before the device is touched: K outside [1, TMVB_TD_KMAX], V <= 0, K V >= 2^31, lambda outside [0, 1] or not finite, n outside
+ * [1, V], a NULL required argument (everything but dense, distinct, saliency and info), only one of distinct and saliency -> TMVB_EINVAL; a
+ * non-finite or negative entry of beta, pw or pi, a row sum of beta, or the sum of pw or of pi, off 1 by more than 1e-6 -> TMVB_ESHAPE; then
+ * ctx == NULL without a visible device -> TMVB_ENODEVICE.
+ *
+ * ---- tmvb_assignment.  Host only.  cost is row-major n x m, n <= m <= TMVB_TD_KMAX, entries finite or +inf.  A minimum-cost assignment of
+ * every row to a column of its own by shortest augmenting paths, O(n^2 m): row_to_col[n] (0-based), *total (or NULL) = the sum of the chosen
+ * costs over the rows ascending.  n < 1, n > m, m > TMVB_TD_KMAX, a NULL cost or row_to_col -> TMVB_EINVAL; a NaN or -inf cost, or no
+ * assignment of finite cost -> TMVB_ESHAPE. */
+#define TMVB_TD_JS 0                                        /* Jensen-Shannon divergence, nats, in [0, ln 2] */
+#define TMVB_TD_HELLINGER 1                                 /* Hellinger distance, in [0, 1] */
+#define TMVB_TD_TV 2                                        /* total variation, in [0, 1] */
+#define TMVB_TD_KL 3                                        /* KL(a_i || b_j), directed, may be +inf */
+#define TMVB_TD_RUN 256                                     /* terms per fixed-order partial sum */
+#define TMVB_TD_KMAX 4096
+typedef struct { int32_t splits, runs; float ms_prep, ms_pairs, ms_merge; } tmvb_topicdiv_info_t;
+int tmvb_topic_divergence(tmvb_ctx* ctx, int32_t metric, int64_t V, int32_t KA, const double* a, int32_t KB, const double* b,
+                          double smooth, int32_t splits, double* D, tmvb_topicdiv_info_t* info);
+typedef struct { float ms_score, ms_select, ms_terms; } tmvb_relevance_info_t;
+int tmvb_term_relevance(tmvb_ctx* ctx, int32_t K, int64_t V, const double* beta, const double* pw, const double* pi, double lambda,
+                        int32_t n, int32_t* idx, double* score, int32_t* count, double* dense, double* distinct, double* saliency,
+                        tmvb_relevance_info_t* info);
+int tmvb_assignment(int32_t n, int32_t m, const double* cost, int32_t* row_to_col, double* total);
+
 #ifdef __cplusplus
 }
 #endif

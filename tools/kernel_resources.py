@@ -53,6 +53,8 @@ BENCHED = {
     "km_seed_pick_kernel": 0,
     # document map (tools/docmap_bench.py): the entropy search, the all-pairs repulsion and its segment sums, the edge sums (forces and KL), the update
     "map_affinity_kernel": 0, "map_repulse_kernel": 0, "map_finish_kernel": 0, "map_attract_kernel<": 0, "map_update_kernel": 0,
+    # topic comparison (tools/topic_compare_bench.py): the transpose, the fp64 pair kernel under its four metrics, the merge of the run sums; relevance
+    "td_prep_kernel": 0, "td_pairs_kernel<": 0, "td_merge_kernel<": 0, "tr_score_kernel": 0, "tr_select_kernel": 0, "tr_terms_kernel": 0,
     # stochastic LDA training (tools/svi_bench.py): the fused global update -- blend + partial row sums, then normalise
     "svi_blend_kernel<": 0, "svi_norm_kernel": 0,
     # stochastic CTM training (tools/ctm_svi_bench.py): the tail of the fused global update -- recentre in fp64, blend (the K x V part is the two above)

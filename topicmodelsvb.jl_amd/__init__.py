@@ -20,6 +20,9 @@ from .coherence import CoherenceResult, coherence, coherence_from_counts, cohere
 from .neighbors import NeighborsResult, docsim, neighbors_raw, topic_proportions
 from .cluster import ClusterResult, cluster_docs, kmeans_raw
 from .docmap import DocMap, map_affinity_raw, map_docs, map_layout_raw
+from .topic_compare import (RelevantTerms, TopicComparison, TopicMap, TopicStability, assignment_raw, compare_topics, pcoa, relevant_terms,
+                            term_frequencies, term_relevance_raw, topic_distances, topic_divergence_raw, topic_map, topic_share, topic_stability,
+                            topic_word_matrix)
 from .search import SearchInfo, SearchResult, pack_queries, search, search_raw
 from .token_topics import TokenTopics, phi, token_factors, token_topics, token_topics_raw
 from .recs_eval import (HeldReaders, RecEvalResult, rank_metrics, rank_metrics_raw, rec_eval, rec_quality, rec_ranks_raw, split_readers,
@@ -40,6 +43,9 @@ __all__ = ["CorpusError", "DocumentError", "EngineError", "TopicModelError", "bu
            "NeighborsResult", "docsim", "neighbors_raw", "topic_proportions",
            "ClusterResult", "cluster_docs", "kmeans_raw",
            "DocMap", "map_affinity_raw", "map_docs", "map_layout_raw",
+           "RelevantTerms", "TopicComparison", "TopicMap", "TopicStability", "assignment_raw", "compare_topics", "pcoa", "relevant_terms",
+           "term_frequencies", "term_relevance_raw", "topic_distances", "topic_divergence_raw", "topic_map", "topic_share", "topic_stability",
+           "topic_word_matrix",
            "SearchInfo", "SearchResult", "pack_queries", "search", "search_raw",
            "TokenTopics", "phi", "token_factors", "token_topics", "token_topics_raw",
            "HeldReaders", "RecEvalResult", "rank_metrics", "rank_metrics_raw", "rec_eval", "rec_quality", "rec_ranks_raw", "split_readers", "split_readers_raw",

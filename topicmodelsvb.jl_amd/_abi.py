@@ -60,6 +60,8 @@ RecRanksInfo = _struct("RecRanksInfo", "tmvb_recranks_info_t", "i32: splits kp; 
 RecTopNInfo = _struct("RecTopNInfo", "tmvb_rectopn_info_t", "i32: splits kp; f32: ms_prep ms_scan ms_merge")
 FoldinInfo = _struct("FoldinInfo", "tmvb_foldin_info_t", "i32: kp capacity; i64: n_reg n_long; f32: ms_prep ms_sweeps")
 SviInfo = _struct("SviInfo", "tmvb_lda_svi_info_t, tmvb_ctm_svi_info_t", "i32: B K; i64: M V t; f64: tau0 kappa rho; f32: c0 c1")
+TopicDivInfo = _struct("TopicDivInfo", "tmvb_topicdiv_info_t", "i32: splits runs; f32: ms_prep ms_pairs ms_merge")
+RelevanceInfo = _struct("RelevanceInfo", "tmvb_relevance_info_t", "f32: ms_score ms_select ms_terms")
 
 _TABLE = """
 int  tmvb_abi_version()
@@ -228,6 +230,9 @@ int  tmvb_ctm_svi_final_pass(h i32 f64 i32 f64)
 int  tmvb_ctm_svi_info(h SviInfo)
 int  tmvb_ctm_svi_doc_sweeps(h pu8)
 int  tmvb_ctm_svi_last_run_ms(h pf32*3 pi64)
+int  tmvb_topic_divergence(h i32 i64 i32 pf64 i32 pf64 f64 i32 pf64 TopicDivInfo)
+int  tmvb_term_relevance(h i32 i64 pf64*3 f64 i32 pi32 pf64 pi32 pf64*3 RelevanceInfo)
+int  tmvb_assignment(i32 i32 pf64 pi32 pf64)
 """
 
 

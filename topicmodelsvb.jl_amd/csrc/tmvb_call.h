@@ -1,5 +1,5 @@
 // tmvb_call.h -- the device scratch of ONE call of a stateless entry point (tmvb_corpus_split, tmvb_heldout_loglik, tmvb_*_gencorp,
-// tmvb_corpus_codocfreq, tmvb_topic_neighbors, tmvb_topic_order, tmvb_ctpf_recommend, tmvb_score_ranks, tmvb_score_topn, tmvb_ctpf_foldin_users, tmvb_ctpf_foldin_users_on, tmvb_topic_search, tmvb_token_topics, tmvb_topic_kmeans, tmvb_map_affinity, tmvb_map_layout).  Host code only: no device code, no tmvb_internal.h.
+// tmvb_corpus_codocfreq, tmvb_topic_neighbors, tmvb_topic_order, tmvb_ctpf_recommend, tmvb_score_ranks, tmvb_score_topn, tmvb_ctpf_foldin_users, tmvb_ctpf_foldin_users_on, tmvb_topic_search, tmvb_token_topics, tmvb_topic_kmeans, tmvb_map_affinity, tmvb_map_layout, tmvb_topic_divergence, tmvb_term_relevance).  Host code only: no device code, no tmvb_internal.h.
 // (Memory that a handle owns for its lifetime is not this: tmvb_owned in tmvb_handle.h.)
 //
 // Release order.  A call declares, in this order,

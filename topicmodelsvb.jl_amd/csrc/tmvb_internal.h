@@ -177,6 +177,12 @@ int tmvb_corpus_reader_index(tmvb_corpus* c);
 int tmvb_check_host_csr(const char* fn, int64_t M, int64_t V, const int64_t* doc_ptr, const int32_t* terms, const int32_t* counts, bool doc_tokens_limit);
 int tmvb_check_stochastic_beta(int32_t K, int64_t V, const double* beta);
 int tmvb_check_ctx_or_device(const char* fn, tmvb_ctx* ctx);
+// The segmented radix sort behind tmvb_topic_order and tmvb_term_relevance (tmvb_topics.hip; rocPRIM through hipcub): K segments of V (key, column) pairs,
+// d_keys / d_vals row-major [K][V] on the device, filled by the caller's kernel on the call's stream.  Stable: equal keys keep the order they came in, ascending
+// or descending alike.  The sorted pairs come back in buffers of the call (tmvb_call.h), as every temporary does.
+struct tmvb_call;
+int tmvb_segmented_sort_pairs(tmvb_call& c, int K, int64_t V, const double* d_keys, const int32_t* d_vals, bool descending, double** d_sorted_keys,
+                              int32_t** d_sorted_vals);
 
 // EPSILON of the reference (src/utils.jl:3) = 2^-99, exactly representable in fp32.
 // MUTANTS (tests/test_mutants_gpu.py; never defined in a shipped build): deliberately wrong variants of seven operators, one -D flag each, built as
@@ -220,6 +226,8 @@ int tmvb_check_ctx_or_device(const char* fn, tmvb_ctx* ctx);
 //                                   wrong wherever the centroids differ in norm; tests/test_kmeans_mutant_gpu.py
 //   TMVB_MUTANT_MAP_Z_SELF          the normaliser of the document map (tmvb_docmap.hip) keeps the M self terms: Z = blocked(zrow) without - M, so the gradient's
 //                                   repulsive half is too small; tests/test_docmap_mutant_gpu.py
+//   TMVB_MUTANT_TD_DROP_TAIL        the pair kernel of the topic divergences (tmvb_topic_compare.hip) leaves out the last, partial run of terms (V not a multiple of
+//                                   TMVB_TD_RUN); tests/test_topic_compare_mutant_gpu.py
 #ifdef TMVB_MUTANT_FLDA_H_NO_GUARD
 #define TMVB_FLDA_H_GUARD(cond) true
 #else

@@ -36,6 +36,35 @@ static __global__ void topics_offsets_kernel(int* __restrict__ off, int K, int64
     if (i <= K) off[i] = (int)((int64_t)i * V);
 }
 
+// K segments of V pairs, one library sort; stable either way (tmvb_internal.h).  tmvb_topic_order sorts ascending and reads backwards, as the reference does;
+// tmvb_term_relevance (tmvb_topic_compare.hip) sorts descending, so that equal scores keep ascending term ids.
+int tmvb_segmented_sort_pairs(tmvb_call& c, int K, int64_t V, const double* d_keys, const int32_t* d_vals, bool descending, double** d_sorted_keys,
+                              int32_t** d_sorted_vals)
+{
+    const int64_t n = (int64_t)K * V;
+    hipStream_t st = c.stream;
+    int* d_off;
+    char* d_tmp;
+    TMVB_CALL_TRY(c, c.alloc(d_sorted_keys, (size_t)n)); TMVB_CALL_TRY(c, c.alloc(d_sorted_vals, (size_t)n)); TMVB_CALL_TRY(c, c.alloc(&d_off, (size_t)K + 1));
+    hipLaunchKernelGGL(topics_offsets_kernel, dim3((unsigned)((K + 256) / 256)), dim3(256), 0, st, d_off, (int)K, V);
+    TMVB_CALL_HIP(c, hipGetLastError());
+    size_t tmp_bytes = 0;
+    if (descending) {
+        TMVB_CALL_HIP(c, hipcub::DeviceSegmentedRadixSort::SortPairsDescending(nullptr, tmp_bytes, d_keys, *d_sorted_keys, d_vals, *d_sorted_vals, (int)n, (int)K,
+                                                                               (const int*)d_off, (const int*)d_off + 1, 0, 64, st));
+        TMVB_CALL_TRY(c, c.alloc(&d_tmp, std::max<size_t>(tmp_bytes, 16)));
+        TMVB_CALL_HIP(c, hipcub::DeviceSegmentedRadixSort::SortPairsDescending((void*)d_tmp, tmp_bytes, d_keys, *d_sorted_keys, d_vals, *d_sorted_vals, (int)n, (int)K,
+                                                                               (const int*)d_off, (const int*)d_off + 1, 0, 64, st));
+    } else {
+        TMVB_CALL_HIP(c, hipcub::DeviceSegmentedRadixSort::SortPairs(nullptr, tmp_bytes, d_keys, *d_sorted_keys, d_vals, *d_sorted_vals, (int)n, (int)K,
+                                                                     (const int*)d_off, (const int*)d_off + 1, 0, 64, st));
+        TMVB_CALL_TRY(c, c.alloc(&d_tmp, std::max<size_t>(tmp_bytes, 16)));
+        TMVB_CALL_HIP(c, hipcub::DeviceSegmentedRadixSort::SortPairs((void*)d_tmp, tmp_bytes, d_keys, *d_sorted_keys, d_vals, *d_sorted_vals, (int)n, (int)K,
+                                                                     (const int*)d_off, (const int*)d_off + 1, 0, 64, st));
+    }
+    return TMVB_OK;
+}
+
 extern "C" int tmvb_topic_order(tmvb_ctx* ctx, const double* beta, int32_t K, int64_t V, int32_t* topics)
 {
     TMVB_REQUIRE(ctx != nullptr, TMVB_EINVAL, "tmvb_topic_order: ctx is NULL");
@@ -49,20 +78,12 @@ extern "C" int tmvb_topic_order(tmvb_ctx* ctx, const double* beta, int32_t K, in
     TMVB_CALL_TRY(c, c.begin());
     double *d_in, *d_keys, *d_keys2;
     int32_t *d_vals, *d_vals2;
-    int* d_off;
-    char* d_tmp;
-    TMVB_CALL_TRY(c, c.alloc(&d_keys, (size_t)n)); TMVB_CALL_TRY(c, c.alloc(&d_keys2, (size_t)n)); TMVB_CALL_TRY(c, c.alloc(&d_vals, (size_t)n));
-    TMVB_CALL_TRY(c, c.alloc(&d_vals2, (size_t)n)); TMVB_CALL_TRY(c, c.alloc(&d_off, (size_t)K + 1)); TMVB_CALL_TRY(c, c.upload(&d_in, beta, (size_t)n));
+    TMVB_CALL_TRY(c, c.alloc(&d_keys, (size_t)n)); TMVB_CALL_TRY(c, c.alloc(&d_vals, (size_t)n)); TMVB_CALL_TRY(c, c.upload(&d_in, beta, (size_t)n));
     const unsigned nb = (unsigned)((n + 255) / 256);
     hipLaunchKernelGGL(topics_keys_kernel, dim3(nb), dim3(256), 0, st, (const double*)d_in, (int)K, V, d_keys, d_vals);
-    hipLaunchKernelGGL(topics_offsets_kernel, dim3((unsigned)((K + 256) / 256)), dim3(256), 0, st, d_off, (int)K, V);
     TMVB_CALL_HIP(c, hipGetLastError());
-    size_t tmp_bytes = 0;
-    TMVB_CALL_HIP(c, hipcub::DeviceSegmentedRadixSort::SortPairs(nullptr, tmp_bytes, (const double*)d_keys, d_keys2, (const int32_t*)d_vals, d_vals2, (int)n, (int)K,
-                                                                 (const int*)d_off, (const int*)d_off + 1, 0, 64, st));
-    TMVB_CALL_TRY(c, c.alloc(&d_tmp, std::max<size_t>(tmp_bytes, 16)));
-    TMVB_CALL_HIP(c, hipcub::DeviceSegmentedRadixSort::SortPairs((void*)d_tmp, tmp_bytes, (const double*)d_keys, d_keys2, (const int32_t*)d_vals, d_vals2, (int)n, (int)K,
-                                                                 (const int*)d_off, (const int*)d_off + 1, 0, 64, st));
+    const int rc = tmvb_segmented_sort_pairs(c, (int)K, V, d_keys, d_vals, false, &d_keys2, &d_vals2);
+    if (rc != TMVB_OK) return rc;
     hipLaunchKernelGGL(topics_reverse_kernel, dim3(nb), dim3(256), 0, st, (const int32_t*)d_vals2, (int)K, V, d_vals);
     TMVB_CALL_HIP(c, hipGetLastError());
     TMVB_CALL_HIP(c, hipMemcpyAsync(topics, d_vals, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, st));

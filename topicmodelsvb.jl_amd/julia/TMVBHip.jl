@@ -1608,3 +1608,81 @@ function rank_metrics(tgt_ptr::Vector{Int64}, rank::Vector{Int32}, n_cand::Vecto
 	tmvb_check(rc)
 	return (recall=recall, precision=precision, ndcg=ndcg, mrr=mrr, pct_rank=pct_rank, means=means, n_queries=Int(counts[1]), n_targets=Int(counts[2]))
 end
+
+# ---------------------------------------------------------------------------------------------- compare topics
+# The topic side of a model: tmvb_topic_divergence (pairwise Jensen-Shannon / Hellinger / total variation / KL between the rows of one or two K x V
+# topic-word matrices, fp64, every sum in one fixed order), tmvb_assignment (minimum-cost matching of the topics of two runs, host only) and
+# tmvb_term_relevance (the relevance ranking of LDAvis with distinctiveness and saliency).  include/tmvb.h is the specification.
+
+"tmvb_topicdiv_info_t (include/tmvb.h), field for field."
+mutable struct TmvbTopicDivInfo
+	splits::Int32; runs::Int32
+	ms_prep::Float32; ms_pairs::Float32; ms_merge::Float32
+	TmvbTopicDivInfo() = new(0, 0, 0f0, 0f0, 0f0)
+end
+
+"tmvb_relevance_info_t (include/tmvb.h), field for field."
+mutable struct TmvbRelevanceInfo
+	ms_score::Float32; ms_select::Float32; ms_terms::Float32
+	TmvbRelevanceInfo() = new(0f0, 0f0, 0f0)
+end
+
+const TD_METRICS = Dict(:js => 0, :hellinger => 1, :tv => 2, :kl => 3)
+
+"""
+D[i, j] = the divergence of row i of `a` (KA x V, rows are distributions: model.beta) from row j of `b` (KB x V; nothing: of `a` itself).
+metric :js (nats), :hellinger, :tv or :kl (directed; smooth > 0 keeps it finite).
+"""
+function topic_divergence(a::Matrix{Float64}, b::Union{Nothing, Matrix{Float64}}=nothing; metric::Symbol=:js, smooth::Real=0.0, splits::Integer=0,
+						  device::Integer=0)
+	haskey(TD_METRICS, metric)			|| throw(ArgumentError("metric must be :js, :hellinger, :tv or :kl."))
+	KA, V = size(a)
+	KB = b === nothing ? KA : size(b, 1)
+	(b === nothing || size(b, 2) == V)	|| throw(TopicModelError("a and b must be over the same vocabulary."))
+	Dt = zeros(Float64, KB, KA)			# C's row-major [KA][KB]
+	info = TmvbTopicDivInfo()
+	ctx = tmvb_context(device)
+	GC.@preserve info a b Dt begin
+		rc = ccall((:tmvb_topic_divergence, LIBTMVB), Cint,
+			(Ptr{Cvoid}, Int32, Int64, Int32, Ptr{Float64}, Int32, Ptr{Float64}, Float64, Int32, Ptr{Float64}, Ptr{Cvoid}),
+			ctx, TD_METRICS[metric], V, KA, a, KB, b === nothing ? Ptr{Float64}(C_NULL) : pointer(b), smooth, splits, Dt, pointer_from_objref(info))
+		tmvb_destroy_context(ctx)
+		tmvb_check(rc)
+	end
+	return (distance=permutedims(Dt), splits=Int(info.splits), runs=Int(info.runs), ms=(prep=info.ms_prep, pairs=info.ms_pairs, merge=info.ms_merge))
+end
+
+"""
+A minimum-cost assignment of the n rows of `cost` (n x m, n <= m, entries finite or Inf) to distinct columns: (match, total), match[i] 1-based.
+"""
+function assignment(cost::Matrix{Float64})
+	n, m = size(cost)
+	ct = permutedims(cost)				# C's row-major [n][m]
+	match = zeros(Int32, n); total = zeros(Float64, 1)
+	rc = ccall((:tmvb_assignment, LIBTMVB), Cint, (Int32, Int32, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}), n, m, ct, match, total)
+	tmvb_check(rc)
+	return (match=Int.(match) .+ 1, total=total[1])
+end
+
+"""
+The `topn` terms of every topic by relevance lambda log(phi) + (1 - lambda) log(phi / pw), 1-based (0 past count), with their scores, and the
+distinctiveness and saliency of every term.  beta K x V, pw[V] the marginal term probabilities, pi[K] the topic shares.
+"""
+function term_relevance(beta::Matrix{Float64}, pw::Vector{Float64}, pi::Vector{Float64}; lambda::Real=0.6, topn::Integer=10, device::Integer=0)
+	K, V = size(beta)
+	(length(pw) == V && length(pi) == K)	|| throw(TopicModelError("pw must have V entries and pi K."))
+	idx = zeros(Int32, topn, K); score = zeros(Float64, topn, K); count = zeros(Int32, K)		# column-major (slot, k) = C's [k][slot]
+	distinct = zeros(Float64, V); saliency = zeros(Float64, V)
+	info = TmvbRelevanceInfo()
+	ctx = tmvb_context(device)
+	GC.@preserve info beta pw pi idx score count distinct saliency begin
+		rc = ccall((:tmvb_term_relevance, LIBTMVB), Cint,
+			(Ptr{Cvoid}, Int32, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Float64, Int32, Ptr{Int32}, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64},
+			 Ptr{Float64}, Ptr{Cvoid}),
+			ctx, K, V, beta, pw, pi, lambda, topn, idx, score, count, Ptr{Float64}(C_NULL), distinct, saliency, pointer_from_objref(info))
+		tmvb_destroy_context(ctx)
+		tmvb_check(rc)
+	end
+	return (idx=permutedims(Int.(idx) .+ 1), score=permutedims(score), count=Int.(count), distinctiveness=distinct, saliency=saliency,
+			ms=(score=info.ms_score, select=info.ms_select, terms=info.ms_terms))
+end
