@@ -423,6 +423,8 @@ int tmvb_fctm_train_group(tmvb_fctm* const* hs, int32_t n, int32_t iter, double 
                           double vtol, int32_t checkelbo, double* elbo_traj, int32_t* iters_done, double* elbo_baseline);
 int tmvb_fctm_sweep_hist(tmvb_fctm* h, int64_t* hist, int32_t nbins, int64_t* newton_steps);
 int tmvb_fctm_doc_sweeps(tmvb_fctm* h, uint8_t* out);
+/* As tmvb_ctm_solver_stats, for the filtered model's E-step (zeros when the wave-per-document kernels ran). */
+int tmvb_fctm_solver_stats(tmvb_fctm* h, int64_t* out12);
 /* As tmvb_flda_elbo_form for update_elbo! of src/fCTM.jl:105-115 (lambda for Elogtheta: the E-step kernels' exit test leaves
  * sum_i (phi counts)_i (lambda_i - lambda_old_i) per document); TMVB_FCTM_ELBO_PARTS at tmvb_fctm_create. */
 int tmvb_fctm_elbo_form(tmvb_fctm* h, int32_t* form);

@@ -3,8 +3,10 @@ GPU parity tests for the filtered-CTM path (new device path; oracle src/fCTM.jl)
 oracle and the committed golden fixture.  Tolerances (fp64 -> fp32 state; fp64 Newton gradients on device): the fctm.* keys of tests/tol.py --
 round 6: measured on MI355X and frozen at <= 10x (lambda in units of CTM's bound 1.5e-5 + 1.5e-5 |lambda|; round 5 they were literals up to 130x
 looser); tests/test_mutants_gpu.py holds the negative control (update_vsq! in front of update_lambda!: CTM's order instead of src/fCTM.jl:239-240).
-K <= 50 runs the lane-per-document kernel (FILT instantiation, CG Newton solves), 50 < K <= 60 the register Gauss-Jordan kernel,
-60 < K <= 128 the LDS Newton solve.
+K <= 52 runs the lane-per-document kernel (FILT instantiation, CG Newton solves) and, for its documents of more than 2048 unique terms or under
+TMVB_CTM_BATCH=0, the register Gauss-Jordan kernel (one wave per document); 52 < K <= 128 the generic kernel (one topic slot per lane up to
+K = 64, two beyond: CG Newton solves against invsigma in LDS since round 3, K = 53 ... 60 included), K > 128 the same with four slots per lane
+and invsigma read from global memory.
 """
 import os
 
@@ -141,6 +143,47 @@ def test_long_documents_stream_chunks(tmvb, oracle):
         step(gm, viter=3, vtol=0.0); step(om, viter=3, vtol=0.0)
         gm.update_host()
         compare(gm, om, it)
+
+
+@pytest.mark.parametrize("K", [4, 28, 44])
+def test_wave_per_document_kernel_matches_lane_kernel(tmvb, monkeypatch, K):
+    """fCTM's twin of test_lane_per_document_kernel_matches_wave_per_document_kernel (tests/test_ctm_gpu.py): TMVB_CTM_BATCH=0 sends every document
+    to ctm_estep_kernel<KP, true> (direct Newton solves in registers), which otherwise only documents of more than 2048 unique terms reach; the
+    default handle runs ctm_estep_batch_kernel<KP, false, true> (CG).  Same corpus (130 documents and an empty one: not a multiple of 64) and
+    state in, two outer iterations, the wave handle's state carried into the lane handle between them.  Bounds: the CTM twin's literals and
+    fctm.tau_abs.  Measured on MI355X before the launch layer was rewritten (profiles/ctm_launch_refactor_ab.json), worst of K = 4 / 28 / 44:
+    lambda 2.7e-5, vsq 4.4e-6 of its max, mu 1.7e-6, sigma 1.2e-6 of its max, ELBO 5.3e-9 relative, tau 1.0e-6, no document's sweep count differs."""
+    pc = tmvb.syn_nsf(M=130, V=300, seed=3)
+    pc = tmvb.PackedCorpus(np.concatenate([pc.doc_ptr[:41], pc.doc_ptr[40:]]), pc.terms, pc.counts, pc.V)     # document 40: empty
+    pair = []
+    for flag in ("0", "1"):
+        monkeypatch.setenv("TMVB_CTM_BATCH", flag)
+        g = tmvb.gpufCTM(pc, K)
+        g.beta = np.asfortranarray(tmvb.dirichlet_rows(K, pc.V, seed=5)); g.beta_old = g.beta.copy(order="F")
+        g.kappa = np.array(tmvb.dirichlet_rows(1, pc.V, seed=9)[0], dtype=np.float64); g.kappa_old = g.kappa.copy()
+        g.update_buffer()
+        pair.append(g)
+    gw, gb = pair
+    for it in range(2):
+        for g in (gw, gb):
+            step(g)
+        # (gpufCTM has no solver_stats of its own: gpuCTM's method, called on the fCTM handle, reaches tmvb_fctm_solver_stats through the handle's _ABI)
+        solver_stats = tmvb.gpuCTM.solver_stats
+        assert solver_stats(gw)["waves"] == 0 and solver_stats(gb)["waves"] == (pc.M + 63) // 64
+        for g in (gw, gb):
+            g.update_host()
+        assert np.array_equal(gw.doc_sweeps() > 0, gb.doc_sweeps() > 0)
+        assert (gw.doc_sweeps() != gb.doc_sweeps()).mean() <= 0.02
+        assert np.abs(gw.lam - gb.lam).max() <= 1e-3, (it, np.abs(gw.lam - gb.lam).max())
+        assert np.abs(gw.vsq - gb.vsq).max() <= 1e-3 * gw.vsq.max()
+        assert np.abs(gw.mu - gb.mu).max() <= 1e-4 and np.abs(gw.sigma - gb.sigma).max() <= 1e-4 * np.abs(gw.sigma).max()
+        ew, eb = gw.update_elbo(), gb.update_elbo()
+        assert abs(ew - eb) <= 1e-6 * abs(ew), (it, ew, eb)
+        within("fctm.tau_abs", np.abs(gw.tau - gb.tau).max(initial=0.0), (it, "tau"))
+        # carry ONE state forward so that differences do not compound into different trajectories
+        for n, _ in gw._STATE:
+            v = getattr(gw, n); setattr(gb, n, np.array(v, copy=True, order="F") if isinstance(v, np.ndarray) else v)
+        gb.update_buffer()
 
 
 def test_errors_and_invariants(tmvb):

@@ -165,6 +165,7 @@ int  tmvb_fctm_set_comm(h h i64)
 int  tmvb_fctm_train_group(ph i32 i32 f64 i32 f64 i32 f64 i32 pf64 pi32 pf64)
 int  tmvb_fctm_sweep_hist(h pi64 i32 pi64)
 int  tmvb_fctm_doc_sweeps(h pu8)
+int  tmvb_fctm_solver_stats(h pi64)
 int  tmvb_fctm_elbo_form(h pi32)
 int  tmvb_ctpf_create(h h i32 ph)
 int  tmvb_ctpf_destroy(h)

@@ -24,6 +24,18 @@
 // M-step: the K x M * M x K scatter matrix sum_d (lambda_d - mu)(lambda_d - mu)^T runs on f32 MFMA
 // (v_mfma_f32_32x32x2_f32); sigma assembly, its inverse and log-determinant run in fp64 in one
 // workgroup.
+//
+// Host half (from `struct tmvb_ctm` down), the launch layer -- helper: what it holds -> the kernels it serves
+//   ctm_params: the CtmParams fields CTM and fCTM share -> every E-step kernel;  ctm_cg_abs2: the absolute CG threshold -> the batch, quad and generic kernels
+//   ctm_dispatch_kp: KP in {4, 12, ..., 52} as a compile-time constant -> ctm_estep_kernel, ctm_estep_batch_kernel, ctm_estep_quad_kernel
+//   ctm_launch_wave<FILT>: a bucket of documents, one wave each -> ctm_estep_kernel<KP, FILT> (documents of > 2048 unique terms, TMVB_CTM_BATCH=0)
+//   ctm_lane_prepare: tables, item queue, regrouping (ctm_regroup -> ctm_reorder_kernel; tmvb_ctm_estep also stages it), CtmBatchArgs -> both of:
+//   ctm_launch_batch<FILT>: one wave per 64 documents -> ctm_estep_batch_kernel<KP, PROF, FILT> (fCTM; CTM under TMVB_CTM_QUAD=0)
+//   ctm_launch_quad: four waves per 64 documents, LDS ctm_quad_lds_bytes -> ctm_estep_quad_kernel<KP, PROF> (CTM)
+//   ctm_launch_lane: which of the two CTM runs (TMVB_CTM_QUAD, the device's LDS limit)
+//   ctm_launch_generic<FILT>: K > 52 -> ctm_estep_generic_kernel<NS, FILT, CG, MAXW, GA>
+//   ctm_fold_tail, ctm_stage_next_order: tmvb_ctm_estep's side streams under the statistics pass -> the tail reductions, staged sigma, ctm_reorder_kernel + queue sort
+//   ctm_dispatch_nslot: 1 / 2 / 4 topic slots per lane -> ctm_elbo_kernel, fctm_elbo_kernel, fctm_elbo_doc_parts_kernel;  ctm_fetch_elbo: the end of both update_elbo!
 #define TMVB_TS_LOGZ 1            // the log-normaliser forms of the statistics pass (decomposed update_elbo!, see ctm_elbo_kernel)
 #include "tmvb_common_kernels.h"
 #include "tmvb_train.h"
@@ -1469,6 +1481,76 @@ struct tmvb_ctm : tmvb_model_base {       // d_stats: S (K*V) | sum_lambda (K) |
 // reloads) and 40.7 ms for the register Gauss-Jordan kernel that round 2 ran there.
 static bool ctm_kp_supported(int kp) { return kp >= 4 && kp <= 52 && kp % 8 == 4; }
 
+// ---- the launch layer (map: the unit's header comment)
+// f(std::integral_constant<int, KP>()) for the seven KP of ctm_kp_supported; every caller sits behind that test (h->generic is false): the refusal is unreachable
+template <typename F>
+static int ctm_dispatch_kp(int KP, F&& f)
+{
+    switch (KP) {
+        case 4: return f(std::integral_constant<int, 4>());
+        case 12: return f(std::integral_constant<int, 12>());
+        case 20: return f(std::integral_constant<int, 20>());
+        case 28: return f(std::integral_constant<int, 28>());
+        case 36: return f(std::integral_constant<int, 36>());
+        case 44: return f(std::integral_constant<int, 44>());
+        case 52: return f(std::integral_constant<int, 52>());
+        default: TMVB_REQUIRE(false, TMVB_EINVAL, "ctm_launch_quad: KP not instantiated");
+    }
+}
+
+// f(std::integral_constant<int, NS>()) for 1, 2 or 4 topic slots per lane (K <= CTM_MAX_K): dispatch_nslot (tmvb_common_kernels.h) would also instantiate
+// the 8- and 16-slot forms of the ELBO kernels, which no CTM handle can reach
+template <typename F>
+static void ctm_dispatch_nslot(int nslot, F&& f)
+{
+    if (nslot == 1) f(std::integral_constant<int, 1>()); else if (nslot == 2) f(std::integral_constant<int, 2>()); else f(std::integral_constant<int, 4>());
+}
+
+// dynamic LDS of ctm_estep_quad_kernel<KP>: the host's copy of cq_dim<KP>::lds_bytes for a KP known at run time
+static constexpr size_t ctm_quad_lds_bytes(int KP) { return (size_t)(5 * KP * 64 + 2 * 3 * 4 * 64) * 4 + (size_t)(2 * 4 * 64) * 8 + (5 * 64 + 4) * 4; }
+template <int... KPV> constexpr bool ctm_quad_lds_agrees() { return ((ctm_quad_lds_bytes(KPV) == cq_dim<KPV>::lds_bytes) && ...); }
+static_assert(ctm_quad_lds_agrees<4, 12, 20, 28, 36, 44, 52>(), "ctm_quad_lds_bytes must follow cq_dim<KP>::lds_bytes (tmvb_ctm_quad.h)");
+
+// what every E-step kernel of CTM and fCTM takes; the entry points add store_w, pdot and the filter's fields
+static CtmParams ctm_params(const tmvb_ctm* h, int niter, double ntol, int viter, double vtol)
+{
+    CtmParams p;
+    p.K = h->K; p.KP = h->KP; p.LPR = h->KP / 4; p.lpr_magic = (unsigned)(0x100000000ull / (unsigned)p.LPR) + 1u;
+    p.doc_ptr = h->corp->d_doc_ptr; p.terms = h->corp->d_terms; p.counts = h->corp->d_counts;
+    p.doc_order = h->d_doc_order; p.tok_inv = h->corp->term_index.d_inv;
+    p.beta = h->d_beta[h->cur]; p.invsigma = h->d_invsigma_f; p.mu = h->d_mu_f;
+    p.lambda = h->d_lambda; p.lambda_old = h->d_lambda_old; p.vsq = h->d_vsq; p.logzeta = h->d_logzeta;
+    p.wtok = h->d_wtok; p.E = h->d_E; p.estride = (h->KP / 4 <= 64) ? h->KP : h->K; p.sweeps = h->d_sweeps; p.newton_steps = h->d_newton;
+    p.niter = niter; p.ntol = ntol; p.viter = viter; p.vtol = vtol; p.debug = 0;
+    return p;
+}
+
+// squared absolute CG stopping threshold: the fraction cg_abs of ntol, never looser than at the reference K = 50 (ntol = 1/K^2)
+static float ctm_cg_abs2(const tmvb_ctm* h, double ntol) { const double fl = h->cg_abs * std::min(ntol, 4e-4); return (float)(fl * fl); }
+
+// the documents behind the long ones regrouped by their last E-step's Newton step counts (d_doc_order0 -> d_doc_order), on stream st
+static int ctm_regroup(tmvb_ctm* h, hipStream_t st)
+{
+    const int64_t Mb = h->M - h->n_long;
+    hipLaunchKernelGGL(ctm_reorder_kernel, dim3((unsigned)((Mb + CTM_REORDER_CHUNK - 1) / CTM_REORDER_CHUNK)), dim3(1024), 0, st,
+                       h->d_doc_order0 + h->n_long, h->d_doc_newton, h->d_doc_order + h->n_long, Mb);
+    TMVB_HIP(hipGetLastError());
+    return TMVB_OK;
+}
+
+// the end of update_elbo! of CTM and fCTM: the sum and the status word of the last sigma inversion come back, a failed inversion is refused
+static int ctm_fetch_elbo(tmvb_ctm* h, double* elbo)
+{
+    tmvb_ctx* ctx = h->ctx;
+    double v = 0.0; int st = 0;
+    TMVB_HIP(hipMemcpyAsync(&v, h->d_elbo, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    TMVB_HIP(hipMemcpyAsync(&st, h->d_status, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    TMVB_HIP(hipStreamSynchronize(ctx->stream));
+    TMVB_REQUIRE(st == 0, TMVB_ENONFINITE, "sigma must be positive-definite.");
+    h->elbo = v; if (elbo) *elbo = v;
+    return TMVB_OK;
+}
+
 extern "C" int tmvb_ctm_destroy(tmvb_ctm* h)
 {
     if (!h) return TMVB_OK;
@@ -1484,6 +1566,7 @@ extern "C" int tmvb_ctm_set_state(tmvb_ctm* h, const double* mu, const double* s
 static int ctm_reduce_docs_on(tmvb_ctm* h, hipStream_t st);
 static int ctm_join_spec(tmvb_ctm* h);
 static int ctm_sigma_mu(tmvb_ctm* h, int do_sigma, int do_mu, bool staged, hipStream_t st);
+static int ctm_launch_lane(tmvb_ctm* h, const CtmParams& p, double ntol);
 
 extern "C" int tmvb_ctm_create(tmvb_ctx* ctx, tmvb_corpus* corp, int32_t K, tmvb_ctm** out)
 {
@@ -1698,7 +1781,7 @@ static int ctm_launch_generic(tmvb_ctm* h, CtmParams p, double ntol)
         TMVB_HIP(hipMemsetAsync(h->d_cg_iters, 0, 16 * sizeof(unsigned long long), ctx->stream));
         p.queue = (unsigned*)(h->d_cg_iters + 12); p.n_docs = h->M; p.cg_diag = h->d_cg_iters;
         p.cg_tol2 = h->cg_tol * h->cg_tol; p.cg_maxit = 4 * h->KP;
-        { const double fl = h->cg_abs * std::min(ntol, 4e-4); p.cg_abs2 = (float)(fl * fl); }
+        p.cg_abs2 = ctm_cg_abs2(h, ntol);
         const unsigned nwg = (unsigned)std::min<int64_t>(ctx->num_cu, (h->M + waves - 1) / waves);
         auto launch = [&](auto kern) -> int {
             TMVB_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -1744,36 +1827,43 @@ __global__ __launch_bounds__(256) void ctm_rowpad_generic_kernel(const float4* _
     dst[q] = c < LPR ? src[v * LPR + c] : float4{0.f, 0.f, 0.f, 0.f};
 }
 
+// What the one-wave and the four-waves lane-per-document launches share: the tables and the CG stopping rule, the item queue over the documents behind the long
+// ones (in processing order, longest first), their regrouping unless the last tmvb_ctm_estep staged it behind its statistics tail, and the kernel's arguments.
+// take_sorted: the launch may follow the queue order of ctm_wave_sort_kernel.  Leaves ba->tb.n_items = 0 when every document is a long one: nothing to launch.
+static int ctm_lane_prepare(tmvb_ctm* h, const CtmParams& p, double ntol, bool take_sorted, CtmBatchArgs* ba)
+{
+    CtmBatchTabs& tb = ba->tb;
+    tb.S = h->d_invsigma_f; tb.sdiag = h->d_bt_sdiag; tb.muf = h->d_bt_muf;
+    tb.Sq = h->d_q_S; tb.sdq = h->d_q_sd; tb.muq = h->d_q_mu;               // (read by the four-waves kernel only)
+    tb.cg_tol2 = h->cg_tol * h->cg_tol; tb.cg_maxit = 4 * h->KP; tb.cg_iters = h->d_cg_iters;
+    tb.cg_abs2 = ctm_cg_abs2(h, ntol);
+    tb.n_items = 0;
+    const int64_t Mb = h->M - h->n_long;                 // the documents behind the long ones in the processing order
+    if (Mb <= 0) return TMVB_OK;
+    tb.next_item = (unsigned*)(h->d_cg_iters + 12); tb.n_items = (int)((Mb + 63) / 64);      // (the queue head is zeroed by the tables kernel)
+    if (h->reorder && h->keys_valid && !h->reorder_staged) { int rrc = ctm_regroup(h, h->ctx->stream); if (rrc) return rrc; }
+    h->reorder_staged = false; h->keys_valid = true;
+    ba->p = p; ba->p.doc_order = (h->queue_sorted && take_sorted) ? h->d_doc_order_q : p.doc_order + h->n_long; ba->p.doc_newton = h->d_doc_newton; ba->M = Mb;
+    h->queue_sorted = false;
+    return TMVB_OK;
+}
+
 // launch of the four-waves-per-item kernel (tmvb_ctm_quad.h): CTM, KP <= 52
 static int ctm_launch_quad(tmvb_ctm* h, const CtmParams& p, double ntol)
 {
     tmvb_ctx* ctx = h->ctx;
     hipLaunchKernelGGL(ctm_quad_tabs_kernel, dim3(1), dim3(256), 0, ctx->stream, h->K, h->KP, h->d_invsigma_f, h->d_mu_f, h->d_q_S, h->d_q_sd, h->d_q_mu, h->d_cg_iters);
     TMVB_HIP(hipGetLastError());
-    CtmBatchTabs tb;
-    tb.S = h->d_invsigma_f; tb.sdiag = h->d_bt_sdiag; tb.muf = h->d_bt_muf;
-    tb.Sq = h->d_q_S; tb.sdq = h->d_q_sd; tb.muq = h->d_q_mu;
-    tb.cg_tol2 = h->cg_tol * h->cg_tol; tb.cg_maxit = 4 * h->KP; tb.cg_iters = h->d_cg_iters;
-    { const double fl = h->cg_abs * std::min(ntol, 4e-4); tb.cg_abs2 = (float)(fl * fl); }
-    const int64_t Mb = h->M - h->n_long;
-    if (Mb <= 0) return TMVB_OK;
-    const int n_items = (int)((Mb + 63) / 64);
+    CtmBatchArgs ba;
+    if (int prc = ctm_lane_prepare(h, p, ntol, true, &ba)) return prc;
+    const int n_items = ba.tb.n_items;
+    if (n_items == 0) return TMVB_OK;
     const int LPRv = h->KP / 4, CPR = 4 * ((LPRv + 3) / 4);
-    const size_t lds = (size_t)(5 * h->KP * 64 + 2 * 3 * 4 * 64) * 4 + (size_t)(2 * 4 * 64) * 8 + (5 * 64 + 4) * 4;      // = cq_dim<KP>::lds_bytes
+    const size_t lds = ctm_quad_lds_bytes(h->KP);
     // two workgroups per CU: two waves per SIMD (TMVB_CTM_QUAD_PER_CU: diagnostics)
     int per_cu = TMVB_CTM_QWAVES;
     if (tmvb_env_str("TMVB_CTM_QUAD_PER_CU")) per_cu = std::max(1, std::min(4, tmvb_env_int("TMVB_CTM_QUAD_PER_CU", 0)));
     const dim3 grid((unsigned)std::min(n_items, per_cu * ctx->num_cu)), block(256);
-    tb.next_item = (unsigned*)(h->d_cg_iters + 12); tb.n_items = n_items;
-    if (h->reorder && h->keys_valid && !h->reorder_staged) {
-        hipLaunchKernelGGL(ctm_reorder_kernel, dim3((unsigned)((Mb + CTM_REORDER_CHUNK - 1) / CTM_REORDER_CHUNK)), dim3(1024), 0, ctx->stream,
-                           h->d_doc_order0 + h->n_long, h->d_doc_newton, h->d_doc_order + h->n_long, Mb);
-        TMVB_HIP(hipGetLastError());
-    }
-    h->reorder_staged = false;
-    h->keys_valid = true;
-    CtmBatchArgs ba;
-    ba.p = p; ba.p.doc_order = h->queue_sorted ? h->d_doc_order_q : p.doc_order + h->n_long; ba.p.doc_newton = h->d_doc_newton; ba.tb = tb; ba.M = Mb;
     if (!h->d_beta_pad || h->beta_pad_cpr != CPR) {
         h->mem.drop(&h->d_beta_pad);
         int prc = h->mem.alloc(&h->d_beta_pad, (size_t)h->V * CPR * 4 + 64); if (prc) return prc;
@@ -1782,18 +1872,17 @@ static int ctm_launch_quad(tmvb_ctm* h, const CtmParams& p, double ntol)
     hipLaunchKernelGGL(ctm_rowpad_generic_kernel, dim3((unsigned)((h->V * CPR + 255) / 256)), dim3(256), 0, ctx->stream, (const float4*)p.beta, (float4*)h->d_beta_pad, h->V, LPRv, CPR);
     TMVB_HIP(hipGetLastError());
     ba.p.beta = h->d_beta_pad;
-    h->queue_sorted = false;
-    // (the dynamic-LDS attribute once per HANDLE, not per process: one host thread may drive several devices, tmvb_ctm_train_group)
-#define CTM_QCASE(KPV) case KPV: { if (!h->quad_attr_set && lds > 48 * 1024) { TMVB_HIP(hipFuncSetAttribute((const void*)ctm_estep_quad_kernel<KPV, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); h->quad_attr_set = true; } \
-                                   hipLaunchKernelGGL((ctm_estep_quad_kernel<KPV, false>), grid, block, lds, ctx->stream, ba); } break;
     static const bool qprof = tmvb_env_on("TMVB_CTM_QPROF", false);
     if (qprof && h->KP == 52) {
         TMVB_HIP(hipFuncSetAttribute((const void*)ctm_estep_quad_kernel<52, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         hipLaunchKernelGGL((ctm_estep_quad_kernel<52, true>), grid, block, lds, ctx->stream, ba);
-    } else
-    switch (h->KP) { CTM_QCASE(4) CTM_QCASE(12) CTM_QCASE(20) CTM_QCASE(28) CTM_QCASE(36) CTM_QCASE(44) CTM_QCASE(52)
-                     default: TMVB_REQUIRE(false, TMVB_EINVAL, "ctm_launch_quad: KP not instantiated"); }
-#undef CTM_QCASE
+    } else if (int lrc = ctm_dispatch_kp(h->KP, [&](auto kp) -> int {
+        // (the dynamic-LDS attribute once per HANDLE, not per process: one host thread may drive several devices, tmvb_ctm_train_group)
+        auto kern = ctm_estep_quad_kernel<decltype(kp)::value, false>;
+        if (!h->quad_attr_set && lds > 48 * 1024) { TMVB_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); h->quad_attr_set = true; }
+        hipLaunchKernelGGL(kern, grid, block, lds, ctx->stream, ba);
+        return TMVB_OK;
+    })) return lrc;
     TMVB_HIP(hipGetLastError());
     return TMVB_OK;
 }
@@ -1805,38 +1894,24 @@ static int ctm_launch_batch(tmvb_ctm* h, const CtmParams& p, double ntol)
     tmvb_ctx* ctx = h->ctx;
     hipLaunchKernelGGL(ctm_batch_tabs_kernel, dim3(1), dim3(64), 0, ctx->stream, h->K, h->KP, h->d_invsigma_f, h->d_mu_f, h->d_bt_sdiag, h->d_bt_muf, h->d_cg_iters);
     TMVB_HIP(hipGetLastError());
-    CtmBatchTabs tb;
-    tb.S = h->d_invsigma_f; tb.sdiag = h->d_bt_sdiag; tb.muf = h->d_bt_muf;
-    tb.cg_tol2 = h->cg_tol * h->cg_tol; tb.cg_maxit = 4 * h->KP; tb.cg_iters = h->d_cg_iters;
-    { const double fl = h->cg_abs * std::min(ntol, 4e-4); tb.cg_abs2 = (float)(fl * fl); }   // never looser than at the reference K = 50 (ntol = 1/K^2)
-    const int64_t Mb = h->M - h->n_long;                 // the documents behind the long ones in the processing order
-    if (Mb <= 0) return TMVB_OK;
+    CtmBatchArgs ba;
+    if (int prc = ctm_lane_prepare(h, p, ntol, !FILT, &ba)) return prc;
+    const int n_items = ba.tb.n_items;
+    if (n_items == 0) return TMVB_OK;
     // persistent launch: one 64-lane workgroup per SIMD of the device (the kernel takes a whole SIMD's register file), each pulling
-    // waves-of-documents from the queue at d_cg_iters[12] (zeroed by ctm_batch_tabs_kernel); the order of the queue is the processing order, longest
-    // documents first.  TMVB_CTM_PERSISTENT=0: one workgroup per wave-of-documents, placed by the hardware dispatcher.
-    const int n_items = (int)((Mb + 63) / 64);
+    // waves-of-documents from the queue at d_cg_iters[12] (zeroed by ctm_batch_tabs_kernel).  TMVB_CTM_PERSISTENT=0: one workgroup per
+    // wave-of-documents, placed by the hardware dispatcher.
     static const bool persistent = tmvb_env_on("TMVB_CTM_PERSISTENT", true);
     const size_t lds = (size_t)h->KP * 64 * (sizeof(double) + sizeof(float)) + 64 * sizeof(int32_t);   // vsq, CG solution / row staging, row ids
     int per_cu = (int)std::min<size_t>(4, (160 * 1024) / lds);            // one wave per SIMD, and what the CU's LDS holds
     if (tmvb_env_str("TMVB_CTM_PER_CU")) per_cu = std::max(1, std::min(per_cu, tmvb_env_int("TMVB_CTM_PER_CU", 0)));   // diagnostics: fewer resident waves (contention experiments, profiles/r5_ctm_token_experiments.txt)
     const dim3 grid((unsigned)(persistent ? std::min(n_items, per_cu * ctx->num_cu) : n_items)), block(64);
-    tb.next_item = (unsigned*)(h->d_cg_iters + 12); tb.n_items = n_items;
-    if (h->reorder && h->keys_valid && !h->reorder_staged) {      // (staged: the last tmvb_ctm_estep already regrouped behind its statistics tail)
-        hipLaunchKernelGGL(ctm_reorder_kernel, dim3((unsigned)((Mb + CTM_REORDER_CHUNK - 1) / CTM_REORDER_CHUNK)), dim3(1024), 0, ctx->stream,
-                           h->d_doc_order0 + h->n_long, h->d_doc_newton, h->d_doc_order + h->n_long, Mb);
-        TMVB_HIP(hipGetLastError());
-    }
-    h->reorder_staged = false;
-    h->keys_valid = true;
-    CtmBatchArgs ba;
-    ba.p = p; ba.p.doc_order = (h->queue_sorted && !FILT) ? h->d_doc_order_q : p.doc_order + h->n_long; ba.p.doc_newton = h->d_doc_newton; ba.tb = tb; ba.M = Mb;
     if (cb_rowb<52, FILT>::value == 256u && h->KP == 52) {
         if (!h->d_beta_pad) { int prc = h->mem.alloc(&h->d_beta_pad, (size_t)h->V * 64); if (prc) return prc; }
         hipLaunchKernelGGL(ctm_rowpad_kernel, dim3((unsigned)((h->V * 16 + 255) / 256)), dim3(256), 0, ctx->stream, (const float4*)p.beta, (float4*)h->d_beta_pad, h->V);
         TMVB_HIP(hipGetLastError());
         ba.p.beta = h->d_beta_pad;
     }
-    h->queue_sorted = false;
     static const bool prof = tmvb_env_on("TMVB_CTM_PROF", false);
     // TMVB_CTM_WAVE_LOG=<file> (with TMVB_CTM_PROF=1): per-item start / end / placement of this launch, written after a synchronisation (diagnostics only)
     static const char* wave_log = tmvb_env_str("TMVB_CTM_WAVE_LOG");
@@ -1849,11 +1924,8 @@ static int ctm_launch_batch(tmvb_ctm* h, const CtmParams& p, double ntol)
         }
         ba.tb.wave_log = h->d_wave_log;
     }
-#define CTM_BCASE(KPV) case KPV: hipLaunchKernelGGL((ctm_estep_batch_kernel<KPV, false, FILT>), grid, block, lds, ctx->stream, ba); break;
     if (prof && h->KP == 52) hipLaunchKernelGGL((ctm_estep_batch_kernel<52, true, FILT>), grid, block, lds, ctx->stream, ba);
-    else switch (h->KP) { CTM_BCASE(4) CTM_BCASE(12) CTM_BCASE(20) CTM_BCASE(28) CTM_BCASE(36) CTM_BCASE(44)
-                          default: hipLaunchKernelGGL((ctm_estep_batch_kernel<52, false, FILT>), grid, block, lds, ctx->stream, ba); break; }
-#undef CTM_BCASE
+    else if (int lrc = ctm_dispatch_kp(h->KP, [&](auto kp) -> int { hipLaunchKernelGGL((ctm_estep_batch_kernel<decltype(kp)::value, false, FILT>), grid, block, lds, ctx->stream, ba); return TMVB_OK; })) return lrc;
     TMVB_HIP(hipGetLastError());
     if (logging) {
         std::vector<unsigned long long> wl((size_t)n_items * 4);
@@ -1864,6 +1936,66 @@ static int ctm_launch_batch(tmvb_ctm* h, const CtmParams& p, double ntol)
     return TMVB_OK;
 }
 
+// launch of the wave-per-document kernel (register Gauss-Jordan, KP <= 52) on one bucket of documents, for CTM (FILT = false) and fCTM (FILT = true)
+// (measured: compiling for 4 waves per SIMD -- 128 VGPRs, 17 spilled -- changes nothing: 5.98 vs 5.97 ms)
+template <bool FILT>
+static int ctm_launch_wave(tmvb_ctm* h, const CtmParams& p, const tmvb_bucket& b, hipStream_t st)
+{
+    const size_t lds = ctm_tile_bytes(b.tile_rows, h->KP, FILT);
+    const dim3 grid((unsigned)b.count), block(64);
+    return ctm_dispatch_kp(h->KP, [&](auto kp) -> int {
+        hipLaunchKernelGGL((ctm_estep_kernel<decltype(kp)::value, FILT>), grid, block, lds, st, p, b.first, b.tile_rows);
+        TMVB_HIP(hipGetLastError());
+        return TMVB_OK;
+    });
+}
+
+// behind the E-step kernels, on a second side stream (nothing else to wait for): the documents regrouped for the NEXT E-step, then the queue order of its launch
+static int ctm_stage_next_order(tmvb_ctm* h)
+{
+    const int64_t Mb = h->M - h->n_long;
+    if (Mb <= 0) return TMVB_OK;
+    hipStream_t s2 = h->aux[1];
+    TMVB_HIP(hipStreamWaitEvent(s2, h->ev_fork, 0));
+    int rc = ctm_regroup(h, s2);
+    if (rc) return rc;
+    h->reorder_staged = true;
+    const bool wsort = tmvb_env_on("TMVB_CTM_WAVESORT", true);
+    const int64_t nfull = Mb / 64;
+    if (wsort && nfull >= 2 && nfull <= CTM_WAVESORT_MAX) {
+        int P = 2; while (P < nfull) P <<= 1;
+        hipLaunchKernelGGL(ctm_wave_key_kernel, dim3((unsigned)nfull), dim3(64), 0, s2, h->d_doc_order + h->n_long, h->corp->d_doc_ptr,
+                           h->d_doc_newton, h->d_wave_keys);
+        hipLaunchKernelGGL(ctm_wave_sort_kernel, dim3(1), dim3(1024), 0, s2, h->d_wave_keys, (int)nfull, P);
+        hipLaunchKernelGGL(ctm_wave_permute_kernel, dim3((unsigned)((Mb + 255) / 256)), dim3(256), 0, s2, h->d_doc_order + h->n_long,
+                           h->d_wave_keys, (int)nfull, Mb, h->d_doc_order_q);
+        TMVB_HIP(hipGetLastError());
+        h->queue_sorted = true;
+    }
+    TMVB_HIP(hipEventRecord(h->ev_spec2, s2));
+    h->spec2_pending = true;
+    return TMVB_OK;
+}
+
+// The document reductions of tmvb_ctm_reduce_docs (sum lambda, sum vsq, the scatter matrix with the current mu: 0.15 ms of small
+// kernels) depend only on what the document kernels just wrote: they run on a side stream under the statistics pass, and
+// tmvb_ctm_reduce_docs finds them done (tail_fresh; any change of lambda / vsq / mu through the API clears the flag).  Behind the tail, still
+// under the statistics pass: update_sigma! staged (single process only: a sharded run all-reduces the tail first) and the next document order.
+static int ctm_fold_tail(tmvb_ctm* h)
+{
+    TMVB_HIP(hipEventRecord(h->ev_fork, h->ctx->stream));
+    TMVB_HIP(hipStreamWaitEvent(h->aux[0], h->ev_fork, 0));
+    int rc = ctm_reduce_docs_on(h, h->aux[0]);
+    if (rc) return rc;
+    TMVB_HIP(hipEventRecord(h->ev_join[0], h->aux[0]));
+    if (!tmvb_env_on("TMVB_CTM_SPECULATE", true)) return TMVB_OK;     // (read per call: the tests run both ways in one process)
+    if (!h->distributed) { if ((rc = ctm_sigma_mu(h, 1, 0, true, h->aux[0]))) return rc; h->sigma_staged = true; }
+    if (h->batch && h->reorder && h->keys_valid && (rc = ctm_stage_next_order(h))) return rc;
+    TMVB_HIP(hipEventRecord(h->ev_spec, h->aux[0]));
+    h->spec_pending = true;
+    return TMVB_OK;
+}
+
 extern "C" int tmvb_ctm_estep(tmvb_ctm* h, int32_t niter, double ntol, int32_t viter, double vtol)
 {
     TMVB_REQUIRE(h != nullptr, TMVB_EINVAL, "tmvb_ctm_estep: handle is NULL");
@@ -1871,15 +2003,7 @@ extern "C" int tmvb_ctm_estep(tmvb_ctm* h, int32_t niter, double ntol, int32_t v
     TMVB_REQUIRE(vtol >= 0 && ntol >= 0, TMVB_EINVAL, "tolerance parameters must be nonnegative.");     // src/gpuCTM.jl:489
     tmvb_ctx* ctx = h->ctx;
     TMVB_HIP(hipSetDevice(ctx->device));
-    CtmParams p;
-    p.K = h->K; p.KP = h->KP; p.LPR = h->KP / 4; p.lpr_magic = (unsigned)(0x100000000ull / (unsigned)p.LPR) + 1u;
-    p.doc_ptr = h->corp->d_doc_ptr; p.terms = h->corp->d_terms; p.counts = h->corp->d_counts;
-    p.doc_order = h->d_doc_order; p.tok_inv = h->corp->term_index.d_inv;
-    p.beta = h->d_beta[h->cur]; p.invsigma = h->d_invsigma_f; p.mu = h->d_mu_f;
-    p.lambda = h->d_lambda; p.lambda_old = h->d_lambda_old; p.vsq = h->d_vsq; p.logzeta = h->d_logzeta;
-    p.wtok = h->d_wtok; p.E = h->d_E; p.estride = (h->KP / 4 <= 64) ? h->KP : h->K; p.sweeps = h->d_sweeps; p.newton_steps = h->d_newton;
-    p.niter = niter; p.ntol = ntol; p.viter = viter; p.vtol = vtol;
-    p.debug = 0;
+    CtmParams p = ctm_params(h, niter, ntol, viter, vtol);
     p.store_w = tmvb_termstats_recomputes(h->KP, h->KP / 4 <= 64) ? 0 : 1;
     // decomposed update_elbo!: this iteration will be checked -- the document kernels leave pdot, the statistics pass the log-normaliser sums
     const bool collect = (h->parts_env == 2 || (h->parts_env != 0 && h->want_parts)) && p.store_w == 0 && viter > 0;
@@ -1910,82 +2034,16 @@ extern "C" int tmvb_ctm_estep(tmvb_ctm* h, int32_t niter, double ntol, int32_t v
         for (int a = 0; a < naux; ++a) TMVB_HIP(hipStreamWaitEvent(h->aux[a], h->ev_fork, 0));
     }
     for (int bi = 0; bi < nb; ++bi) {
-        const tmvb_bucket& b = h->buckets[bi];
-        hipStream_t st = (naux > 0) ? h->aux[bi % naux] : ctx->stream;
-        const size_t lds = tmvb_tile_bytes(b.tile_rows, h->KP);
-        const dim3 grid((unsigned)b.count), block(64);
-#define CTM_CASE(KPV) case KPV: hipLaunchKernelGGL((ctm_estep_kernel<KPV, false>), grid, block, lds, st, p, b.first, b.tile_rows); break;
-        // (measured: compiling for 4 waves per SIMD -- 128 VGPRs, 17 spilled -- changes nothing: 5.98 vs 5.97 ms)
-        switch (h->KP) { CTM_CASE(4) CTM_CASE(12) CTM_CASE(20) CTM_CASE(28) CTM_CASE(36) CTM_CASE(44)
-                         default: hipLaunchKernelGGL((ctm_estep_kernel<52, false>), grid, block, lds, st, p, b.first, b.tile_rows); break; }
-#undef CTM_CASE
-        TMVB_HIP(hipGetLastError());
+        int wrc = ctm_launch_wave<false>(h, p, h->buckets[bi], (naux > 0) ? h->aux[bi % naux] : ctx->stream);
+        if (wrc) return wrc;
     }
-    if (h->batch && h->M > 0) {
-        // round 6: four waves per wave-of-documents (tmvb_ctm_quad.h), two workgroups per CU; TMVB_CTM_QUAD=0 (or the profiling build of the
-        // one-wave kernel, TMVB_CTM_PROF=1) selects round 3's one-wave kernel
-        static const bool quad = tmvb_env_on("TMVB_CTM_QUAD", true) && !tmvb_env_on("TMVB_CTM_PROF", false);
-        // (the four-waves kernel wants 78 KB of LDS per workgroup at KP = 52: on a device whose per-workgroup limit is below that the one-wave kernel -- 40 KB -- runs)
-        if (h->lds_limit < 0) {
-            int v = 0;
-            if (hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, ctx->device) != hipSuccess || v <= 0) { (void)hipGetLastError(); v = 64 * 1024; }
-            h->lds_limit = v;
-        }
-        const size_t quad_lds = (size_t)(5 * h->KP * 64 + 2 * 3 * 4 * 64) * 4 + (size_t)(2 * 4 * 64) * 8 + (5 * 64 + 4) * 4;
-        int brc = (quad && quad_lds <= (size_t)h->lds_limit) ? ctm_launch_quad(h, p, ntol) : ctm_launch_batch<false>(h, p, ntol);
-        if (brc) return brc;
+    if (h->batch && h->M > 0) { int brc = ctm_launch_lane(h, p, ntol); if (brc) return brc; }
+    for (int a = 0; a < naux; ++a) {
+        TMVB_HIP(hipEventRecord(h->ev_join[a], h->aux[a]));
+        TMVB_HIP(hipStreamWaitEvent(ctx->stream, h->ev_join[a], 0));
     }
-    if (naux > 0) {
-        for (int a = 0; a < naux; ++a) {
-            TMVB_HIP(hipEventRecord(h->ev_join[a], h->aux[a]));
-            TMVB_HIP(hipStreamWaitEvent(ctx->stream, h->ev_join[a], 0));
-        }
-    }
-    // The document reductions of tmvb_ctm_reduce_docs (sum lambda, sum vsq, the scatter matrix with the current mu: 0.15 ms of small
-    // kernels) depend only on what the document kernels just wrote: they run here on a side stream under the statistics pass, and
-    // tmvb_ctm_reduce_docs finds them done (tail_fresh; any change of lambda / vsq / mu through the API clears the flag).
-    const bool folded = h->M > 0 && h->aux[0] != nullptr;
-    if (folded) {
-        TMVB_HIP(hipEventRecord(h->ev_fork, ctx->stream));
-        TMVB_HIP(hipStreamWaitEvent(h->aux[0], h->ev_fork, 0));
-        int frc = ctm_reduce_docs_on(h, h->aux[0]);
-        if (frc) return frc;
-        TMVB_HIP(hipEventRecord(h->ev_join[0], h->aux[0]));
-        // behind the tail, still under the statistics pass: update_sigma! staged (single process only: a sharded run all-reduces the
-        // tail first) and the documents regrouped for the next E-step
-        const bool spec = tmvb_env_on("TMVB_CTM_SPECULATE", true);     // (read per call: the tests run both ways in one process)
-        if (spec) {
-            if (!h->distributed) { frc = ctm_sigma_mu(h, 1, 0, true, h->aux[0]); if (frc) return frc; h->sigma_staged = true; }
-            if (h->batch && h->reorder && h->keys_valid) {
-                // on a second side stream (nothing but the E-step kernels to wait for): regroup, then the queue order of the launch
-                const int64_t Mb = h->M - h->n_long;
-                if (Mb > 0) {
-                    hipStream_t s2 = h->aux[1];
-                    TMVB_HIP(hipStreamWaitEvent(s2, h->ev_fork, 0));
-                    hipLaunchKernelGGL(ctm_reorder_kernel, dim3((unsigned)((Mb + CTM_REORDER_CHUNK - 1) / CTM_REORDER_CHUNK)), dim3(1024), 0, s2,
-                                       h->d_doc_order0 + h->n_long, h->d_doc_newton, h->d_doc_order + h->n_long, Mb);
-                    TMVB_HIP(hipGetLastError());
-                    h->reorder_staged = true;
-                    const bool wsort = tmvb_env_on("TMVB_CTM_WAVESORT", true);
-                    const int64_t nfull = Mb / 64;
-                    if (wsort && nfull >= 2 && nfull <= CTM_WAVESORT_MAX) {
-                        int P = 2; while (P < nfull) P <<= 1;
-                        hipLaunchKernelGGL(ctm_wave_key_kernel, dim3((unsigned)nfull), dim3(64), 0, s2, h->d_doc_order + h->n_long, h->corp->d_doc_ptr,
-                                           h->d_doc_newton, h->d_wave_keys);
-                        hipLaunchKernelGGL(ctm_wave_sort_kernel, dim3(1), dim3(1024), 0, s2, h->d_wave_keys, (int)nfull, P);
-                        hipLaunchKernelGGL(ctm_wave_permute_kernel, dim3((unsigned)((Mb + 255) / 256)), dim3(256), 0, s2, h->d_doc_order + h->n_long,
-                                           h->d_wave_keys, (int)nfull, Mb, h->d_doc_order_q);
-                        TMVB_HIP(hipGetLastError());
-                        h->queue_sorted = true;
-                    }
-                    TMVB_HIP(hipEventRecord(h->ev_spec2, s2));
-                    h->spec2_pending = true;
-                }
-            }
-            TMVB_HIP(hipEventRecord(h->ev_spec, h->aux[0]));
-            h->spec_pending = true;
-        }
-    }
+    const bool folded = h->M > 0 && h->aux[0] != nullptr;      // the statistics tail (and what is staged behind it) on side streams under the statistics pass
+    if (folded) { int frc = ctm_fold_tail(h); if (frc) return frc; }
     // update_beta!(model, d)  src/CTM.jl:122-125 as the gather-side statistics pass (no epsilon in CTM's phi)
     TermStatsParams tp;
     tp.K = h->K; tp.tstride = h->KP; tp.ostride = h->K;
@@ -1999,6 +2057,21 @@ extern "C" int tmvb_ctm_estep(tmvb_ctm* h, int32_t niter, double ntol, int32_t v
     TMVB_HIP(hipEventRecord(h->ev1, ctx->stream));
     h->timed = true;
     return TMVB_OK;
+}
+
+// (defined behind tmvb_ctm_estep: hipcc emits a unit's kernel instantiations in the order of their first use, and that order stays what it was)
+// the lane-per-document launch of CTM: round 6's four waves per wave-of-documents (tmvb_ctm_quad.h), two workgroups per CU; TMVB_CTM_QUAD=0 (or the
+// profiling build of the one-wave kernel, TMVB_CTM_PROF=1) selects round 3's one-wave kernel
+static int ctm_launch_lane(tmvb_ctm* h, const CtmParams& p, double ntol)
+{
+    static const bool quad = tmvb_env_on("TMVB_CTM_QUAD", true) && !tmvb_env_on("TMVB_CTM_PROF", false);
+    // (the four-waves kernel wants 78 KB of LDS per workgroup at KP = 52: on a device whose per-workgroup limit is below that the one-wave kernel -- 40 KB -- runs)
+    if (h->lds_limit < 0) {
+        int v = 0;
+        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, h->ctx->device) != hipSuccess || v <= 0) { (void)hipGetLastError(); v = 64 * 1024; }
+        h->lds_limit = v;
+    }
+    return (quad && ctm_quad_lds_bytes(h->KP) <= (size_t)h->lds_limit) ? ctm_launch_quad(h, p, ntol) : ctm_launch_batch<false>(h, p, ntol);
 }
 
 // sum_d lambda_d, sum_d vsq_d and the scatter matrix (with the CURRENT = previous-iteration mu) into the statistics tail
@@ -2157,27 +2230,17 @@ extern "C" int tmvb_ctm_update_elbo(tmvb_ctm* h, double* elbo)
     TMVB_HIP(hipSetDevice(ctx->device));
     const bool parts = h->logz_valid && h->pw_valid && !h->force_walk;         // everything per token was left behind by the iteration itself
     h->elbo_form = parts ? 1 : 0;
-    if (parts && h->M > 0) {
-#define CTM_ELBO_DOC(NSV) hipLaunchKernelGGL((ctm_elbo_kernel<NSV, false>), dim3((unsigned)h->M), dim3(64), 0, ctx->stream, h->K, h->KP, h->corp->d_doc_ptr, \
-                               h->corp->d_terms, h->corp->d_counts, h->d_mu, h->d_invsigma, h->d_logdet, h->d_beta[h->cur], \
-                               h->d_beta[h->cur ^ 1], h->d_lambda, h->d_lambda_old, h->d_vsq, h->d_logzeta, h->d_doc_val, h->d_pdot)
-        if (h->nslot == 1) CTM_ELBO_DOC(1); else if (h->nslot == 2) CTM_ELBO_DOC(2); else CTM_ELBO_DOC(4);
-#undef CTM_ELBO_DOC
-        TMVB_HIP(hipGetLastError());
-    } else
     if (h->M > 0) {
-        if (h->nslot == 1)
-            hipLaunchKernelGGL((ctm_elbo_kernel<1>), dim3((unsigned)h->M), dim3(64), 0, ctx->stream, h->K, h->KP, h->corp->d_doc_ptr,
-                               h->corp->d_terms, h->corp->d_counts, h->d_mu, h->d_invsigma, h->d_logdet, h->d_beta[h->cur],
-                               h->d_beta[h->cur ^ 1], h->d_lambda, h->d_lambda_old, h->d_vsq, h->d_logzeta, h->d_doc_val);
-        else if (h->nslot == 2)
-            hipLaunchKernelGGL((ctm_elbo_kernel<2>), dim3((unsigned)h->M), dim3(64), 0, ctx->stream, h->K, h->KP, h->corp->d_doc_ptr,
-                               h->corp->d_terms, h->corp->d_counts, h->d_mu, h->d_invsigma, h->d_logdet, h->d_beta[h->cur],
-                               h->d_beta[h->cur ^ 1], h->d_lambda, h->d_lambda_old, h->d_vsq, h->d_logzeta, h->d_doc_val);
-        else
-            hipLaunchKernelGGL((ctm_elbo_kernel<4>), dim3((unsigned)h->M), dim3(64), 0, ctx->stream, h->K, h->KP, h->corp->d_doc_ptr,
-                               h->corp->d_terms, h->corp->d_counts, h->d_mu, h->d_invsigma, h->d_logdet, h->d_beta[h->cur],
-                               h->d_beta[h->cur ^ 1], h->d_lambda, h->d_lambda_old, h->d_vsq, h->d_logzeta, h->d_doc_val);
+        // per document: the decomposed form (TOK = false, with the E-step's pdot) or the token walk
+        auto per_doc = [&](auto tok) {
+            ctm_dispatch_nslot(h->nslot, [&](auto ns) {
+                hipLaunchKernelGGL((ctm_elbo_kernel<decltype(ns)::value, decltype(tok)::value>), dim3((unsigned)h->M), dim3(64), 0, ctx->stream, h->K, h->KP,
+                                   h->corp->d_doc_ptr, h->corp->d_terms, h->corp->d_counts, h->d_mu, h->d_invsigma, h->d_logdet, h->d_beta[h->cur],
+                                   h->d_beta[h->cur ^ 1], h->d_lambda, h->d_lambda_old, h->d_vsq, h->d_logzeta, h->d_doc_val,
+                                   decltype(tok)::value ? (const float*)nullptr : (const float*)h->d_pdot);
+            });
+        };
+        if (parts) per_doc(std::false_type()); else per_doc(std::true_type());
         TMVB_HIP(hipGetLastError());
     }
     if (parts)
@@ -2186,15 +2249,7 @@ extern "C" int tmvb_ctm_update_elbo(tmvb_ctm* h, double* elbo)
     else
         hipLaunchKernelGGL(sum_docs_kernel, dim3(1), dim3(1024), 0, ctx->stream, h->d_doc_val, h->M, h->d_elbo);
     TMVB_HIP(hipGetLastError());
-    double v = 0.0;
-    int st = 0;
-    TMVB_HIP(hipMemcpyAsync(&v, h->d_elbo, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    TMVB_HIP(hipMemcpyAsync(&st, h->d_status, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    TMVB_HIP(hipStreamSynchronize(ctx->stream));
-    TMVB_REQUIRE(st == 0, TMVB_ENONFINITE, "sigma must be positive-definite.");
-    h->elbo = v;
-    if (elbo) *elbo = v;
-    return TMVB_OK;
+    return ctm_fetch_elbo(h, elbo);
 }
 
 extern "C" int tmvb_ctm_elbo_form(tmvb_ctm* h, int32_t* form) { return tmvb_model_elbo_form("tmvb_ctm_elbo_form", h, form); }
@@ -2621,14 +2676,8 @@ extern "C" int tmvb_fctm_estep(tmvb_fctm* h, int32_t niter, double ntol, int32_t
     tmvb_ctm* b = h->base;
     tmvb_ctx* ctx = b->ctx;
     TMVB_HIP(hipSetDevice(ctx->device));
-    CtmParams p;
-    p.K = b->K; p.KP = b->KP; p.LPR = b->KP / 4; p.lpr_magic = (unsigned)(0x100000000ull / (unsigned)p.LPR) + 1u;
-    p.doc_ptr = b->corp->d_doc_ptr; p.terms = b->corp->d_terms; p.counts = b->corp->d_counts;
-    p.doc_order = b->d_doc_order; p.tok_inv = b->corp->term_index.d_inv;
-    p.beta = b->d_beta[b->cur]; p.invsigma = b->d_invsigma_f; p.mu = b->d_mu_f;
-    p.lambda = b->d_lambda; p.lambda_old = b->d_lambda_old; p.vsq = b->d_vsq; p.logzeta = b->d_logzeta;
-    p.wtok = b->d_wtok; p.E = b->d_E; p.estride = (b->KP / 4 <= 64) ? b->KP : b->K; p.sweeps = b->d_sweeps; p.newton_steps = b->d_newton;
-    p.niter = niter; p.ntol = ntol; p.viter = viter; p.vtol = vtol; p.debug = 0; p.store_w = 0;
+    CtmParams p = ctm_params(b, niter, ntol, viter, vtol);
+    p.store_w = 0;
     p.L = h->d_L; p.kappa = h->d_kappa; p.eta = (float)h->eta; p.tau = h->d_tau; p.tau_old = h->d_tau_old; p.lse = h->d_lse;
     // decomposed update_elbo! (fctm_elbo_doc_parts_kernel): an iteration that will be checked stores the per-token exponent and the per-document
     // sum_i (phi counts)_i (lambda_i - lambda_old_i); viter = 0 leaves no responsibilities (token walk)
@@ -2643,15 +2692,7 @@ extern "C" int tmvb_fctm_estep(tmvb_fctm* h, int32_t niter, double ntol, int32_t
     } else {
         // lane-per-document kernel for all but the long documents (b->n_long; the buckets then hold only those), else every bucket
         if (b->batch && b->M > 0) { int brc = ctm_launch_batch<true>(b, p, ntol); if (brc) return brc; }
-        for (const tmvb_bucket& bk : b->buckets) {
-            const size_t lds = ctm_tile_bytes(bk.tile_rows, b->KP, true);
-            const dim3 grid((unsigned)bk.count), block(64);
-#define FCTM_CASE(KPV) case KPV: hipLaunchKernelGGL((ctm_estep_kernel<KPV, true>), grid, block, lds, ctx->stream, p, bk.first, bk.tile_rows); break;
-            switch (b->KP) { FCTM_CASE(4) FCTM_CASE(12) FCTM_CASE(20) FCTM_CASE(28) FCTM_CASE(36) FCTM_CASE(44)
-                             default: hipLaunchKernelGGL((ctm_estep_kernel<52, true>), grid, block, lds, ctx->stream, p, bk.first, bk.tile_rows); break; }
-#undef FCTM_CASE
-            TMVB_HIP(hipGetLastError());
-        }
+        for (const tmvb_bucket& bk : b->buckets) { int wrc = ctm_launch_wave<true>(b, p, bk, ctx->stream); if (wrc) return wrc; }
     }
     FldaStatsParams sp;
     sp.K = b->K; sp.KP = b->KP; sp.L = h->d_L; sp.elog_old = b->d_lambda_old; sp.tau = h->d_tau; sp.tau_old = h->d_tau_old; sp.lse = h->d_lse;
@@ -2695,48 +2736,29 @@ extern "C" int tmvb_fctm_update_elbo(tmvb_fctm* h, double* elbo)
     TMVB_HIP(hipSetDevice(ctx->device));
     const bool parts = b->filt_pw_valid && !h->force_walk && h->parts_env != 0;
     h->elbo_form = parts ? 1 : 0;
-    if (parts) {
-        if (b->M > 0) {
-            const dim3 grid((unsigned)b->M), block(64);
-#define FCTM_PARTS(NSV) hipLaunchKernelGGL((fctm_elbo_doc_parts_kernel<NSV>), grid, block, 0, ctx->stream, b->K, b->corp->d_doc_ptr, b->corp->d_terms, b->corp->d_counts, \
-                               b->d_mu, b->d_invsigma, b->d_logdet, h->eta, h->d_kappa, b->d_lambda, b->d_vsq, b->d_logzeta, h->d_tau, h->d_tau_old, h->d_lse, \
-                               h->d_aold, b->d_pdot, b->d_doc_val)
-            if (b->nslot == 1) FCTM_PARTS(1); else if (b->nslot == 2) FCTM_PARTS(2); else FCTM_PARTS(4);
-#undef FCTM_PARTS
-            TMVB_HIP(hipGetLastError());
-        }
-        hipLaunchKernelGGL(ctm_elbo_final_kernel, dim3(1), dim3(1024), 0, ctx->stream, b->d_doc_val, b->M, (const double*)nullptr, (int64_t)0, b->d_pw_partial, b->pw_blocks,
-                           b->distributed && b->M_total > 0 ? (double)b->M / (double)b->M_total : 1.0, b->d_elbo);
-        TMVB_HIP(hipGetLastError());
-    } else {
     if (b->M > 0) {
         const dim3 grid((unsigned)b->M), block(64);
-        if (b->nslot == 1)
-            hipLaunchKernelGGL((fctm_elbo_kernel<1>), grid, block, 0, ctx->stream, b->K, b->KP, b->corp->d_doc_ptr, b->corp->d_terms, b->corp->d_counts,
-                               b->d_mu, b->d_invsigma, b->d_logdet, h->eta, h->d_kappa, b->d_beta[b->cur], b->d_beta[b->cur ^ 1], b->d_lambda,
-                               b->d_lambda_old, b->d_vsq, b->d_logzeta, h->d_tau, h->d_tau_old, b->d_doc_val);
-        else if (b->nslot == 2)
-            hipLaunchKernelGGL((fctm_elbo_kernel<2>), grid, block, 0, ctx->stream, b->K, b->KP, b->corp->d_doc_ptr, b->corp->d_terms, b->corp->d_counts,
-                               b->d_mu, b->d_invsigma, b->d_logdet, h->eta, h->d_kappa, b->d_beta[b->cur], b->d_beta[b->cur ^ 1], b->d_lambda,
-                               b->d_lambda_old, b->d_vsq, b->d_logzeta, h->d_tau, h->d_tau_old, b->d_doc_val);
+        if (parts)
+            ctm_dispatch_nslot(b->nslot, [&](auto ns) {
+                hipLaunchKernelGGL((fctm_elbo_doc_parts_kernel<decltype(ns)::value>), grid, block, 0, ctx->stream, b->K, b->corp->d_doc_ptr, b->corp->d_terms,
+                                   b->corp->d_counts, b->d_mu, b->d_invsigma, b->d_logdet, h->eta, h->d_kappa, b->d_lambda, b->d_vsq, b->d_logzeta, h->d_tau,
+                                   h->d_tau_old, h->d_lse, h->d_aold, b->d_pdot, b->d_doc_val);
+            });
         else
-            hipLaunchKernelGGL((fctm_elbo_kernel<4>), grid, block, 0, ctx->stream, b->K, b->KP, b->corp->d_doc_ptr, b->corp->d_terms, b->corp->d_counts,
-                               b->d_mu, b->d_invsigma, b->d_logdet, h->eta, h->d_kappa, b->d_beta[b->cur], b->d_beta[b->cur ^ 1], b->d_lambda,
-                               b->d_lambda_old, b->d_vsq, b->d_logzeta, h->d_tau, h->d_tau_old, b->d_doc_val);
+            ctm_dispatch_nslot(b->nslot, [&](auto ns) {
+                hipLaunchKernelGGL((fctm_elbo_kernel<decltype(ns)::value>), grid, block, 0, ctx->stream, b->K, b->KP, b->corp->d_doc_ptr, b->corp->d_terms,
+                                   b->corp->d_counts, b->d_mu, b->d_invsigma, b->d_logdet, h->eta, h->d_kappa, b->d_beta[b->cur], b->d_beta[b->cur ^ 1],
+                                   b->d_lambda, b->d_lambda_old, b->d_vsq, b->d_logzeta, h->d_tau, h->d_tau_old, b->d_doc_val);
+            });
         TMVB_HIP(hipGetLastError());
     }
-    hipLaunchKernelGGL(sum_docs_kernel, dim3(1), dim3(1024), 0, ctx->stream, b->d_doc_val, b->M, b->d_elbo);
+    if (parts)
+        hipLaunchKernelGGL(ctm_elbo_final_kernel, dim3(1), dim3(1024), 0, ctx->stream, b->d_doc_val, b->M, (const double*)nullptr, (int64_t)0, b->d_pw_partial, b->pw_blocks,
+                           b->distributed && b->M_total > 0 ? (double)b->M / (double)b->M_total : 1.0, b->d_elbo);
+    else
+        hipLaunchKernelGGL(sum_docs_kernel, dim3(1), dim3(1024), 0, ctx->stream, b->d_doc_val, b->M, b->d_elbo);
     TMVB_HIP(hipGetLastError());
-    }
-    double v = 0.0;
-    int st = 0;
-    TMVB_HIP(hipMemcpyAsync(&v, b->d_elbo, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    TMVB_HIP(hipMemcpyAsync(&st, b->d_status, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    TMVB_HIP(hipStreamSynchronize(ctx->stream));
-    TMVB_REQUIRE(st == 0, TMVB_ENONFINITE, "sigma must be positive-definite.");
-    b->elbo = v;
-    if (elbo) *elbo = v;
-    return TMVB_OK;
+    return ctm_fetch_elbo(b, elbo);
 }
 
 extern "C" int tmvb_fctm_elbo_form(tmvb_fctm* h, int32_t* form) { return tmvb_model_elbo_form("tmvb_fctm_elbo_form", h, form); }
@@ -2795,3 +2817,4 @@ extern "C" int tmvb_fctm_sweep_hist(tmvb_fctm* h, int64_t* hist, int32_t nbins, 
     TMVB_REQUIRE(h != nullptr, TMVB_EINVAL, "tmvb_fctm_sweep_hist: handle is NULL");
     return tmvb_ctm_sweep_hist(h->base, hist, nbins, newton_steps);
 }
+extern "C" int tmvb_fctm_solver_stats(tmvb_fctm* h, int64_t* out12) { TMVB_REQUIRE(h != nullptr, TMVB_EINVAL, "tmvb_fctm_solver_stats: handle is NULL"); return tmvb_ctm_solver_stats(h->base, out12); }
