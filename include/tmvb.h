@@ -1157,6 +1157,63 @@ int tmvb_term_relevance(tmvb_ctx* ctx, int32_t K, int64_t V, const double* beta,
                         tmvb_relevance_info_t* info);
 int tmvb_assignment(int32_t n, int32_t m, const double* cost, int32_t* row_to_col, double* total);
 
+/* ============================== topics by group and over time: grouped word-topic statistics ==============================
+ * How the topics differ between parts of the corpus (years, journals, author classes, cluster labels): for every group g of documents the
+ * sufficient statistics of the topic-word matrix restricted to g (the reference has no such function; topics_over_time / topics_per_class
+ * elsewhere).  Stateless and family-agnostic like tmvb_token_topics, whose conventions apply: everything is on the HOST, A is K x M and B is
+ * K x V, column-major fp64, nonnegative; the CSR is doc_ptr[M + 1], terms, counts (ids in any order, repeats inside a document legal).
+ *
+ * ---- tmvb_group_topics.  group[d] in [0, G) names the group of document d, -1 leaves the document out.
+ * Responsibilities: r_k of an entry (w, c) of document d are EXACTLY those of tmvb_token_topics: A, B and eps rounded once to fp32,
+ * y_k = fma(A[k, d], B[k, w], eps), the sum in that function's fixed order, r_k = y_k / S the IEEE fp32 division (one device function serves both).
+ * Index: the entries of the documents with group[d] >= 0, ordered by (group, term, document, position in the document); a RUN is the entries of
+ * one (group, term).  tmvb_group_index returns exactly this order (np.lexsort on the four keys).
+ * S_g[k, w] = the fp64 sum over the run's entries of (double)c * (double)r_k (the product is exact for c < 2^29).  Order: a run is cut into
+ * segments of TMVB_GT_SEG consecutive entries; inside a segment entry i goes to slot i mod E, E = 64 / lanes_per_entry; a slot adds its
+ * entries sequentially ascending from 0; the E slot sums meet in an xor butterfly over the slot number (distances 1, 2, 4, ...: a fixed tree);
+ * the segment sums of a run are added sequentially in ascending order, starting from the first.  The order is a function of the inputs alone:
+ * not of which workgroup finishes first, of max_chunk_groups or of the outputs asked for.  No floating-point atomics.
+ * mass[g][k] = sum_w S_g[k, w]: lane t of 256 adds w = t, t + 256, ... ascending from 0, the 256 sums meet in a halving tree (t += t + 128,
+ * then 64, ...).  tokens[g] = sum of c, docs[g] = documents with group[d] == g (empty ones included): exact integers.  sum_k mass[g][k] equals
+ * tokens[g] up to rounding; the prevalence of topic k in g is mass[g][k] / sum_j mass[g][j], the caller's to compute.
+ * top_idx[g][k][n], top_p[g][k][n]: with beta_g[k, w] = S_g[k, w] / mass[g][k] the n best terms of the row under the total order (p descending,
+ * term id ascending on equal p) and their p; the stable descending segmented radix sort of tmvb_term_relevance, chunk_groups K segments of V.
+ * A row with mass 0 -- every row of a group without entries -- gets -1 and 0 in every slot.
+ * shift[g][k] = the Jensen-Shannon divergence (nats; the addend and the clamp of TMVB_TD_JS) of beta_g[k, .] from the pooled row
+ * pooled[k, .] = (sum_g S_g[k, .] added in ascending g from 0) / its row sum (the order of mass).  drift[g][k] = the same divergence from
+ * beta_g'[k, .], g' the nearest lower group id that has entries; 0 for the first group with entries.  Both are 0 for a group without entries.
+ * The sum over w runs in the order of mass.  shift and drift may be NULL, together or singly.  dense (or NULL) receives every S_g, [G][K][V].
+ * max_chunk_groups bounds the groups whose K x V fp64 blocks are on the device at once; 0 = the library's choice: as many as keep that buffer
+ * at 256 MiB and chunk_groups K V < 2^31 (the sort).  EVERY output is bit-identical for every value of it, over calls, and with or without
+ * dense, shift or drift.  (With more than one chunk and shift asked for, the statistics are accumulated twice: the pooled row needs every group.)
+ * S, mass, tokens and docs are additive over document shards (up to the rounding of the fp64 sums); the selection and the divergences are not.
+ * info (or NULL): nsel = selected entries, runs, segments = work items of the accumulation kernel, group_chunks, lanes_per_entry, ms_index =
+ * host time of the index build, ms_accum / ms_select / ms_shift = device time of the accumulation with its combine and row sums, of the
+ * normalisation, sort and selection, and of the pooled row with both divergences (HIP events around the kernels only).
+ * Errors, judged before the device is touched -> TMVB_EINVAL: K outside [1, 1024], G outside [1, 65536], eps outside [2^-100, 1] or NaN, M <= 0
+ * or V <= 0 (or 2^31 - 1 and more), n outside [1, min(V, 64)], K V >= 2^31, a NULL required argument (everything but shift, drift, dense and
+ * info), max_chunk_groups < 0; then the data: a doc_ptr that does not start at 0 or decreases, 2^31 - 2 or more entries, a term outside
+ * [0, V), a count < 1 or >= 2^29, a group id outside [-1, G), a negative, NaN or beyond-fp32 value of B or of a selected column of A.  Then
+ * ctx == NULL without a visible device -> TMVB_ENODEVICE (there is no CPU path).
+ *
+ * ---- tmvb_group_index.  HOST ONLY, touches no device (like tmvb_digamma_f64): the index the kernel walks, by two stable counting sorts (by
+ * term, then by group) on at most 16 host threads.  *n_runs runs; run u is entries run_ptr[u] .. run_ptr[u + 1] - 1 of entry[], of group
+ * run_group[u] and term run_term[u]; entry[i] is a position in the CSR.  The caller sizes run_ptr for nsel + 1 and run_group / run_term for nsel
+ * elements (the worst case: every entry a run of its own), entry for nsel.  M <= 0, V <= 0, G outside [1, 65536], a NULL argument, a bad CSR,
+ * a term outside [0, V), a group id outside [-1, G) -> TMVB_EINVAL. */
+#ifndef TMVB_GT_SEG
+#define TMVB_GT_SEG 512                                     /* entries per segment of a run: one wave adds up a segment */
+#endif
+#define TMVB_GT_TOP_MAX 64
+#define TMVB_GT_GMAX 65536
+typedef struct { int64_t nsel, runs, segments; int32_t group_chunks, lanes_per_entry; float ms_index, ms_accum, ms_select, ms_shift; } tmvb_group_topics_info_t;
+int tmvb_group_topics(tmvb_ctx* ctx, int32_t K, int64_t V, int64_t M, const double* A, const double* B, const int64_t* doc_ptr,
+                      const int32_t* terms, const int32_t* counts, const int32_t* group, int32_t G, double eps, int32_t n,
+                      int32_t max_chunk_groups, int64_t* docs, int64_t* tokens, double* mass, int32_t* top_idx, double* top_p,
+                      double* shift, double* drift, double* dense, tmvb_group_topics_info_t* info);
+int tmvb_group_index(int64_t M, int64_t V, const int64_t* doc_ptr, const int32_t* terms, const int32_t* group, int32_t G,
+                     int64_t* n_runs, int64_t* run_ptr, int32_t* run_group, int32_t* run_term, int64_t* entry);
+
 #ifdef __cplusplus
 }
 #endif

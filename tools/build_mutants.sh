@@ -1,5 +1,5 @@
 #!/bin/bash
-# The deliberately WRONG libraries of tests/test_mutants_gpu.py, tests/test_heldout_mutant_gpu.py, tests/test_coherence_mutant_gpu.py, tests/test_neighbors_mutant_gpu.py, tests/test_recranks_mutant_gpu.py, tests/test_rectopn_mutant_gpu.py, tests/test_search_mutant_gpu.py, tests/test_token_topics_mutant_gpu.py, tests/test_kmeans_mutant_gpu.py, tests/test_docmap_mutant_gpu.py and tests/test_topic_compare_mutant_gpu.py (negative controls of the parity suite), each = the shipped objects with one
+# The deliberately WRONG libraries of tests/test_mutants_gpu.py, tests/test_heldout_mutant_gpu.py, tests/test_coherence_mutant_gpu.py, tests/test_neighbors_mutant_gpu.py, tests/test_recranks_mutant_gpu.py, tests/test_rectopn_mutant_gpu.py, tests/test_search_mutant_gpu.py, tests/test_token_topics_mutant_gpu.py, tests/test_kmeans_mutant_gpu.py, tests/test_docmap_mutant_gpu.py, tests/test_topic_compare_mutant_gpu.py and tests/test_group_topics_mutant_gpu.py (negative controls of the parity suite), each = the shipped objects with one
 # translation unit recompiled under a -DTMVB_MUTANT_* flag (csrc/tmvb_internal.h lists them):
 #   topicmodelsvb.jl_amd/libtmvb_hip_mut_lda_eps.so     epsilon dropped from LDA's phi / gamma            (src/LDA.jl:152, :145)
 #   topicmodelsvb.jl_amd/libtmvb_hip_mut_ctpf_bet.so    log bet for log vav in CTPF's xi                   (src/CTPF.jl:336 vs src/gpuCTPF.jl:624)
@@ -24,6 +24,7 @@
 #   topicmodelsvb.jl_amd/libtmvb_hip_mut_kmeans_no_bias.so  assignment kernel of the k-means clustering whose epilogue compares the dot products without b_c = -n_c / 2 (tests/test_kmeans_mutant_gpu.py)
 #   topicmodelsvb.jl_amd/libtmvb_hip_mut_docmap_z_with_self.so  normaliser of the document map that keeps the M self terms: Z = the blocked sum of zrow without - M (tests/test_docmap_mutant_gpu.py)
 #   topicmodelsvb.jl_amd/libtmvb_hip_mut_topicdiv_drop_tail.so  pair kernel of the topic divergences without the last partial run of 256 terms (tests/test_topic_compare_mutant_gpu.py)
+#   topicmodelsvb.jl_amd/libtmvb_hip_mut_gt_seg_cut.so  combine kernel of the grouped word-topic statistics without the last segment of a run longer than one segment (tests/test_group_topics_mutant_gpu.py)
 # Needs the shipped build first (python -c "import __graft_entry__ as g; g.build()").  In parallel, but two builds of one translation unit never in the same batch (they share a temporary): tmvb_ctm.hip and
 # tmvb_lda.hip have three variants each (tmvb_core.hip one: mut_index_repeat), hence three batches.  About 4 minutes for the first two batches plus one more build of tmvb_lda.hip and tmvb_ctm.hip.
 cd "$(dirname "$0")/.." || exit 1
@@ -52,5 +53,6 @@ tools/build_variant.sh mut_tt_tie_last tmvb_token_topics.hip -DTMVB_MUTANT_TT_TI
 tools/build_variant.sh mut_kmeans_no_bias tmvb_kmeans.hip -DTMVB_MUTANT_KM_NO_BIAS=1 &
 tools/build_variant.sh mut_docmap_z_with_self tmvb_docmap.hip -DTMVB_MUTANT_MAP_Z_SELF=1 &
 tools/build_variant.sh mut_topicdiv_drop_tail tmvb_topic_compare.hip -DTMVB_MUTANT_TD_DROP_TAIL=1 &
+tools/build_variant.sh mut_gt_seg_cut tmvb_group_topics.hip -DTMVB_MUTANT_GT_SEG_CUT=1 &
 wait
 ls -la topicmodelsvb.jl_amd/libtmvb_hip_mut_*.so

@@ -55,6 +55,8 @@ BENCHED = {
     "map_affinity_kernel": 0, "map_repulse_kernel": 0, "map_finish_kernel": 0, "map_attract_kernel<": 0, "map_update_kernel": 0,
     # topic comparison (tools/topic_compare_bench.py): the transpose, the fp64 pair kernel under its four metrics, the merge of the run sums; relevance
     "td_prep_kernel": 0, "td_pairs_kernel<": 0, "td_merge_kernel<": 0, "tr_score_kernel": 0, "tr_select_kernel": 0, "tr_terms_kernel": 0,
+    # topics by group (tools/group_topics_bench.py): the accumulation over the (group, term) index, the combine of the long runs, the fixed-order row kernels
+    "group_topics_kernel": 0, "gt_combine_kernel": 0, "gt_rowsum_kernel": 0, "gt_norm_kernel": 0, "gt_pool_kernel": 0, "gt_select_kernel": 0, "gt_js_kernel": 0,
     # stochastic LDA training (tools/svi_bench.py): the fused global update -- blend + partial row sums, then normalise
     "svi_blend_kernel<": 0, "svi_norm_kernel": 0,
     # stochastic CTM training (tools/ctm_svi_bench.py): the tail of the fused global update -- recentre in fp64, blend (the K x V part is the two above)

@@ -25,6 +25,7 @@ from .topic_compare import (RelevantTerms, TopicComparison, TopicMap, TopicStabi
                             topic_word_matrix)
 from .search import SearchInfo, SearchResult, pack_queries, search, search_raw
 from .token_topics import TokenTopics, phi, token_factors, token_topics, token_topics_raw
+from .group_topics import GroupTopics, group_index_raw, group_topics, group_topics_raw, time_bins
 from .recs_eval import (HeldReaders, RecEvalResult, rank_metrics, rank_metrics_raw, rec_eval, rec_quality, rec_ranks_raw, split_readers,
                         split_readers_raw)
 from .recs_topn import RecTopN, rec_topn_raw, recommend_topn
@@ -48,6 +49,7 @@ __all__ = ["CorpusError", "DocumentError", "EngineError", "TopicModelError", "bu
            "topic_word_matrix",
            "SearchInfo", "SearchResult", "pack_queries", "search", "search_raw",
            "TokenTopics", "phi", "token_factors", "token_topics", "token_topics_raw",
+           "GroupTopics", "group_index_raw", "group_topics", "group_topics_raw", "time_bins",
            "HeldReaders", "RecEvalResult", "rank_metrics", "rank_metrics_raw", "rec_eval", "rec_quality", "rec_ranks_raw", "split_readers", "split_readers_raw",
            "RecTopN", "rec_topn_raw", "recommend_topn",
            "FOLDIN_REG_CAPACITY", "FOLDIN_REG_CAPACITY_BIGK", "FoldinUsers", "foldin_libraries", "foldin_reg_capacity", "foldin_users", "foldin_users_raw",

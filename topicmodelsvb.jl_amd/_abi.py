@@ -62,6 +62,8 @@ FoldinInfo = _struct("FoldinInfo", "tmvb_foldin_info_t", "i32: kp capacity; i64:
 SviInfo = _struct("SviInfo", "tmvb_lda_svi_info_t, tmvb_ctm_svi_info_t", "i32: B K; i64: M V t; f64: tau0 kappa rho; f32: c0 c1")
 TopicDivInfo = _struct("TopicDivInfo", "tmvb_topicdiv_info_t", "i32: splits runs; f32: ms_prep ms_pairs ms_merge")
 RelevanceInfo = _struct("RelevanceInfo", "tmvb_relevance_info_t", "f32: ms_score ms_select ms_terms")
+GroupTopicsInfo = _struct("GroupTopicsInfo", "tmvb_group_topics_info_t", "i64: nsel runs segments; i32: group_chunks lanes_per_entry; "
+                          "f32: ms_index ms_accum ms_select ms_shift")
 
 _TABLE = """
 int  tmvb_abi_version()
@@ -234,6 +236,8 @@ int  tmvb_ctm_svi_last_run_ms(h pf32*3 pi64)
 int  tmvb_topic_divergence(h i32 i64 i32 pf64 i32 pf64 f64 i32 pf64 TopicDivInfo)
 int  tmvb_term_relevance(h i32 i64 pf64*3 f64 i32 pi32 pf64 pi32 pf64*3 RelevanceInfo)
 int  tmvb_assignment(i32 i32 pf64 pi32 pf64)
+int  tmvb_group_topics(h i32 i64 i64 pf64 pf64 pi64 pi32*3 i32 f64 i32 i32 pi64 pi64 pf64 pi32 pf64*4 GroupTopicsInfo)
+int  tmvb_group_index(i64 i64 pi64 pi32 pi32 i32 pi64 pi64 pi32 pi32 pi64)
 """
 
 

@@ -23,7 +23,7 @@ LIB_PATH = os.path.join(_HERE, "libtmvb_hip.so")
 # experiments only (tools/build_variant.sh): TMVB_LIB_VARIANT=<name> loads libtmvb_hip_<name>.so, the same sources built with extra -D
 # flags, so that a compile-time variant can be timed against the shipped library inside ONE gpurun call (boxes differ by up to 8 %)
 _VARIANT = os.environ.get("TMVB_LIB_VARIANT", "")
-SOURCES = ["tmvb_core.hip", "tmvb_comm.hip", "tmvb_lda.hip", "tmvb_flda.hip", "tmvb_ctm.hip", "tmvb_ctpf.hip", "tmvb_ctpf_recs.hip", "tmvb_topics.hip", "tmvb_gencorp.hip", "tmvb_heldout.hip", "tmvb_coherence.hip", "tmvb_neighbors.hip", "tmvb_recranks.hip", "tmvb_rectopn.hip", "tmvb_lda_svi.hip", "tmvb_ctm_svi.hip", "tmvb_ctpf_foldin.hip", "tmvb_search.hip", "tmvb_token_topics.hip", "tmvb_kmeans.hip", "tmvb_docmap.hip", "tmvb_topic_compare.hip"]
+SOURCES = ["tmvb_core.hip", "tmvb_comm.hip", "tmvb_lda.hip", "tmvb_flda.hip", "tmvb_ctm.hip", "tmvb_ctpf.hip", "tmvb_ctpf_recs.hip", "tmvb_topics.hip", "tmvb_gencorp.hip", "tmvb_heldout.hip", "tmvb_coherence.hip", "tmvb_neighbors.hip", "tmvb_recranks.hip", "tmvb_rectopn.hip", "tmvb_lda_svi.hip", "tmvb_ctm_svi.hip", "tmvb_ctpf_foldin.hip", "tmvb_search.hip", "tmvb_token_topics.hip", "tmvb_kmeans.hip", "tmvb_docmap.hip", "tmvb_topic_compare.hip", "tmvb_group_topics.hip"]
 
 OK, EINVAL, ESHAPE, ECORPUS, ENOMEM, EHIP, ENONFINITE, ENODEVICE, ERCCL = range(9)
 

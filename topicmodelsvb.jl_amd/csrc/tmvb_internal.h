@@ -228,6 +228,8 @@ int tmvb_segmented_sort_pairs(tmvb_call& c, int K, int64_t V, const double* d_ke
 //                                   repulsive half is too small; tests/test_docmap_mutant_gpu.py
 //   TMVB_MUTANT_TD_DROP_TAIL        the pair kernel of the topic divergences (tmvb_topic_compare.hip) leaves out the last, partial run of terms (V not a multiple of
 //                                   TMVB_TD_RUN); tests/test_topic_compare_mutant_gpu.py
+//   TMVB_MUTANT_GT_SEG_CUT          the combine kernel of the grouped word-topic statistics (tmvb_group_topics.hip) leaves out the last segment of a run of more than one
+//                                   segment (more than TMVB_GT_SEG entries of one (group, term)); tests/test_group_topics_mutant_gpu.py
 #ifdef TMVB_MUTANT_FLDA_H_NO_GUARD
 #define TMVB_FLDA_H_GUARD(cond) true
 #else

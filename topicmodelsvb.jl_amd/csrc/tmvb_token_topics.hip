@@ -8,7 +8,7 @@
 // rows, the document's A row in LDS, L = 2^logL lanes per entry (lane r takes the 16-byte chunks r, r + L, ... of the row, at most four), one
 // workgroup per work item -- a run of entries of one selected document: 64 lanes up to TT_SHORT_TRIPS trips of a wave, 256 lanes beyond.
 // What is new: a lane keeps its <= 16 values in registers across the sum, because they are needed again after it.
-//   sum        per lane ((y0 + y1) + (y2 + y3)) per chunk, chunks in ascending order; the L partial sums meet in a fixed xor butterfly, so every
+//   sum        (tmvb_token_phi.h, shared with tmvb_group_topics.hip) per lane ((y0 + y1) + (y2 + y3)) per chunk, chunks in ascending order; the L partial sums meet in a fixed xor butterfly, so every
 //              lane of the entry holds the same bits of S; r = y / S is the IEEE fp32 division.
 //   top-t      t rounds: a lane offers the best of its values not yet taken as a packed key (r bits << 32 | ~k: larger key = larger r, on equal
 //              r the lower topic), the L keys meet in an xor butterfly of max, the lane that owned the winner marks it taken.  No LDS, no
@@ -20,6 +20,7 @@
 // stream order): the result does not depend on the cuts.
 #include "tmvb_internal.h"
 #include "tmvb_call.h"
+#include "tmvb_token_phi.h"
 
 #include <algorithm>
 #include <cstring>
@@ -58,12 +59,7 @@ static __global__ __launch_bounds__(WG) void token_topics_kernel(int K, int KP, 
     if (hard)
         for (int j = tid; j < G * K; j += WG) s_hard[j] = 0;
     __syncthreads();
-    unsigned vmask = 0;                                // bit 4 q + j: value j of the lane's q-th chunk is a topic
-#pragma unroll
-    for (int q = 0; q < 4; q++)
-#pragma unroll
-        for (int j = 0; j < 4; j++)
-            if (4 * (r + q * L) + j < K) vmask |= 1u << (4 * q + j);
+    const unsigned vmask = tt_value_mask(K, r, L);     // bit 4 q + j: value j of the lane's q-th chunk is a topic
     for (int64_t i0 = 0; i0 < n; i0 += G) {            // uniform trip count: every lane takes part in the butterflies
         const int64_t i = i0 + g;
         const bool live = i < n;
@@ -74,22 +70,14 @@ static __global__ __launch_bounds__(WG) void token_topics_kernel(int K, int KP, 
             c_n = counts[it.sel0 + i];
             row = reinterpret_cast<const float4*>(B + (int64_t)terms[it.sel0 + i] * KP);
         }
-        float S = 0.0f;
+        float4 av[4], bv[4];
 #pragma unroll
         for (int q = 0; q < 4; q++) {
             const int c = r + q * L;
-            float4 bv = make_float4(0.0f, 0.0f, 0.0f, 0.0f), av = bv;
-            if (live && c < nch) { bv = row[c]; av = s4[c]; }
-            y[4 * q + 0] = (vmask >> (4 * q + 0)) & 1u ? __fmaf_rn(av.x, bv.x, eps) : 0.0f;
-            y[4 * q + 1] = (vmask >> (4 * q + 1)) & 1u ? __fmaf_rn(av.y, bv.y, eps) : 0.0f;
-            y[4 * q + 2] = (vmask >> (4 * q + 2)) & 1u ? __fmaf_rn(av.z, bv.z, eps) : 0.0f;
-            y[4 * q + 3] = (vmask >> (4 * q + 3)) & 1u ? __fmaf_rn(av.w, bv.w, eps) : 0.0f;
-            S += (y[4 * q + 0] + y[4 * q + 1]) + (y[4 * q + 2] + y[4 * q + 3]);
+            bv[q] = make_float4(0.0f, 0.0f, 0.0f, 0.0f); av[q] = bv[q];
+            if (live && c < nch) { bv[q] = row[c]; av[q] = s4[c]; }
         }
-        for (int o = L >> 1; o; o >>= 1) S += __shfl_xor(S, o);
-        if (!live) S = 1.0f;
-#pragma unroll
-        for (int j = 0; j < 16; j++) y[j] = __fdiv_rn(y[j], S);        // y is r from here on
+        tt_responsibilities(y, av, bv, vmask, eps, L, live);           // tmvb_token_phi.h; y is r from here on
         if (DENSE) {
             if (live) {
                 float4* out = reinterpret_cast<float4*>(phi + (it.loc0 + i) * (int64_t)KP);
@@ -143,15 +131,6 @@ static __global__ __launch_bounds__(WG) void token_topics_kernel(int K, int KP, 
 
 // ------------------------------------------------------------------------------------------------------------------ host
 namespace {
-// lanes per entry: the smallest power of two that leaves a lane at most four 16-byte chunks of the row, at most a wave (tmvb_heldout.hip)
-int tt_log_lanes(int K)
-{
-    const int nch = (K + 3) / 4;
-    int logL = 0;
-    while (logL < 6 && (4 << logL) < nch) logL++;
-    return logL;
-}
-
 // dynamic LDS of a workgroup of wg lanes: the A row, and with hard the G = wg / L tables of K bins (G K <= 16 wg: K <= 16 L)
 size_t tt_lds_bytes(int wg, int K, int KP, int logL, bool hard)
 {

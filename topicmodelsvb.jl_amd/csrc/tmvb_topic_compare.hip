@@ -31,6 +31,7 @@
 #include <vector>
 
 #pragma clang fp contract(off)
+#include "tmvb_divergence_terms.h"
 
 #define TD_T 32                     // pairs per tile edge
 #define TD_CH 64                    // terms per staged chunk
@@ -63,30 +64,7 @@ static __global__ __launch_bounds__(256) void td_prep_kernel(int metric, int K, 
 }
 
 // ------------------------------------------------------------------------------------------------------------------ divergence: pairs
-// p, q: the prepared values (HELLINGER: roots; KL: smoothed)
-template <int METRIC>
-__device__ __forceinline__ double td_term(double p, double q)
-{
-    if (METRIC == TMVB_TD_JS) {
-        const double s = p + q;
-        const double x = p > 0.0 ? p * log((2.0 * p) / s) : 0.0;
-        const double y = q > 0.0 ? q * log((2.0 * q) / s) : 0.0;
-        return 0.5 * (x + y);
-    }
-    if (METRIC == TMVB_TD_HELLINGER) {
-        const double d = p - q;
-        return 0.5 * (d * d);
-    }
-    if (METRIC == TMVB_TD_TV) return 0.5 * fabs(p - q);
-    return p > 0.0 ? p * log(p / q) : 0.0;                           // KL: q = 0 < p gives p * log(inf) = +inf
-}
-
-template <int METRIC>
-__device__ __forceinline__ double td_finish(double s)
-{
-    return (METRIC == TMVB_TD_JS || METRIC == TMVB_TD_KL) ? (s > 0.0 ? s : 0.0) : s;      // max(0, s); HELLINGER's root is the host's
-}
-
+// the addend td_term<METRIC>(p, q) and the clamp td_finish<METRIC>(s): tmvb_divergence_terms.h (shared with tmvb_group_topics.hip)
 // A: [>= TD_T gridDim.y][vp], B: [>= TD_T gridDim.x][vp].  nruns: runs the kernel walks; rps: runs per group (blockIdx.z).  split == 0: out = D[KA][KB];
 // else out = part[run][KA][KB].
 template <int METRIC>

@@ -1686,3 +1686,62 @@ function term_relevance(beta::Matrix{Float64}, pw::Vector{Float64}, pi::Vector{F
 	return (idx=permutedims(Int.(idx) .+ 1), score=permutedims(score), count=Int.(count), distinctiveness=distinct, saliency=saliency,
 			ms=(score=info.ms_score, select=info.ms_select, terms=info.ms_terms))
 end
+
+# ---- topics by group and over time (include/tmvb.h: tmvb_group_topics, tmvb_group_index) ---------------------------------------------------
+# For every group g of documents S_g[k, w] = the sum over the entries (w, c) of the documents of g of c r_k(d, w), r the responsibilities of
+# tmvb_token_topics; from it the topic masses, the top words of every topic inside the group, its Jensen-Shannon shift from the pooled topic and
+# its drift from the previous group.  include/tmvb.h is the specification.
+
+"tmvb_group_topics_info_t (include/tmvb.h), field for field."
+mutable struct TmvbGroupTopicsInfo
+	nsel::Int64; runs::Int64; segments::Int64
+	group_chunks::Int32; lanes_per_entry::Int32
+	ms_index::Float32; ms_accum::Float32; ms_select::Float32; ms_shift::Float32
+	TmvbGroupTopicsInfo() = new(0, 0, 0, 0, 0, 0f0, 0f0, 0f0, 0f0)
+end
+
+"""
+Topics by group: `group[d]` in 1:G names the group of document d of the model's corpus, 0 leaves the document out.  Returns docs[G], tokens[G],
+mass[K, G], prevalence[K, G], idx[topn, K, G] (1-based term ids, 0 for a group without entries), prob[topn, K, G], shift[K, G] and drift[K, G].
+"""
+function group_topics(model::Union{hipLDA, hipCTM, hipCTPF}, group::Vector{<:Integer}, G::Integer; topn::Integer=10, device::Integer=0)
+	length(group) == model.M			|| throw(ArgumentError("group must hold one label per document."))
+	all(g -> 0 <= g <= G, group)		|| throw(ArgumentError("group labels must lie in 0:G."))
+	update_host!(model)
+	A, B = token_factors(model)
+	K, M = size(A); V = size(B, 2)
+	doc_ptr, terms, counts = corp_csr(model.corp)
+	zgroup = Int32.(group .- 1)
+	docs = zeros(Int64, G); tokens = zeros(Int64, G)
+	mass = zeros(Float64, K, G)										# column-major (k, g) = C's [g][k]
+	idx = fill(Int32(-1), topn, K, G); prob = zeros(Float64, topn, K, G)
+	shift = zeros(Float64, K, G); drift = zeros(Float64, K, G)
+	info = TmvbGroupTopicsInfo()
+	ctx = tmvb_context(device)
+	GC.@preserve info A B doc_ptr terms counts zgroup docs tokens mass idx prob shift drift begin
+		rc = ccall((:tmvb_group_topics, LIBTMVB), Cint,
+			(Ptr{Cvoid}, Int32, Int64, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Int32, Float64, Int32, Int32,
+			 Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Cvoid}),
+			ctx, K, V, M, A, B, doc_ptr, terms, counts, zgroup, G, EPSILON, topn, 0,
+			docs, tokens, mass, idx, prob, shift, drift, Ptr{Float64}(C_NULL), pointer_from_objref(info))
+		tmvb_destroy_context(ctx)
+		tmvb_check(rc)
+	end
+	return (docs=docs, tokens=tokens, mass=mass, prevalence=mass ./ sum(mass, dims=1), idx=Int.(idx) .+ 1, prob=prob, shift=shift, drift=drift,
+			info=(nsel=Int(info.nsel), runs=Int(info.runs), segments=Int(info.segments), group_chunks=Int(info.group_chunks),
+				  lanes_per_entry=Int(info.lanes_per_entry), ms_index=info.ms_index, ms_accum=info.ms_accum, ms_select=info.ms_select, ms_shift=info.ms_shift))
+end
+
+"The (group, term) index tmvb_group_topics walks (host only): (run_ptr, run_group, run_term, entry), 0-based as the library returns them."
+function group_index(doc_ptr::Vector{Int64}, terms::Vector{Int32}, group::Vector{Int32}, G::Integer, V::Integer)
+	M = length(doc_ptr) - 1
+	nsel = sum(Int[doc_ptr[d+1] - doc_ptr[d] for d in 1:M if group[d] >= 0])
+	n_runs = Ref{Int64}(0)
+	run_ptr = zeros(Int64, nsel + 1); run_group = zeros(Int32, max(nsel, 1)); run_term = zeros(Int32, max(nsel, 1)); entry = zeros(Int64, max(nsel, 1))
+	rc = ccall((:tmvb_group_index, LIBTMVB), Cint,
+		(Int64, Int64, Ptr{Int64}, Ptr{Int32}, Ptr{Int32}, Int32, Ref{Int64}, Ptr{Int64}, Ptr{Int32}, Ptr{Int32}, Ptr{Int64}),
+		M, V, doc_ptr, terms, group, G, n_runs, run_ptr, run_group, run_term, entry)
+	tmvb_check(rc)
+	r = n_runs[]
+	return (run_ptr=run_ptr[1:r+1], run_group=run_group[1:r], run_term=run_term[1:r], entry=entry[1:nsel])
+end
