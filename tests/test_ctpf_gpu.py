@@ -108,16 +108,33 @@ def test_device_elbo_matches_oracle(tmvb, oracle, case):
         within("ctpf.elbo_rel_step", abs(e_g - e_o) / abs(e_o), (it, e_g, e_o))
 
 
-@pytest.mark.parametrize("grid", ["0", "1"])
-def test_long_documents_and_the_lane_per_token_path(tmvb, oracle, monkeypatch, grid):
+LONG_SHAPES = [(30, 3), (64, 1), (90, 20), (128, 32), (129, 5), (192, 30), (100, 40), (128, 64), (60, 100), (250, 10), (200, 300), (20, 500),
+               (300, 200), (380, 380), (600, 50), (10, 0), (5, 600)]
+LDS_PAIR = [(600, 50), (5, 600)]
+# subsets of the classes: the plan the constructor builds then holds a launch kind the whole corpus never reaches
+LONG_SUBSETS = {
+    "all": LONG_SHAPES,
+    "no33": [s for s in LONG_SHAPES if s not in ((300, 200), (380, 380))],                          # only the (2, 4) four-wave class: ctpf_estep_grid_long_kernel<LPR, 2, 4, 4>
+    "no24": [s for s in LONG_SHAPES if s not in ((60, 100), (250, 10), (200, 300), (20, 500))],     # only (3, 3): ctpf_estep_grid_long_kernel<LPR, 3, 3, 4>
+    "narrow": [(30, 3), (64, 1), (90, 20), (10, 0)] + LDS_PAIR,                                     # no wide launch (nothing on aux[0]), no four-wave launch
+    "wide": [(128, 32), (129, 5), (192, 30), (100, 40), (128, 64)] + LDS_PAIR,                      # no narrow launch; grid 0: two-tile register documents only
+    "short": [(30, 3), (64, 1), (10, 0)] + LDS_PAIR,                                                # grid 0: one-tile register documents only
+}
+
+
+@pytest.mark.parametrize("grid,subset", [pytest.param("0", "all", id="0"), pytest.param("1", "all", id="1")] +
+                         [pytest.param("1", s, id="1-" + s) for s in ("no33", "no24", "narrow", "wide")] +
+                         [pytest.param("0", s, id="0-" + s) for s in ("wide", "short")])
+def test_long_documents_and_the_lane_per_token_path(tmvb, oracle, monkeypatch, grid, subset):
     """The grid-tile kernel's classes on one corpus -- documents of up to 192 terms with few readers, 33 .. 64 readers, and the
     four-wave classes (up to 256 terms x 512 readers, 384 x 384), plus one document beyond them (LDS kernel) -- and, with
-    TMVB_CTPF_GRID=0, the lane = token register-tile path of rounds 1-2 on the same corpus; pinned sweeps, against the oracle."""
+    TMVB_CTPF_GRID=0, the lane = token register-tile path of rounds 1-2 on the same corpus; pinned sweeps, against the oracle.
+    The subsets leave classes out, so that the launches the whole corpus merges away (one four-wave class alone, one register-tile
+    tile count alone) and plans without a narrow or a wide launch run too."""
     monkeypatch.setenv("TMVB_CTPF_GRID", grid)
     rng = np.random.default_rng(11)
     V, U, K = 1500, 700, 50
-    shapes = [(30, 3), (64, 1), (90, 20), (128, 32), (129, 5), (192, 30), (100, 40), (128, 64), (60, 100), (250, 10), (200, 300), (20, 500),
-              (300, 200), (380, 380), (600, 50), (10, 0), (5, 600)]
+    shapes = LONG_SUBSETS[subset]
     tl, rl = [], []
     for n, r in shapes:
         tl.append((np.sort(rng.choice(V, size=n, replace=False)), rng.integers(1, 4, size=n)))

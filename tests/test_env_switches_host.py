@@ -18,7 +18,8 @@ INTEGRATION = os.path.join(ROOT, "INTEGRATION.md")
 REMOVED = {
     "TMVB_DEBUG_FLAGS", "TMVB_TS_CPL", "TMVB_CTPF_GRID_ANY", "TMVB_CTPF_SPLIT", "TMVB_CTPF_REG_ANY", "TMVB_CTPF_LONG_PRIO", "TMVB_CTPF_FUSE_STATS",
     "TMVB_CTPF_FUSED_MSTEP", "TMVB_CTM_FOLD_REDUCE", "TMVB_CTM_FORCE_GENERIC", "TMVB_CTM_MAX_TILE_KB", "TMVB_LDA_ELBO_LEGACY", "TMVB_LDA_ELBO_NO_PW",
-    "TMVB_LDA_ELBO_EARLY", "TMVB_LDA_NO_LONG", "TMVB_LDA_PIECE_FRACS",
+    "TMVB_LDA_ELBO_EARLY", "TMVB_LDA_NO_LONG", "TMVB_LDA_PIECE_FRACS", "TMVB_LDA_CHAIN_AUX", "TMVB_LDA_SPLIT_OUT", "TMVB_LDA_ELBO_STREAM",
+    "TMVB_LDA_SIDE_STREAM", "TMVB_CTPF_LONG_MERGE",
 }
 NAME = re.compile(r"TMVB_[A-Z0-9_]+")
 READ = re.compile(r"\btmvb_env_(?:on|int|str)\(\s*\"(TMVB_[A-Z0-9_]+)\"")

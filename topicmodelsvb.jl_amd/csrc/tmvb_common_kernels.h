@@ -355,6 +355,19 @@ static int dispatch_nslot(int nslot, F&& f)
     }
 }
 
+// f(std::integral_constant<int, LPR>()) for LPR = KP / 4 = 1, 3, ..., LPR_MAX: the lanes-per-row count of the register- and grid-tile kernels as a
+// compile-time constant (LDA instantiates up to 25, CTPF up to 15).  Every caller sits behind its model's reg_path test: the refusal is unreachable.
+template <int LPR_MAX, int LPR = 1, typename F>
+static int tmvb_dispatch_lpr(int lpr, F&& f)
+{
+    if constexpr (LPR > LPR_MAX) {
+        tmvb_set_error("no register- or grid-tile kernel is instantiated for KP=%d", 4 * lpr);
+        return TMVB_EINVAL;
+    } else {
+        return lpr == LPR ? f(std::integral_constant<int, LPR>()) : tmvb_dispatch_lpr<LPR_MAX, LPR + 2>(lpr, std::forward<F>(f));
+    }
+}
+
 static size_t tmvb_tile_bytes(int rows, int KP) { return ((size_t)rows * KP + KP + 3 * (size_t)rows) * sizeof(float); }
 
 
@@ -590,13 +603,13 @@ static inline int64_t tmvb_build_lds_buckets(const std::vector<int64_t>& len, co
     const int tmax = tiles.back();
     int64_t cnt = 0;
     while (pos + cnt < n_lds && len[order[pos + cnt]] > tmax) ++cnt;   // stream chunks through the largest tile
-    if (cnt) buckets.push_back({pos, cnt, tmax, 0});
+    if (cnt) buckets.push_back({pos, cnt, tmax});
     pos += cnt;
     for (int b = (int)tiles.size() - 1; b >= 0 && pos < n_lds; --b) {
         const int64_t lo = (b > 0) ? tiles[b - 1] : -1;
         cnt = 0;
         while (pos + cnt < n_lds && len[order[pos + cnt]] > lo) ++cnt;
-        if (cnt) buckets.push_back({pos, cnt, tiles[b], 0});
+        if (cnt) buckets.push_back({pos, cnt, tiles[b]});
         pos += cnt;
     }
     // merge small buckets into their larger neighbour (a launch needs enough waves to matter)

@@ -17,8 +17,14 @@
 // its reader rows; 2 fp32 digammas per topic per sweep instead of K (N_d + 2 R_d).
 // The scatters update_alef!(d) / update_he!(d) are gather-side statistics passes over the term and
 // the reader inverted indices (tmvb_termstats.h); HBM-bound like LDA.
+//
+// Host half (from `struct tmvb_ctpf` down), the E-step's launch layer -- what decides -> what it serves
+//   ctpf_build_plan (tmvb_estep_plan.h), called by tmvb_ctpf_create: document order + one ctpf_launch per kernel launch (kind, documents, stream role)
+//   tmvb_ctpf_estep: forks aux[0] / aux[1], issues the plan record by record through ctpf_launch_docs, joins, then the ELBO parts and the two statistics passes
+//   ctpf_launch_docs: a record's kind -> ctpf_launch_grid<LPR> / ctpf_launch_reg<LPR> (tmvb_dispatch_lpr<15>) or ctpf_estep_kernel<LPR_T, NS> (LDS tile)
 #define TMVB_TS_LOGZ 1            // the log-normaliser forms of the statistics pass (decomposed update_elbo!, ctpf_elbo_doc_parts_kernel)
 #include "tmvb_common_kernels.h"
+#include "tmvb_estep_plan.h"
 
 // xi's rate is `log vav` (src/CTPF.jl:336).  -DTMVB_MUTANT_CTPF_LOG_BET (tests/test_mutants_gpu.py, never in a shipped build) stores log bet in its place --
 // the reference's own OpenCL bug (src/gpuCTPF.jl:624) -- to prove that the parity tests notice.
@@ -426,11 +432,12 @@ __global__ __launch_bounds__(64) void ctpf_estep_reg_any_kernel(CtpfParams p, in
 }
 
 template <int LPR>
-static void ctpf_launch_reg(int tiles, dim3 grid, hipStream_t st, const CtpfParams& p, int64_t first, const int* tol)
+static void ctpf_launch_reg(const ctpf_launch& b, hipStream_t st, const CtpfParams& p, const int* tol)
 {
-    if (tiles == 99) hipLaunchKernelGGL((ctpf_estep_reg_any_kernel<LPR>), grid, dim3(64), 0, st, p, first, tol);
-    else if (tiles <= 1) hipLaunchKernelGGL((ctpf_estep_reg_kernel<LPR, 1>), grid, dim3(64), 0, st, p, first, tol);
-    else hipLaunchKernelGGL((ctpf_estep_reg_kernel<LPR, 2>), grid, dim3(64), 0, st, p, first, tol);
+    const dim3 grid((unsigned)b.count);
+    if (b.kind == ctpf_kind::REG_ANY) hipLaunchKernelGGL((ctpf_estep_reg_any_kernel<LPR>), grid, dim3(64), 0, st, p, b.first, tol);
+    else if (b.n <= 1) hipLaunchKernelGGL((ctpf_estep_reg_kernel<LPR, 1>), grid, dim3(64), 0, st, p, b.first, tol);
+    else hipLaunchKernelGGL((ctpf_estep_reg_kernel<LPR, 2>), grid, dim3(64), 0, st, p, b.first, tol);
 }
 
 // ------------------------------------------------------------------------------ grid-tile E-step (tmvb_gridtile.h)
@@ -557,19 +564,7 @@ __device__ __forceinline__ void ctpf_estep_grid_body(const CtpfParams& p, const 
     }
 }
 
-// length classes of the grid-tile kernels (term pairs, reader pairs per lane): single-wave (2, 1) (3, 1) (4, 1) (6, 1) = documents of <= 32 readers
-// by their terms (<= 64 / 96 / 128 / 192), and (4, 2) = <= 128 terms with <= 64 readers;
-// multi-wave classes, four waves per document: (2 term pairs, 4 reader pairs) = <= 256 terms, <= 512 readers, and (3, 3) = <= 384, <= 384
-static inline bool ctpf_grid_class(int64_t n, int64_t r, int* npt, int* npr, int* waves)
-{
-    *waves = 1;
-    if (r <= 32 && n <= 192) { *npr = 1; *npt = n <= 64 ? 2 : n <= 96 ? 3 : n <= 128 ? 4 : 6; return true; }
-    if (r <= 64 && n <= 128) { *npt = 4; *npr = 2; return true; }
-    if (n <= 256 && r <= 512) { *npt = 2; *npr = 4; *waves = 4; return true; }
-    if (n <= 384 && r <= 384) { *npt = 3; *npr = 3; *waves = 4; return true; }
-    return false;
-}
-
+// (the length classes of these kernels: ctpf_grid_class, tmvb_estep_plan.h)
 #define CTPF_GRID_LDS(BWV)                                                                                              \
     __shared__ float xch[2][4][128];                    /* multi-wave documents: per-wave partial (G | H), by sweep parity */ \
     __shared__ __attribute__((aligned(16))) float ef_all[BWV][2][4][16]
@@ -620,13 +615,14 @@ __global__ __launch_bounds__(64) void ctpf_estep_grid_wide_kernel(CtpfParams p, 
     else ctpf_estep_grid_body<LPR, 4, 1>(p, d, topic_of_lane, ef_all, xch);
 }
 template <int LPR>
-static void ctpf_launch_grid(const tmvb_bucket& b, dim3 grid, hipStream_t st, const CtpfParams& p, int64_t first, const int* tol)
+static void ctpf_launch_grid(const ctpf_launch& b, hipStream_t st, const CtpfParams& p, const int* tol)
 {
-    if (b.waves == 4 && b.grid_np == 96) { hipLaunchKernelGGL((ctpf_estep_grid_long2_kernel<LPR>), grid, dim3(256), 0, st, p, first, tol, (int)b.grid_np2); return; }
-    if (b.waves == 4 && b.grid_np == 2) { hipLaunchKernelGGL((ctpf_estep_grid_long_kernel<LPR, 2, 4, 4>), grid, dim3(256), 0, st, p, first, tol); return; }
-    if (b.waves == 4) { hipLaunchKernelGGL((ctpf_estep_grid_long_kernel<LPR, 3, 3, 4>), grid, dim3(256), 0, st, p, first, tol); return; }
-    if (b.grid_np == 98) { hipLaunchKernelGGL((ctpf_estep_grid_wide_kernel<LPR>), grid, dim3(64), 0, st, p, first, tol); return; }
-    if (b.grid_np == 97) { hipLaunchKernelGGL((ctpf_estep_grid_narrow_kernel<LPR>), grid, dim3(64), 0, st, p, first, tol); return; }
+    const dim3 grid((unsigned)b.count), block(64 * (unsigned)b.waves);
+    if (b.kind == ctpf_kind::GRID_LONG2) hipLaunchKernelGGL((ctpf_estep_grid_long2_kernel<LPR>), grid, block, 0, st, p, b.first, tol, (int)b.count_a);
+    else if (b.kind == ctpf_kind::GRID_LONG && b.npt == 2) hipLaunchKernelGGL((ctpf_estep_grid_long_kernel<LPR, 2, 4, 4>), grid, block, 0, st, p, b.first, tol);
+    else if (b.kind == ctpf_kind::GRID_LONG) hipLaunchKernelGGL((ctpf_estep_grid_long_kernel<LPR, 3, 3, 4>), grid, block, 0, st, p, b.first, tol);
+    else if (b.kind == ctpf_kind::GRID_WIDE) hipLaunchKernelGGL((ctpf_estep_grid_wide_kernel<LPR>), grid, block, 0, st, p, b.first, tol);
+    else hipLaunchKernelGGL((ctpf_estep_grid_narrow_kernel<LPR>), grid, block, 0, st, p, b.first, tol);
 }
 // shape update + table refresh:  X[id][i] = prior + stats[id][i];  T[id][i] = exp(psi(X));  stats <- 0
 // (update_alef!/update_he! src/CTPF.jl:251-255, :266-270: X <- X_temp, X_temp <- prior)
@@ -1361,7 +1357,8 @@ struct tmvb_ctpf : tmvb_model_base {     // d_stats: alef_stats (K*V) | he_stats
     int* d_grid_topic_of_lane = nullptr;   // grid-tile kernel (tmvb_gridtile.h): the same for its 16-lane reduce-scatter
     bool grid_path = false;             // KP <= 60: documents of <= 512 terms and <= 512 readers use the grid-tile kernels (ctpf_estep_grid_*_kernel)
     bool reg_path = false;              // KP = 4 * odd <= 60: short documents (<= 128 terms, <= 64 readers) use ctpf_estep_reg_kernel
-    std::vector<tmvb_bucket> buckets;
+    std::vector<ctpf_launch> plan;      // the E-step's launches in issue order (ctpf_build_plan)
+    bool aux0_used = false;             // the E-step joins aux[0]: a launch of the plan runs there, or there is no register path
     static constexpr int NAUX = 4;
     hipStream_t aux[NAUX] = {nullptr, nullptr, nullptr, nullptr};
     hipEvent_t ev_fork = nullptr, ev_join[NAUX] = {nullptr, nullptr, nullptr, nullptr};
@@ -1434,8 +1431,6 @@ extern "C" int tmvb_ctpf_create(tmvb_ctx* ctx, tmvb_corpus* corp, int32_t K, tmv
     TMVB_HIP(hipMemset(h->d_mstep_counter, 0, sizeof(unsigned int)));
     TMVB_HIP(hipMemset(h->d_E1, 0, ((size_t)h->estride * h->M + 4) * sizeof(float)));      // the pad columns stay zero for good
     TMVB_HIP(hipMemset(h->d_E2, 0, ((size_t)h->estride * h->M + 4) * sizeof(float)));
-    // processing order: first the documents of the LDS-tile kernel by rows (terms + readers), longest first, in LDS
-    // buckets on the combined row count; then the register-tile documents (<= 128 terms and <= 64 readers) by tiles
     h->reg_path = (h->KP / 4) <= 15 && ((h->KP / 4) & 1);
     if (h->reg_path) {
         std::vector<int> tol, lot;
@@ -1448,58 +1443,14 @@ extern "C" int tmvb_ctpf_create(tmvb_ctx* ctx, tmvb_corpus* corp, int32_t K, tmv
                    tmvb_env_on("TMVB_CTPF_GRID", true);
     if (h->grid_path) {
         std::vector<int> tol;
-        switch (h->KP / 4) {
-#define CTPF_GRID_MAP_CASE(LPRV) case LPRV: tmvb_grid_lane_map_fill<LPRV, 0>(tol); break;
-            CTPF_GRID_MAP_CASE(1) CTPF_GRID_MAP_CASE(3) CTPF_GRID_MAP_CASE(5) CTPF_GRID_MAP_CASE(7) CTPF_GRID_MAP_CASE(9) CTPF_GRID_MAP_CASE(11)
-            CTPF_GRID_MAP_CASE(13) CTPF_GRID_MAP_CASE(15)
-#undef CTPF_GRID_MAP_CASE
-            default: h->grid_path = false;
-        }
-        if (h->grid_path) {
-            if ((rc = h->mem.alloc(&h->d_grid_topic_of_lane, tol.size()))) return rc;
-            TMVB_HIP(hipMemcpy(h->d_grid_topic_of_lane, tol.data(), tol.size() * sizeof(int), hipMemcpyHostToDevice));
-        }
+        if ((rc = tmvb_dispatch_lpr<15>(h->KP / 4, [&](auto lpr) -> int { tmvb_grid_lane_map_fill<decltype(lpr)::value, 0>(tol); return TMVB_OK; }))) return rc;
+        if ((rc = h->mem.alloc(&h->d_grid_topic_of_lane, tol.size()))) return rc;
+        TMVB_HIP(hipMemcpy(h->d_grid_topic_of_lane, tol.data(), tol.size() * sizeof(int), hipMemcpyHostToDevice));
     }
-    std::vector<int64_t> len((size_t)h->M);
-    std::vector<int32_t> order, reg2, reg1;
-    // grid-tile classes (ctpf_grid_class): key = waves * 10000 + npt * 100 + npr, longest class first
-    std::vector<std::pair<int, int32_t>> gdocs;
-    for (int64_t d = 0; d < h->M; ++d) {
-        len[d] = corp->h_doc_len[d] + corp->h_rdr_len[d];
-        int npt = 0, npr = 0, wv = 1;
-        if (h->grid_path && ctpf_grid_class(corp->h_doc_len[d], corp->h_rdr_len[d], &npt, &npr, &wv)) {
-            gdocs.emplace_back(wv * 10000 + npt * 100 + npr, (int32_t)d);
-            continue;
-        }
-        const bool reg = h->reg_path && !h->grid_path && corp->h_doc_len[d] <= 128 && corp->h_rdr_len[d] <= 64;
-        if (!reg) order.push_back((int32_t)d);
-        else if (corp->h_doc_len[d] > 64) reg2.push_back((int32_t)d);
-        else reg1.push_back((int32_t)d);
-    }
-    std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) { return len[x] > len[y]; });
-    const int64_t n_lds = (int64_t)order.size();
-    tmvb_build_lds_buckets(len, order, n_lds, h->KP, -1, 3, h->buckets, h->reg_path ? TMVB_BIG_TILE_BYTES : TMVB_MAX_TILE_BYTES);
-    auto by_terms = [&](int32_t x, int32_t y) { return corp->h_doc_len[x] > corp->h_doc_len[y]; };
-    std::stable_sort(reg2.begin(), reg2.end(), by_terms);
-    std::stable_sort(reg1.begin(), reg1.end(), by_terms);
-    if (!reg2.empty()) h->buckets.push_back({(int64_t)order.size(), (int64_t)reg2.size(), 0, 2});
-    order.insert(order.end(), reg2.begin(), reg2.end());
-    if (!reg1.empty()) h->buckets.push_back({(int64_t)order.size(), (int64_t)reg1.size(), 0, 1});
-    order.insert(order.end(), reg1.begin(), reg1.end());
-    if (!gdocs.empty()) {
-        std::stable_sort(gdocs.begin(), gdocs.end(), [&](const std::pair<int, int32_t>& x, const std::pair<int, int32_t>& y) {
-            return x.first != y.first ? x.first > y.first : len[x.second] > len[y.second]; });
-        size_t q = 0;
-        while (q < gdocs.size()) {
-            size_t e = q;
-            while (e < gdocs.size() && gdocs[e].first == gdocs[q].first) ++e;
-            tmvb_bucket b{(int64_t)order.size(), (int64_t)(e - q), 0, 1};
-            b.waves = gdocs[q].first / 10000; b.grid_np = (gdocs[q].first / 100) % 100; b.grid_np2 = gdocs[q].first % 100;
-            h->buckets.push_back(b);
-            for (size_t u = q; u < e; ++u) order.push_back(gdocs[u].second);
-            q = e;
-        }
-    }
+    std::vector<int32_t> order;
+    ctpf_build_plan(corp->h_doc_len, corp->h_rdr_len, h->KP, h->reg_path, h->grid_path, order, h->plan);
+    h->aux0_used = !h->reg_path;         // (no register path: aux[0] is one of the alternating pair and is joined whatever the plan holds)
+    for (const ctpf_launch& b : h->plan) h->aux0_used = h->aux0_used || b.role == tmvb_role::BESIDE;
     if (h->M) TMVB_HIP(hipMemcpyAsync(h->d_doc_order, order.data(), (size_t)h->M * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
     TMVB_HIP(hipMemsetAsync(h->d_stats, 0, (size_t)h->stats_len() * sizeof(float), ctx->stream));
     TMVB_HIP(hipMemsetAsync(h->d_sweeps, 0, std::max<size_t>((size_t)h->M, 1), ctx->stream));
@@ -1672,6 +1623,28 @@ static int ctpf_elbo_consts(tmvb_ctpf* h)
     return TMVB_OK;
 }
 
+// one record of the plan on its stream
+static int ctpf_launch_docs(tmvb_ctpf* h, const CtpfParams& p, const ctpf_launch& b, hipStream_t st)
+{
+    switch (b.kind) {
+        case ctpf_kind::GRID_NARROW: case ctpf_kind::GRID_WIDE: case ctpf_kind::GRID_LONG: case ctpf_kind::GRID_LONG2:
+            return tmvb_dispatch_lpr<15>(p.LPR, [&](auto lpr) -> int { ctpf_launch_grid<decltype(lpr)::value>(b, st, p, h->d_grid_topic_of_lane); return TMVB_OK; });
+        case ctpf_kind::REG: case ctpf_kind::REG_ANY:
+            return tmvb_dispatch_lpr<15>(p.LPR, [&](auto lpr) -> int { ctpf_launch_reg<decltype(lpr)::value>(b, st, p, h->d_topic_of_lane); return TMVB_OK; });
+        case ctpf_kind::LDS_TILE: break;
+    }
+    const size_t lds = ctpf_tile_bytes(b.tile_rows, h->KP);
+    auto launch = [&](auto kern) -> int {
+        if (lds > TMVB_MAX_TILE_BYTES)                // long documents: the whole row set resident in up to 156 KiB of LDS
+            TMVB_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(kern, dim3((unsigned)b.count), dim3(64), lds, st, p, b.first, b.tile_rows);
+        return TMVB_OK;
+    };
+    return (h->nslot > 4) ? launch(ctpf_estep_kernel<0, 8>) : (h->nslot > 2) ? launch(ctpf_estep_kernel<0, 4>)
+           : (h->nslot == 2) ? ((p.LPR == 25) ? launch(ctpf_estep_kernel<25, 2>) : launch(ctpf_estep_kernel<0, 2>))
+           : (p.LPR == 13) ? launch(ctpf_estep_kernel<13, 1>) : (p.LPR == 3) ? launch(ctpf_estep_kernel<3, 1>) : launch(ctpf_estep_kernel<0, 1>);
+}
+
 extern "C" int tmvb_ctpf_estep(tmvb_ctpf* h, int32_t viter, double vtol)
 {
     TMVB_REQUIRE(h != nullptr, TMVB_EINVAL, "tmvb_ctpf_estep: handle is NULL");
@@ -1716,85 +1689,21 @@ extern "C" int tmvb_ctpf_estep(tmvb_ctpf* h, int32_t viter, double vtol)
         p.shift = h->d_shift;
     }
     if (h->timing) TMVB_HIP(hipEventRecord(h->ev0, ctx->stream));
-    // stream plan as in tmvb_lda_estep for one statistics pass: the register-tile buckets run back to back on the
-    // context's stream (the critical chain document kernels -> statistics -> M-step pays kernel boundaries, not ~20 us
-    // cross-stream hops: the whole iteration is 0.3 ms), the LDS-tile buckets (long documents) on aux[1]
-    const int nb = (int)h->buckets.size();
-    hipStream_t chain_st = ctx->stream;                          // only used when h->reg_path
+    // stream plan as in tmvb_lda_estep for one statistics pass: the register- and grid-tile launches of the single-wave documents run
+    // back to back on the context's stream (the critical chain document kernels -> statistics -> M-step pays kernel boundaries, not ~20 us
+    // cross-stream hops: the whole iteration is 0.3 ms), the long documents (LDS tile, four-wave classes) on aux[1], the wide single-wave
+    // classes on aux[0]: the roles of tmvb_estep_plan.h.
+    // (Measured and dropped: everything in one launch of four-wave workgroups, long documents first and four single-wave
+    //  documents per later workgroup: 0.256 ms per iteration against 0.193 ms.)
     TMVB_HIP(hipEventRecord(h->ev_fork, ctx->stream));
     for (int a = 0; a < 2; ++a) TMVB_HIP(hipStreamWaitEvent(h->aux[a], h->ev_fork, 0));
-    bool aux0_used = !h->reg_path;
-    for (int bi = 0; bi < nb; ++bi) {
-        const tmvb_bucket& b = h->buckets[bi];
-        dim3 grid((unsigned)b.count), block(64);
-        if (b.grid_np > 0) {
-            // the multi-wave (long) documents on aux[1] next to the chain, the single-wave classes as two mixed-class launches (below).
-            // (Measured and dropped: everything in one launch of four-wave workgroups, long documents first and four single-wave
-            //  documents per later workgroup: 0.256 ms per iteration against 0.193 ms.)
-            hipStream_t st = b.waves > 1 ? h->aux[1] : chain_st;
-            tmvb_bucket bb = b;
-            // the (3, 3) four-wave bucket and the (2, 4) one behind it as one launch (ctpf_estep_grid_long2_kernel); TMVB_CTPF_LONG_MERGE=0: two
-            if (b.waves == 4 && b.grid_np == 3 && b.grid_np2 == 3 && bi + 1 < nb && h->buckets[bi + 1].waves == 4 && h->buckets[bi + 1].grid_np == 2 &&
-                h->buckets[bi + 1].grid_np2 == 4 && h->buckets[bi + 1].first == b.first + b.count && b.count < (1 << 30) && tmvb_env_on("TMVB_CTPF_LONG_MERGE", true)) {
-                bb.grid_np = 96; bb.grid_np2 = (int)b.count; bb.count = b.count + h->buckets[bi + 1].count;
-                grid = dim3((unsigned)bb.count);
-                ++bi;
-            }
-            // (round 4) the single-wave classes as TWO launches by register need: every single-wave bucket leaves here as class 97
-            // (ctpf_estep_grid_narrow_kernel, on the chain) or 98 (ctpf_estep_grid_wide_kernel, on aux[0]) with its neighbours of the same kind
-            if (b.waves == 1) {
-                const bool wide = b.grid_np >= 4;
-                int64_t cnt = b.count;
-                while (bi + 1 < nb && h->buckets[bi + 1].grid_np > 0 && h->buckets[bi + 1].waves == 1 &&
-                       h->buckets[bi + 1].first == b.first + cnt && (h->buckets[bi + 1].grid_np >= 4) == wide) { cnt += h->buckets[bi + 1].count; ++bi; }
-                bb.count = cnt; bb.grid_np = wide ? 98 : 97; grid = dim3((unsigned)cnt);
-                if (wide) { st = h->aux[0]; aux0_used = true; }
-            }
-            switch (p.LPR) {
-#define CTPF_GRID_CASE(LPRV) case LPRV: ctpf_launch_grid<LPRV>(bb, grid, st, p, b.first, h->d_grid_topic_of_lane); break;
-                CTPF_GRID_CASE(1) CTPF_GRID_CASE(3) CTPF_GRID_CASE(5) CTPF_GRID_CASE(7) CTPF_GRID_CASE(9) CTPF_GRID_CASE(11) CTPF_GRID_CASE(13)
-                CTPF_GRID_CASE(15)
-#undef CTPF_GRID_CASE
-                default: TMVB_REQUIRE(false, TMVB_EINVAL, "tmvb_ctpf_estep: no grid-tile kernel for KP=%d", h->KP);
-            }
-            TMVB_HIP(hipGetLastError());
-            continue;
-        }
-        if (b.reg_tiles > 0) {
-            hipStream_t st = chain_st;
-            // two adjacent register-tile buckets (T = 2 then T = 1 in processing order): one mixed-tile launch
-            int tiles = b.reg_tiles;
-            if (bi + 1 < nb && h->buckets[bi + 1].reg_tiles > 0 && h->buckets[bi + 1].first == b.first + b.count) {
-                grid = dim3((unsigned)(b.count + h->buckets[bi + 1].count));
-                tiles = 99;
-                ++bi;
-            }
-            switch (p.LPR) {
-#define CTPF_REG_CASE(LPRV) case LPRV: ctpf_launch_reg<LPRV>(tiles, grid, st, p, b.first, h->d_topic_of_lane); break;
-                CTPF_REG_CASE(1) CTPF_REG_CASE(3) CTPF_REG_CASE(5) CTPF_REG_CASE(7) CTPF_REG_CASE(9) CTPF_REG_CASE(11) CTPF_REG_CASE(13)
-                CTPF_REG_CASE(15)
-#undef CTPF_REG_CASE
-                default: TMVB_REQUIRE(false, TMVB_EINVAL, "tmvb_ctpf_estep: no register-tile kernel for KP=%d", h->KP);
-            }
-            TMVB_HIP(hipGetLastError());
-            continue;
-        }
-        hipStream_t st = h->reg_path ? h->aux[1] : h->aux[(bi & 1) ^ 1];
-        const size_t lds = ctpf_tile_bytes(b.tile_rows, h->KP);
-        auto launch = [&](auto kern) -> int {
-            if (lds > TMVB_MAX_TILE_BYTES)                // long documents: the whole row set resident in up to 156 KiB of LDS
-                TMVB_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL(kern, grid, block, lds, st, p, b.first, b.tile_rows);
-            return TMVB_OK;
-        };
-        int lrc = (h->nslot > 4) ? launch(ctpf_estep_kernel<0, 8>) : (h->nslot > 2) ? launch(ctpf_estep_kernel<0, 4>)
-                  : (h->nslot == 2) ? ((p.LPR == 25) ? launch(ctpf_estep_kernel<25, 2>) : launch(ctpf_estep_kernel<0, 2>))
-                  : (p.LPR == 13) ? launch(ctpf_estep_kernel<13, 1>) : (p.LPR == 3) ? launch(ctpf_estep_kernel<3, 1>) : launch(ctpf_estep_kernel<0, 1>);
+    for (const ctpf_launch& b : h->plan) {
+        int lrc = ctpf_launch_docs(h, p, b, b.role == tmvb_role::CHAIN ? ctx->stream : b.role == tmvb_role::LONG ? h->aux[1] : h->aux[0]);
         if (lrc) return lrc;
         TMVB_HIP(hipGetLastError());
     }
     for (int a = 0; a < 2; ++a) {
-        if (a == 0 && !aux0_used) continue;                   // aux[0] carried nothing in this plan
+        if (a == 0 && !h->aux0_used) continue;                // aux[0] carried nothing in this plan
         TMVB_HIP(hipEventRecord(h->ev_join[a], h->aux[a]));
         TMVB_HIP(hipStreamWaitEvent(ctx->stream, h->ev_join[a], 0));
     }

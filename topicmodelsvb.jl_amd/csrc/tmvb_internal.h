@@ -75,16 +75,12 @@ struct tmvb_ctx {
     size_t lds_per_cu = 160 * 1024;
 };
 
-// One launch bucket of the per-document kernels: documents [first, first+count) of doc_order,
+// One launch bucket of the LDS-tile per-document kernels: documents [first, first+count) of doc_order,
 // all with at most `tile_rows` rows (or more, for the last bucket, which streams chunks).
+// (LDA and CTPF have more kernels than that: their launch records are in tmvb_estep_plan.h.)
 struct tmvb_bucket {
     int64_t first = 0, count = 0;
     int32_t tile_rows = 0;
-    int32_t reg_tiles = 0;     // > 0: register-tile kernel with this many 64-token tiles (no LDS tile)
-    int32_t piece = 0;         // pipelined E-step: which statistics pass consumes this bucket's documents
-    int32_t waves = 1;         // > 1: register-tile kernel with one workgroup of `waves` waves per (long) document
-    int32_t grid_np = 0;       // > 0: grid-tile kernel (tmvb_gridtile.h) with this many token PAIRS per lane (<= 32 grid_np tokens)
-    int32_t grid_np2 = 0;      // CTPF: reader pairs per lane of the grid-tile kernel
 };
 
 // Inverted (id-major) index over a CSR token stream, cut into chunks of at most TMVB_CHUNK tokens.

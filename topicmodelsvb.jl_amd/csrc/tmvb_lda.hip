@@ -27,8 +27,17 @@
 //
 // Roofline: HBM/gather-bound by byte count, VALU-issue bound in practice.  Algorithmic
 // bytes per outer iteration: nnz*(8 + 4K + 4K) + 12*M*K + 12*K*V + 4*(M+1).
+//
+// Host half (from `struct tmvb_lda` down), the E-step's launch layer -- what decides -> what it serves
+//   lda_build_plan, lda_cut_pieces (tmvb_estep_plan.h), called by tmvb_lda_create: document order + one lda_launch per kernel launch (kind, documents,
+//       stream role, piece);  lda_piece_count: how many statistics passes
+//   lda_estep_impl: forks the streams, issues the plan record by record through lda_launch_docs, opens a piece's statistics pass behind the chain's last
+//       launch of that piece (close_pieces), then the side chain (Elogtheta column sums, the ELBO's per-document half)
+//   lda_launch_docs: a record's kind -> lda_launch_grid<LPR> / lda_launch_reg<LPR, TMAX> (tmvb_dispatch_lpr<25>) or lda_estep_kernel<NS, LPR_T> (LDS tile)
+//   lda_elbo_enqueue: update_elbo!'s three forms -> lda_elbo_reg_kernel<LPR, WITH_PW> (tmvb_dispatch_lpr<25>), lda_elbo_kernel<NS>, the decomposed form
 #define TMVB_TS_LOGZ 1            // this translation unit instantiates the log-normaliser forms of the statistics pass (update_elbo!)
 #include "tmvb_common_kernels.h"
+#include "tmvb_estep_plan.h"
 #include "tmvb_train.h"
 #include "tmvb_call.h"
 #include "tmvb_handle.h"
@@ -477,8 +486,6 @@ __global__ __launch_bounds__(64) void lda_estep_reg_kernel(LdaParams p, int64_t 
     lda_estep_reg_body<LPR, T>(p, d, off, (int)(p.doc_ptr[d + 1] - off), topic_of_lane);
 }
 
-// long documents: one workgroup of TMVB_LONG_WAVES waves per document (see lda_estep_reg_body, W > 1)
-#define TMVB_LONG_WAVES 4
 template <int LPR, int T>
 __global__ __launch_bounds__(64 * TMVB_LONG_WAVES) void lda_estep_reg_long_kernel(LdaParams p, int64_t first,
                                                                                  const int* __restrict__ topic_of_lane)
@@ -1022,22 +1029,6 @@ __global__ __launch_bounds__(256) void lda_elbo_doc_kernel(int K, int64_t M, con
     if (tid == 0) block_val[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
-#define TMVB_REG_ANY_TILES 99   // bucket of register-tile documents with mixed tile counts (lda_estep_reg_any_kernel)
-#define TMVB_GRID_ANY_NP 99     // bucket of grid-tile documents with mixed lengths (lda_estep_grid_any_kernel)
-#define TMVB_GRID_TT_NP 1       // bucket of documents of <= 64 unique terms on the two-copy kernel (lda_estep_tt_kernel; KP <= 60)
-
-// token pairs per lane of the widest grid-tile instantiation: 2 NP LPR tile registers + 2 LPR accumulators + ~40 must stay
-// within the 256 architectural VGPRs.  KP <= 60: 6 pairs (documents of <= 192 unique terms per wave), KP <= 76: 4, KP <= 100: 3.
-constexpr int lda_grid_np_max(int lpr) { return lpr <= 15 ? 6 : lpr <= 19 ? 4 : 3; }
-
-// token-pair classes of the grid-tile kernel: a document runs the smallest instantiated NP (2, 3, 4, 6 up to the maximum) that holds it
-static inline int lda_grid_np_class(int64_t n, int np_max)
-{
-    const int64_t np = (n + 31) / 32;
-    const int c = np <= 2 ? 2 : np <= 3 ? 3 : np <= 4 ? 4 : 6;
-    return c <= np_max ? c : np_max;
-}
-
 // All grid-tile documents of a SMALL corpus / shard in one launch (the pair count is read per document, wave-uniform)
 template <int LPR>
 __global__ __launch_bounds__(64) void lda_estep_grid_any_kernel(LdaParams p, int64_t first, const int* __restrict__ topic_of_lane)
@@ -1059,13 +1050,16 @@ __global__ __launch_bounds__(64) void lda_estep_grid_any_kernel(LdaParams p, int
 // (A/B on one box, alternating).  LDA's sweeps keep a SIMD busier than CTPF's one- or two-sweep documents do, and the second launch costs a
 // cross-stream join in a 0.17 ms iteration.)
 template <int LPR>
-static void lda_launch_grid(int np, dim3 grid, dim3 block, hipStream_t st, const LdaParams& p, int64_t first, const int* tol)
+static void lda_launch_grid(const lda_launch& b, hipStream_t st, const LdaParams& p, const int* tol)
 {
     constexpr int NPM = lda_grid_np_max(LPR);
-    if (block.x == 128) { hipLaunchKernelGGL((lda_estep_grid_long_kernel<LPR, NPM, 2>), grid, block, 0, st, p, first, tol); return; }
-    if (block.x == 256) { hipLaunchKernelGGL((lda_estep_grid_long_kernel<LPR, NPM, 4>), grid, block, 0, st, p, first, tol); return; }
-    if (np == TMVB_GRID_ANY_NP) hipLaunchKernelGGL((lda_estep_grid_any_kernel<LPR>), grid, block, 0, st, p, first, tol);
-    else if (np == TMVB_GRID_TT_NP) {
+    const dim3 grid((unsigned)b.count), block(64 * (unsigned)b.waves);
+    const int64_t first = b.first;
+    const int np = b.n;
+    if (b.kind == lda_kind::GRID_LONG && b.waves == 2) hipLaunchKernelGGL((lda_estep_grid_long_kernel<LPR, NPM, 2>), grid, block, 0, st, p, first, tol);
+    else if (b.kind == lda_kind::GRID_LONG) hipLaunchKernelGGL((lda_estep_grid_long_kernel<LPR, NPM, 4>), grid, block, 0, st, p, first, tol);
+    else if (b.kind == lda_kind::GRID_ANY) hipLaunchKernelGGL((lda_estep_grid_any_kernel<LPR>), grid, block, 0, st, p, first, tol);
+    else if (b.kind == lda_kind::TWO_COPY) {
         if constexpr (LPR <= 15) hipLaunchKernelGGL((lda_estep_tt_kernel<LPR>), grid, block, 0, st, p, first);
     }
     else if (np <= 2) hipLaunchKernelGGL((lda_estep_grid_kernel<LPR, 2>), grid, block, 0, st, p, first, tol);
@@ -1074,18 +1068,21 @@ static void lda_launch_grid(int np, dim3 grid, dim3 block, hipStream_t st, const
     else hipLaunchKernelGGL((lda_estep_grid_kernel<LPR, (NPM >= 6 ? 6 : NPM)>), grid, block, 0, st, p, first, tol);
 }
 
-// register-tile launch for a bucket of `tiles`-tile documents (instantiates T = 1..TMAX only)
-template <int LPR, int TMAX>
-static void lda_launch_reg(int tiles, dim3 grid, dim3 block, hipStream_t st, const LdaParams& p, int64_t first, const int* tol)
+// register-tile launch for documents of b.n tiles (instantiates T = 1..TMAX only)
+template <int LPR, int TMAX = lda_reg_max_tiles(LPR)>
+static void lda_launch_reg(const lda_launch& b, hipStream_t st, const LdaParams& p, const int* tol)
 {
-    if (block.x > 64) {            // one workgroup of TMVB_LONG_WAVES waves per long document
+    const dim3 grid((unsigned)b.count), block(64 * (unsigned)b.waves);
+    const int64_t first = b.first;
+    const int tiles = b.n;
+    if (b.kind == lda_kind::REG_LONG) {            // one workgroup of TMVB_LONG_WAVES waves per long document
         if (tiles <= 1) hipLaunchKernelGGL((lda_estep_reg_long_kernel<LPR, 1>), grid, block, 0, st, p, first, tol);
         else if (tiles == 2 || TMAX == 2) hipLaunchKernelGGL((lda_estep_reg_long_kernel<LPR, (TMAX >= 2 ? 2 : 1)>), grid, block, 0, st, p, first, tol);
         else if (tiles == 3 || TMAX == 3) hipLaunchKernelGGL((lda_estep_reg_long_kernel<LPR, (TMAX >= 3 ? 3 : 1)>), grid, block, 0, st, p, first, tol);
         else hipLaunchKernelGGL((lda_estep_reg_long_kernel<LPR, (TMAX >= 4 ? 4 : 1)>), grid, block, 0, st, p, first, tol);
         return;
     }
-    if (tiles == TMVB_REG_ANY_TILES) hipLaunchKernelGGL((lda_estep_reg_any_kernel<LPR, TMAX>), grid, block, 0, st, p, first, tol);
+    if (b.kind == lda_kind::REG_ANY) hipLaunchKernelGGL((lda_estep_reg_any_kernel<LPR, TMAX>), grid, block, 0, st, p, first, tol);
     else if (tiles <= 1) hipLaunchKernelGGL((lda_estep_reg_kernel<LPR, 1>), grid, block, 0, st, p, first, tol);
     else if (tiles == 2 || TMAX == 2) hipLaunchKernelGGL((lda_estep_reg_kernel<LPR, (TMAX >= 2 ? 2 : 1)>), grid, block, 0, st, p, first, tol);
     else if (tiles == 3 || TMAX == 3) hipLaunchKernelGGL((lda_estep_reg_kernel<LPR, (TMAX >= 3 ? 3 : 1)>), grid, block, 0, st, p, first, tol);
@@ -1117,8 +1114,7 @@ struct tmvb_lda : tmvb_model_base {      // d_stats: S (K*V) | Elogtheta_sum (K)
     float* d_ts_partial = nullptr;     // [n_slots][K+1]
     int* d_topic_of_lane = nullptr;    // register-tile kernel lane maps
     int* d_grid_topic_of_lane = nullptr;   // grid-tile kernel lane map (tmvb_gridtile.h)
-    bool grid_path = false;            // KP <= 100 with recomputed statistics weights: documents of <= 32 grid_np_max terms use lda_estep_grid_kernel
-    int grid_np_max = 0;               // lda_grid_np_max(KP / 4)
+    bool grid_path = false;            // KP <= 100 with recomputed statistics weights: documents of <= 32 lda_grid_np_max(KP / 4) terms use lda_estep_grid_kernel
     bool reg_path = false;             // K <= 64 with a specialised LPR: short documents use lda_estep_reg_kernel
     int32_t* d_doc_order = nullptr;
     double* d_partial = nullptr;       // [TMVB_REDUCE_BLOCKS][K]
@@ -1126,8 +1122,8 @@ struct tmvb_lda : tmvb_model_base {      // d_stats: S (K*V) | Elogtheta_sum (K)
     double* d_esum = nullptr;          // [K]
     double* d_doc_val = nullptr;       // [M]
     int* d_iters = nullptr;
-    std::vector<tmvb_bucket> buckets;
-    // the length buckets of one E-step are independent: they are issued round-robin on a few
+    std::vector<lda_launch> plan;      // the E-step's document-kernel launches in issue order (lda_build_plan, lda_cut_pieces)
+    // the launches of one E-step are independent: they are issued on a few
     // auxiliary streams (fork/join on the context's stream) so that their tails overlap
     static constexpr int NAUX = 4;
     hipStream_t aux[NAUX] = {nullptr, nullptr, nullptr, nullptr};
@@ -1188,87 +1184,6 @@ struct tmvb_lda : tmvb_model_base {      // d_stats: S (K*V) | Elogtheta_sum (K)
     bool own_globals = true, own_aux = true;
 };
 
-static bool lda_reg_lpr_supported(int lpr) { return lpr >= 1 && lpr <= 25 && (lpr & 1); }   // every KP = 4 * odd <= 100
-// 64-token register tiles per document: the tile costs T * KP VGPRs of the 512 available per lane
-// tiles * KP + KP / 4 + ~35 VGPRs must stay within the 256 architectural VGPRs (beyond that the tile spills to AGPRs;
-// measured still ahead of the LDS-tile kernel at KP = 100, T = 3)
-static int lda_reg_max_tiles(int lpr) { return lpr <= 13 ? 4 : (lpr <= 17 || lpr == 25) ? 3 : 2; }
-
-static int lda_piece_count(const tmvb_lda* h);
-
-static void lda_build_buckets(tmvb_lda* h, std::vector<int32_t>& order)
-{
-    const std::vector<int64_t>& len = h->corp->h_doc_len;
-    order.resize(h->M);
-    std::iota(order.begin(), order.end(), 0);
-    std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) { return len[x] > len[y]; });
-    h->buckets.clear();
-    const int max_tiles = lda_reg_max_tiles(h->KP / 4);
-    const int64_t reg_max = h->grid_path ? 32 * h->grid_np_max : h->reg_path ? 64 * max_tiles : -1;
-    // documents longer than reg_max: LDS-tile kernel
-    // long documents get up to 156 KiB of LDS (one workgroup per CU): a tile that holds the whole document is
-    // gathered once per E-step, a streamed one once per sweep
-    // Documents between 64 T and 64 T W unique terms keep the register-tile arithmetic with one workgroup of
-    // W = TMVB_LONG_WAVES waves each (lda_estep_reg_long_kernel); only what is longer still goes through LDS.
-    const bool long_reg = h->reg_path;
-    const int64_t long_max = long_reg ? (int64_t)64 * max_tiles * TMVB_LONG_WAVES : reg_max;
-    int64_t pos = tmvb_build_lds_buckets(len, order, h->M, h->KP, long_max, 3, h->buckets, TMVB_BIG_TILE_BYTES);
-    // grid-tile kernel with 4 / 2 waves per document: up to 768 / 384 unique terms
-    const int64_t grid_long_max = (h->grid_path && long_reg) ? (int64_t)32 * h->grid_np_max * 4 : 0;
-    if (long_reg) {
-        for (int T = max_tiles; T >= 1 && pos < h->M; --T) {   // (KP = 100, T = 3 spills to AGPRs and is still 2.8x the LDS kernel)
-            const int64_t lo = std::max<int64_t>(std::max<int64_t>(64 * TMVB_LONG_WAVES * (int64_t)(T - 1), reg_max), grid_long_max);
-            int64_t cnt = 0;
-            while (pos + cnt < h->M && len[order[pos + cnt]] > lo) ++cnt;
-            if (cnt) { tmvb_bucket b{pos, cnt, 0, T}; b.waves = TMVB_LONG_WAVES; h->buckets.push_back(b); }
-            pos += cnt;
-        }
-        for (int Wv = 4; Wv >= 2 && grid_long_max > 0 && pos < h->M; Wv >>= 1) {
-            const int64_t lo = (int64_t)32 * h->grid_np_max * (Wv / 2);
-            int64_t cnt = 0;
-            while (pos + cnt < h->M && len[order[pos + cnt]] > lo) ++cnt;
-            if (cnt) { tmvb_bucket b{pos, cnt, 0, 1}; b.waves = Wv; b.grid_np = h->grid_np_max; h->buckets.push_back(b); }
-            pos += cnt;
-        }
-    }
-    // small corpora (one statistics pass): ONE launch for all register-tile documents, longest first
-    // (KP <= 60 only: with two result slots per lane the widest body costs the short documents a wave per SIMD --
-    //  measured at KP = 100, 16 k documents: 2.14 k it/s merged, 2.26 k separate)
-    if (h->reg_path && h->KP <= 60 && pos < h->M && lda_piece_count(h) == 1 && tmvb_env_str("TMVB_LDA_NO_MERGE") == nullptr) {
-        tmvb_bucket b{pos, h->M - pos, 0, TMVB_REG_ANY_TILES};
-        if (h->grid_path) b.grid_np = TMVB_GRID_ANY_NP;
-        h->buckets.push_back(b);
-        return;
-    }
-    if (h->grid_path) {
-        // grid-tile buckets, longest first: one launch per instantiated pair count
-        // (round 4) documents of <= 64 unique terms on the two-copy kernel (lda_estep_tt_kernel, KP <= 60): OFF by default -- measured A/B on
-        // SYN-NSF K = 50, alternating on one box: 1256 / 1267 it/s with it against 1287 / 1288 without (its ~125 VALU instructions per sweep
-        // against 200 are paid for with 29 dependent LDS broadcast reads per sweep and three waves per SIMD instead of four).  TMVB_LDA_TT=1
-        // selects it (read per model: tests/test_lda_gpu.py runs it against the oracle).
-        const bool tt = tmvb_env_on("TMVB_LDA_TT", false) && h->KP <= 60 && h->estride <= 64;
-        auto cls = [&](int64_t n) { return (tt && n <= 64) ? TMVB_GRID_TT_NP : lda_grid_np_class(n, h->grid_np_max); };
-        while (pos < h->M) {
-            const int np = cls(len[order[pos]]);
-            int64_t cnt = 0;
-            while (pos + cnt < h->M && cls(len[order[pos + cnt]]) == np) ++cnt;
-            tmvb_bucket b{pos, cnt, 0, (np + 1) / 2};        // reg_tiles > 0 marks a register bucket (chain stream, piece cuts)
-            b.grid_np = np;
-            h->buckets.push_back(b);
-            pos += cnt;
-        }
-        return;
-    }
-    // register-tile buckets: T = ceil(N / 64) tiles of 64 tokens
-    for (int T = max_tiles; T >= 1 && pos < h->M; --T) {
-        const int64_t lo = 64 * (int64_t)(T - 1);
-        int64_t cnt = 0;
-        while (pos + cnt < h->M && (len[order[pos + cnt]] > lo || T == 1)) ++cnt;
-        if (cnt) h->buckets.push_back({pos, cnt, 0, T});
-        pos += cnt;
-    }
-}
-
 static int lda_piece_count(const tmvb_lda* h)
 {
     if (!tmvb_termstats_recomputes(h->KP, h->e_padded) || !h->reg_path) return 1;
@@ -1280,50 +1195,6 @@ static int lda_piece_count(const tmvb_lda* h)
     const int64_t nnz = h->corp->info.nnz;
     if (nnz < (int64_t)(1 << 22)) return 1;
     return h->KP / 4 >= 25 ? 2 : 3;
-}
-
-// Cut the register-tile buckets where the running token count crosses a multiple of nnz / P.  The LDS-tile
-// (long-document) buckets go with the LAST piece: they are issued first, on their own stream, and have the
-// whole E-step to finish.  Fills doc_piece[d] and replaces h->buckets.
-static void lda_cut_pieces(tmvb_lda* h, const std::vector<int32_t>& order, int P, std::vector<int32_t>& doc_piece)
-{
-    const std::vector<int64_t>& len = h->corp->h_doc_len;
-    const int64_t nnz = std::max<int64_t>(h->corp->info.nnz, 1);
-    // cumulative token fractions at which a piece ends: the last pieces are smaller, because the statistics
-    // pass of the last piece has no document kernels left to hide under
-    std::vector<double> cum(P);
-    {
-        double tot = 0.0;
-        for (int q = 0; q < P; ++q) { cum[q] = 1.0 + 0.5 * (double)(P - 1 - q) / (double)std::max(P - 1, 1); tot += cum[q]; }
-        double run = 0.0;
-        for (int q = 0; q < P; ++q) { run += cum[q] / tot; cum[q] = run; }
-        cum[P - 1] = 2.0;
-    }
-    auto piece_of = [&](int64_t run) { const double x = (double)run / (double)nnz; int q = 0; while (q < P - 1 && x >= cum[q]) ++q; return q; };
-    doc_piece.assign(h->M, 0);
-    std::vector<tmvb_bucket> cut;
-    int64_t run = 0;
-    for (const tmvb_bucket& b : h->buckets) {
-        if (b.reg_tiles == 0 || b.waves > 1) {               // LDS-tile and workgroup-per-document buckets: last piece, aux[1]
-            tmvb_bucket c = b; c.piece = P - 1;
-            for (int64_t q = b.first; q < b.first + b.count; ++q) doc_piece[order[q]] = P - 1;
-            cut.push_back(c);
-            continue;
-        }
-        int64_t start = b.first;
-        int piece = piece_of(run);
-        for (int64_t q = b.first; q < b.first + b.count; ++q) {
-            const int pq = piece_of(run);
-            if (pq != piece) {
-                if (q > start) { tmvb_bucket c = b; c.first = start; c.count = q - start; c.piece = piece; cut.push_back(c); }
-                start = q; piece = pq;
-            }
-            doc_piece[order[q]] = pq;
-            run += len[order[q]];
-        }
-        if (b.first + b.count > start) { tmvb_bucket c = b; c.first = start; c.count = b.first + b.count - start; c.piece = piece; cut.push_back(c); }
-    }
-    h->buckets.swap(cut);
 }
 
 static int lda_join_side(tmvb_lda* h)
@@ -1398,33 +1269,31 @@ extern "C" int tmvb_lda_create(tmvb_ctx* ctx, tmvb_corpus* corp, int32_t K, tmvb
     }
     // grid-tile kernel (tmvb_gridtile.h): KP <= 100 (LPR <= 25; up to 6 / 4 / 3 token pairs per lane for KP <= 60 / 76 / 100 within 256 VGPRs), statistics pass
     // recomputes the token weights (nothing per token is stored); TMVB_LDA_GRID=0 keeps the lane = token register tile
-    h->grid_np_max = lda_grid_np_max(h->KP / 4);
     h->grid_path = h->reg_path && h->KP <= 100 && tmvb_termstats_recomputes(h->KP, h->e_padded) &&
                    (uint64_t)h->V * (uint64_t)h->KP * 4u < (1ull << 32) &&            // rows are addressed by 32-bit byte offsets
                    tmvb_env_on("TMVB_LDA_GRID", true);
     if (h->grid_path) {
         std::vector<int> tol;
-        switch (h->KP / 4) {
-#define LDA_GRID_MAP_CASE(LPRV) case LPRV: tmvb_grid_lane_map_fill<LPRV>(tol); break;
-            LDA_GRID_MAP_CASE(1) LDA_GRID_MAP_CASE(3) LDA_GRID_MAP_CASE(5) LDA_GRID_MAP_CASE(7) LDA_GRID_MAP_CASE(9) LDA_GRID_MAP_CASE(11)
-            LDA_GRID_MAP_CASE(13) LDA_GRID_MAP_CASE(15) LDA_GRID_MAP_CASE(17) LDA_GRID_MAP_CASE(19) LDA_GRID_MAP_CASE(21) LDA_GRID_MAP_CASE(23)
-            LDA_GRID_MAP_CASE(25)
-#undef LDA_GRID_MAP_CASE
-            default: h->grid_path = false;
-        }
-        if (h->grid_path) {
-            if ((rc = h->mem.alloc(&h->d_grid_topic_of_lane, tol.size()))) return rc;
-            TMVB_HIP(hipMemcpy(h->d_grid_topic_of_lane, tol.data(), tol.size() * sizeof(int), hipMemcpyHostToDevice));
-        }
+        if ((rc = tmvb_dispatch_lpr<25>(h->KP / 4, [&](auto lpr) -> int { tmvb_grid_lane_map_fill<decltype(lpr)::value>(tol); return TMVB_OK; }))) return rc;
+        if ((rc = h->mem.alloc(&h->d_grid_topic_of_lane, tol.size()))) return rc;
+        TMVB_HIP(hipMemcpy(h->d_grid_topic_of_lane, tol.data(), tol.size() * sizeof(int), hipMemcpyHostToDevice));
     }
     std::vector<int32_t> order;
-    lda_build_buckets(h, order);
     {
         const int P = lda_piece_count(h);
+        lda_plan_flags pf;
+        pf.reg_path = h->reg_path; pf.grid_path = h->grid_path;
+        pf.one_launch = h->reg_path && h->KP <= 60 && P == 1 && tmvb_env_str("TMVB_LDA_NO_MERGE") == nullptr;
+        // (round 4) documents of <= 64 unique terms on the two-copy kernel (lda_estep_tt_kernel, KP <= 60): OFF by default -- measured A/B on
+        // SYN-NSF K = 50, alternating on one box: 1256 / 1267 it/s with it against 1287 / 1288 without (its ~125 VALU instructions per sweep
+        // against 200 are paid for with 29 dependent LDS broadcast reads per sweep and three waves per SIMD instead of four).  TMVB_LDA_TT=1
+        // selects it (read per model: tests/test_lda_gpu.py runs it against the oracle).
+        pf.two_copy = tmvb_env_on("TMVB_LDA_TT", false) && h->KP <= 60 && h->estride <= 64;
+        lda_build_plan(corp->h_doc_len, h->KP, pf, order, h->plan);
         size_t slots = 0;
         if (P > 1) {
             std::vector<int32_t>& doc_piece = h->doc_piece;
-            lda_cut_pieces(h, order, P, doc_piece);
+            lda_cut_pieces(corp->h_doc_len, corp->info.nnz, order, P, h->plan, doc_piece);
             h->pieces.resize(P);
             h->ev_piece.assign(P, nullptr);
             // the pieces' inverted indices are independent host work (a counting sort over the corpus each, ~50 ms at SYN-NSF's size): one thread per piece
@@ -1552,11 +1421,31 @@ extern "C" int tmvb_lda_get_state(tmvb_lda* h, double* alpha, double* beta, doub
 
 static int lda_estep_impl(tmvb_lda* h, int32_t viter, double vtol);
 
-// stream of the side chain (TMVB_LDA_SIDE_STREAM: experiment with the stream -> hardware-queue mapping)
-static int lda_side_index()
+// one record of the plan on its stream
+static int lda_launch_docs(tmvb_lda* h, const LdaParams& p, const lda_launch& b, hipStream_t st)
 {
-    static const int ix = [] { const int v = tmvb_env_int("TMVB_LDA_SIDE_STREAM", (int)tmvb_lda::SIDE); return (v >= 0 && v < (int)tmvb_lda::NAUX) ? v : (int)tmvb_lda::SIDE; }();
-    return ix;
+    switch (b.kind) {
+        case lda_kind::GRID: case lda_kind::GRID_ANY: case lda_kind::GRID_LONG: case lda_kind::TWO_COPY:
+            return tmvb_dispatch_lpr<25>(p.LPR, [&](auto lpr) -> int { lda_launch_grid<decltype(lpr)::value>(b, st, p, h->d_grid_topic_of_lane); return TMVB_OK; });
+        case lda_kind::REG: case lda_kind::REG_ANY: case lda_kind::REG_LONG:
+            return tmvb_dispatch_lpr<25>(p.LPR, [&](auto lpr) -> int { lda_launch_reg<decltype(lpr)::value>(b, st, p, h->d_topic_of_lane); return TMVB_OK; });
+        case lda_kind::LDS_TILE: break;
+    }
+    const size_t lds = tmvb_tile_bytes(b.tile_rows, h->KP);
+    return dispatch_nslot(h->nslot, [&](auto ns) -> int {
+        constexpr int NS = decltype(ns)::value;
+        auto launch = [&](auto kern) -> int {
+            if (lds > TMVB_MAX_TILE_BYTES)
+                TMVB_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            hipLaunchKernelGGL(kern, dim3((unsigned)b.count), dim3(64), lds, st, p, b.first, b.tile_rows);
+            return TMVB_OK;
+        };
+        if (NS == 1 && p.LPR == 13) return launch(lda_estep_kernel<1, 13>);
+        if (NS == 1 && p.LPR == 3) return launch(lda_estep_kernel<1, 3>);
+        if (NS == 1 && p.LPR == 5) return launch(lda_estep_kernel<1, 5>);
+        if (NS == 2 && p.LPR == 25) return launch(lda_estep_kernel<2, 25>);
+        return launch(lda_estep_kernel<NS, 0>);
+    });
 }
 
 extern "C" int tmvb_lda_estep(tmvb_lda* h, int32_t viter, double vtol)
@@ -1598,11 +1487,9 @@ static int lda_estep_impl(tmvb_lda* h, int32_t viter, double vtol)
     p.viter = viter; p.vtol = (float)vtol;
     p.store_w = tmvb_termstats_recomputes(h->KP, h->e_padded) ? 0 : 1;
     if (h->timing) TMVB_HIP(hipEventRecord(h->ev0, ctx->stream));
-    // Stream plan: the register-tile buckets run back to back on aux[0] (piece after piece), the LDS-tile
-    // buckets (long documents; every bucket when K has no register-tile instantiation) on aux[1] -- a single
-    // long document is a latency-bound 0.1-0.2 ms and must not queue ahead of the short ones -- and the
-    // statistics pass of each piece on the context's stream.  (More streams only alias the same hardware queues.)
-    const int nb = (int)h->buckets.size();
+    // Stream plan (the records' roles, tmvb_estep_plan.h): the chain's launches run back to back, piece after piece; the long documents
+    // (every launch when K has no register-tile instantiation) run on aux[1] -- a single long document is a latency-bound 0.1-0.2 ms and
+    // must not queue ahead of the short ones.  (More streams only alias the same hardware queues.)
     const int P = std::max<int>((int)h->pieces.size(), 1);      // 1: one statistics pass over the corpus' own index
     auto piece_index = [&](int q) -> const tmvb_inv_index& { return h->pieces.empty() ? h->corp->term_index : h->pieces[q]; };
     // One statistics pass (small corpora, one GPU's shard of a sharded run): the critical chain document kernels ->
@@ -1613,10 +1500,8 @@ static int lda_estep_impl(tmvb_lda* h, int32_t viter, double vtol)
     // before the last run on aux[0] in the chain's shadow (where an event hop costs nothing), and the last pass -- the one
     // nothing hides -- follows the last document kernel on the context's stream, as do the M-step and the next E-step: no
     // cross-stream hop is left on the critical path of an iteration (there were two, ~20 us each, around the last pass).
-    // TMVB_LDA_CHAIN_AUX=1 restores the round-2 plan (chain on aux[0], every pass on the context's stream).
-    static const bool chain_aux = tmvb_env_on("TMVB_LDA_CHAIN_AUX", false);
-    hipStream_t chain_st = (h->reg_path && (P == 1 || !chain_aux)) ? ctx->stream : h->aux[0];
-    const bool shadow_stats = P > 1 && chain_st == ctx->stream;       // passes 0 .. P-2 on aux[0]
+    // (Round 2's plan -- the chain on aux[0], every pass on the context's stream -- measured 1228 it/s against 1268 and was removed.)
+    hipStream_t chain_st = h->reg_path ? ctx->stream : h->aux[0];     // no register path: LDS-tile launches only, alternating aux[1] / aux[0]
     if (chain_st == ctx->stream) { int jrc = lda_join_side(h); if (jrc) return jrc; }   // update_alpha! of the last iteration
     if (h->elbo_pending) {                                  // (the chain on aux[0]: the document kernels there rewrite what lda_elbo_doc_kernel reads)
         TMVB_HIP(hipStreamWaitEvent(ctx->stream, h->ev_elbo, 0));
@@ -1679,12 +1564,11 @@ static int lda_estep_impl(tmvb_lda* h, int32_t viter, double vtol)
     // Round 5: the passes before the last accumulate in order in d_stats on aux[0]; the LAST pass, on the context's stream behind the last document
     // kernel, used to wait for them (round 4's timeline: last document kernel done at 589 us, pass 2 + its combine at 625 us, one cross-queue hop, last
     // pass 637 - 705 us -- 48 us of a 750 us iteration with the chain waiting).  It now writes a buffer of its own (and its own multi-chunk partials) and
-    // starts at once; the join with aux[0] moves behind it, and update_beta!'s column-sum pass adds the two buffers on its way.  One context only (a
-    // sharded handle all-reduces d_stats); TMVB_LDA_SPLIT_OUT=0: the round-4 order.
-    static const bool split_out_env = tmvb_env_on("TMVB_LDA_SPLIT_OUT", true);
+    // starts at once; the join with aux[0] moves behind it, and update_beta!'s column-sum pass adds the two buffers on its way (1312 it/s against 1283 in
+    // the round-4 order, same call).  One context only (a sharded handle all-reduces d_stats),
     // (round-5 advice) ... and only into the library's OWN statistics buffer: a host that bound its tensor (tmvb_lda_bind_stats, dist.py) may read it
     // directly between estep and update_beta!, and must see the whole of S there, not S minus the last piece
-    bool split_out = split_out_env && shadow_stats && h->own_stats && !h->distributed && h->comm == nullptr && !h->ar_live;
+    const bool split_out = P > 1 && h->own_stats && !h->distributed && h->comm == nullptr && !h->ar_live;
     if (split_out && !h->d_stats_b) {
         size_t slots = 1;
         for (const tmvb_inv_index& ix : h->pieces) slots = std::max(slots, (size_t)ix.n_slots);
@@ -1697,26 +1581,21 @@ static int lda_estep_impl(tmvb_lda* h, int32_t viter, double vtol)
     int piece_open = 0;                                 // pieces [0, piece_open) have their statistics pass issued
     auto close_pieces = [&](int upto) -> int {          // document kernels of pieces < upto are all issued
         for (; piece_open < upto; ++piece_open) {
-            if (piece_open == P - 1) {                  // the last piece also holds the long documents (aux[1])
+            const bool last = piece_open == P - 1;
+            hipStream_t pass_st = last ? ctx->stream : h->aux[0];         // the passes before the last: in the chain's shadow
+            if (last) {                                 // the last piece also holds the long documents (aux[1])
                 TMVB_HIP(hipEventRecord(h->ev_chain, chain_st));          // the chain's own document kernels, before the join below
                 TMVB_HIP(hipEventRecord(h->ev_join[1], h->aux[1]));
                 TMVB_HIP(hipStreamWaitEvent(chain_st, h->ev_join[1], 0));
             }
-            hipStream_t pass_st = ctx->stream;
-            if (shadow_stats) {
-                if (piece_open < P - 1) {                // in the chain's shadow: aux[0] waits for this piece's document kernels
-                    pass_st = h->aux[0];
-                    TMVB_HIP(hipEventRecord(h->ev_piece[piece_open], chain_st));
-                    TMVB_HIP(hipStreamWaitEvent(pass_st, h->ev_piece[piece_open], 0));
-                } else if (!split_out) {                 // the passes accumulate in order: the last one waits for aux[0]'s
-                    TMVB_HIP(hipEventRecord(h->ev_join[0], h->aux[0]));
-                    TMVB_HIP(hipStreamWaitEvent(ctx->stream, h->ev_join[0], 0));
-                }
-            } else {
+            if (!last || P == 1) {                      // the pass waits for this piece's document kernels where they ran on another stream
                 TMVB_HIP(hipEventRecord(h->ev_piece[piece_open], chain_st));
-                if (chain_st != ctx->stream) TMVB_HIP(hipStreamWaitEvent(ctx->stream, h->ev_piece[piece_open], 0));
+                if (pass_st != chain_st) TMVB_HIP(hipStreamWaitEvent(pass_st, h->ev_piece[piece_open], 0));
+            } else if (!split_out) {                    // the passes accumulate in order: the last one waits for aux[0]'s
+                TMVB_HIP(hipEventRecord(h->ev_join[0], h->aux[0]));
+                TMVB_HIP(hipStreamWaitEvent(ctx->stream, h->ev_join[0], 0));
             }
-            if (piece_open == P - 1 && h->ar_live) {     // tmvb_lda_estep_allreduce: slice by slice, an event behind each
+            if (last && h->ar_live) {     // tmvb_lda_estep_allreduce: slice by slice, an event behind each
                 const tmvb_inv_index& ix = h->pieces.empty() ? h->ar_index : h->pieces.back();
                 for (int k = 0; k < h->ar_slices; ++k) {
                     int rc = tmvb_launch_termstats(ctx, h->nslot, h->KP, h->e_padded, ix, with_logz(tp, piece_open), pass_st, h->ar_order[(size_t)k]);
@@ -1740,59 +1619,13 @@ static int lda_estep_impl(tmvb_lda* h, int32_t viter, double vtol)
         }
         return TMVB_OK;
     };
-    for (int bi = 0; bi < nb; ++bi) {
-        const tmvb_bucket& b = h->buckets[bi];
-        const bool chain = b.reg_tiles > 0 && b.waves == 1;   // single-wave register buckets: the piece chain on aux[0]
-        hipStream_t st = chain ? chain_st : h->aux[1];
-        if (!h->reg_path) st = h->aux[(bi & 1) ^ 1];          // LDS-tile buckets only: alternate the two streams
-        if (chain) { int rc = close_pieces(b.piece); if (rc) return rc; }
-        if (b.grid_np > 0) {
-            const dim3 grid((unsigned)b.count), block(64 * (unsigned)b.waves);
-            const int* tol = h->d_grid_topic_of_lane;
-            switch (p.LPR) {
-#define LDA_GRID_CASE(LPRV) case LPRV: lda_launch_grid<LPRV>(b.grid_np, grid, block, st, p, b.first, tol); break;
-                LDA_GRID_CASE(1) LDA_GRID_CASE(3) LDA_GRID_CASE(5) LDA_GRID_CASE(7) LDA_GRID_CASE(9) LDA_GRID_CASE(11) LDA_GRID_CASE(13)
-                LDA_GRID_CASE(15) LDA_GRID_CASE(17) LDA_GRID_CASE(19) LDA_GRID_CASE(21) LDA_GRID_CASE(23) LDA_GRID_CASE(25)
-#undef LDA_GRID_CASE
-                default: TMVB_REQUIRE(false, TMVB_EINVAL, "tmvb_lda_estep: no grid-tile kernel for KP=%d", h->KP);
-            }
-            TMVB_HIP(hipGetLastError());
-            continue;
-        }
-        if (b.reg_tiles > 0) {
-            const dim3 grid((unsigned)b.count), block(64 * (unsigned)b.waves);
-            const int* tol = h->d_topic_of_lane;
-            switch (p.LPR) {
-#define LDA_REG_CASE(LPRV, TMAX) case LPRV: lda_launch_reg<LPRV, TMAX>(b.reg_tiles, grid, block, st, p, b.first, tol); break;
-                LDA_REG_CASE(1, 4) LDA_REG_CASE(3, 4) LDA_REG_CASE(5, 4) LDA_REG_CASE(7, 4) LDA_REG_CASE(9, 4) LDA_REG_CASE(11, 4)
-                LDA_REG_CASE(13, 4) LDA_REG_CASE(15, 3) LDA_REG_CASE(17, 3) LDA_REG_CASE(19, 2) LDA_REG_CASE(21, 2) LDA_REG_CASE(23, 2)
-                LDA_REG_CASE(25, 3)
-#undef LDA_REG_CASE
-                default: TMVB_REQUIRE(false, TMVB_EINVAL, "tmvb_lda_estep: no register-tile kernel for KP=%d", h->KP);
-            }
-            TMVB_HIP(hipGetLastError());
-            continue;
-        }
-        const size_t lds = tmvb_tile_bytes(b.tile_rows, h->KP);
-        int rc = dispatch_nslot(h->nslot, [&](auto ns) -> int {
-            constexpr int NS = decltype(ns)::value;
-            const dim3 grid((unsigned)b.count), block(64);
-            auto launch = [&](auto kern) -> int {
-                if (lds > TMVB_MAX_TILE_BYTES)
-                    TMVB_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                hipLaunchKernelGGL(kern, grid, block, lds, st, p, b.first, b.tile_rows);
-                return TMVB_OK;
-            };
-            if (NS == 1 && p.LPR == 13) return launch(lda_estep_kernel<1, 13>);
-            if (NS == 1 && p.LPR == 3) return launch(lda_estep_kernel<1, 3>);
-            if (NS == 1 && p.LPR == 5) return launch(lda_estep_kernel<1, 5>);
-            if (NS == 2 && p.LPR == 25) return launch(lda_estep_kernel<2, 25>);
-            return launch(lda_estep_kernel<NS, 0>);
-        });
+    for (const lda_launch& b : h->plan) {
+        if (b.role == tmvb_role::CHAIN) { int rc = close_pieces(b.piece); if (rc) return rc; }
+        int rc = lda_launch_docs(h, p, b, b.role == tmvb_role::CHAIN ? chain_st : b.role == tmvb_role::LONG ? h->aux[1] : h->aux[0]);
         if (rc) return rc;
         TMVB_HIP(hipGetLastError());
     }
-    hipStream_t side = h->aux[lda_side_index()];
+    hipStream_t side = h->aux[tmvb_lda::SIDE];
     {
         int rc = close_pieces(P);
         if (rc) return rc;
@@ -1831,8 +1664,7 @@ static int lda_estep_impl(tmvb_lda* h, int32_t viter, double vtol)
                 TMVB_HIP(hipFuncSetAttribute((const void*)lda_elbo_doc_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
                 h->elbo_doc_lds_set = (int)lds;
             }
-            static const bool own_stream = tmvb_env_on("TMVB_LDA_ELBO_STREAM", true);   // 0: in a row on the side stream (A/B)
-            hipStream_t es = own_stream ? h->aux[tmvb_lda::ELBO] : side;
+            hipStream_t es = h->aux[tmvb_lda::ELBO];              // a stream of its own, not in a row on the side stream
             // the kernel starts behind the column sums of Elogtheta (ev_acopy re-recorded behind them) rather than with the end of the document kernels: right
             // beside the last statistics pass it slows that pass more than it gains -- time to the plateau 1.262 / 1.247 / 1.239 s against 1.263 / 1.281 / 1.266 s,
             // alternating in one call
@@ -2077,7 +1909,7 @@ extern "C" int tmvb_lda_update_alpha(tmvb_lda* h, int32_t niter, double ntol)
     tmvb_ctx* ctx = h->ctx;
     TMVB_HIP(hipSetDevice(ctx->device));
     const float* ef = h->distributed ? h->d_stats + (size_t)h->K * h->V : nullptr;
-    hipStream_t side = h->aux[lda_side_index()];
+    hipStream_t side = h->aux[tmvb_lda::SIDE];
     // One context: the Newton step needs nothing but Elogtheta_sum, which the E-step left on this very
     // stream, so it starts under the statistics pass.  Document-sharded: it needs the all-reduced sums, i.e.
     // the context's stream as of the preceding update_beta call (or as of now).
@@ -2124,20 +1956,16 @@ static int lda_elbo_enqueue(tmvb_lda* h)
     } else if (h->M > 0 && h->reg_path) {
         const dim3 grid((unsigned)h->M), block(64);
         use_pw = h->pw_valid && !h->pw_diff;
-        switch (h->KP / 4) {
-#define LDA_ELBO_CASE(LPRV) case LPRV: \
-            if (use_pw) hipLaunchKernelGGL((lda_elbo_reg_kernel<LPRV, false>), grid, block, 0, ctx->stream, h->K, h->d_doc_order, h->corp->d_doc_ptr, \
-                               h->corp->d_terms, h->corp->d_counts, h->d_alpha_d, h->d_beta[h->cur], h->d_beta[h->cur ^ 1], \
-                               h->d_gamma, h->d_elog, h->d_elog_old, h->d_doc_val); \
-            else hipLaunchKernelGGL((lda_elbo_reg_kernel<LPRV, true>), grid, block, 0, ctx->stream, h->K, h->d_doc_order, h->corp->d_doc_ptr, \
-                               h->corp->d_terms, h->corp->d_counts, h->d_alpha_d, h->d_beta[h->cur], h->d_beta[h->cur ^ 1], \
-                               h->d_gamma, h->d_elog, h->d_elog_old, h->d_doc_val); \
-            break;
-            LDA_ELBO_CASE(1) LDA_ELBO_CASE(3) LDA_ELBO_CASE(5) LDA_ELBO_CASE(7) LDA_ELBO_CASE(9) LDA_ELBO_CASE(11) LDA_ELBO_CASE(13)
-            LDA_ELBO_CASE(15) LDA_ELBO_CASE(17) LDA_ELBO_CASE(19) LDA_ELBO_CASE(21) LDA_ELBO_CASE(23) LDA_ELBO_CASE(25)
-#undef LDA_ELBO_CASE
-            default: TMVB_REQUIRE(false, TMVB_EINVAL, "tmvb_lda_update_elbo: no token-parallel kernel for KP=%d", h->KP);
-        }
+        int rc = tmvb_dispatch_lpr<25>(h->KP / 4, [&](auto lpr) -> int {
+            constexpr int LPR = decltype(lpr)::value;
+            auto launch = [&](auto kern) {
+                hipLaunchKernelGGL(kern, grid, block, 0, ctx->stream, h->K, h->d_doc_order, h->corp->d_doc_ptr, h->corp->d_terms, h->corp->d_counts, h->d_alpha_d,
+                                   h->d_beta[h->cur], h->d_beta[h->cur ^ 1], h->d_gamma, h->d_elog, h->d_elog_old, h->d_doc_val);
+            };
+            if (use_pw) launch(lda_elbo_reg_kernel<LPR, false>); else launch(lda_elbo_reg_kernel<LPR, true>);
+            return TMVB_OK;
+        });
+        if (rc) return rc;
         TMVB_HIP(hipGetLastError());
     } else if (h->M > 0) {
         int rc = dispatch_nslot(h->nslot, [&](auto ns) -> int {
@@ -2244,7 +2072,7 @@ extern "C" int tmvb_lda_sweep_hist(tmvb_lda* h, int64_t* hist, int32_t nbins) { 
 extern "C" int tmvb_lda_estep_launches(tmvb_lda* h, int32_t* n)
 {
     TMVB_REQUIRE(h && n, TMVB_EINVAL, "tmvb_lda_estep_launches: NULL argument");
-    *n = (int32_t)h->buckets.size();
+    *n = (int32_t)h->plan.size();
     return TMVB_OK;
 }
 
